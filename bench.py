@@ -13,6 +13,10 @@ is not already running under a launcher; under `python -m torch.distributed.run 
 it is one of the ranks.  Either way: one process per GPU, rank 0 prints ONE JSON line on stdout.  Inputs are
 resident in HBM before the timed region; the kernel duration for the roofline object comes from HIP events recorded
 on the stream the kernel runs on.
+
+A plain run does only what the headline needs: set up (shard, placement choice), warm up, time --steps steps, write
+--dump-outputs DIR if given, print the line.  --full adds what is measured or checked beside it: the device identity,
+the parity sample against the CPU oracle with cpu_baseline, and extra (the other configs' rates, BAM files).
 """
 from __future__ import annotations
 
@@ -38,25 +42,42 @@ MIN_BASEQ = 20
 # algorithmic bytes per cluster: read 2*(2*150) + 17, write 2*(150 + 2) + 4
 BYTES_PER_PAIR = 2 * (2 * L_READ) + L_BC + 2 * (L_READ + 2) + 4      # 925
 HBM_PEAK_GBS = 8000.0
+DUMP_ROWS = 32768               # --dump-outputs: clusters sampled from rank 0's shard (their 2 x 150 output bytes as float32: 39 MB)
+DUMP_SEED = 4242
+
+
+def steps_arg(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError("the number of timed steps must be at least 1")
+    return v
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=steps_arg, default=20, help="timed steps (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the device identity from rocm-smi, the parity sample "
+                         "against the CPU oracle with cpu_baseline (--cpu-sample, --cpu-threads, --no-all-cores, --faithful-reads) and "
+                         "extra (rates of the other configs, BAM files; --no-extra).  A plain run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64): the counters, "
+                         f"the outputs of {DUMP_ROWS} clusters drawn with a fixed seed, and whole-shard column sums and histograms")
     ap.add_argument("--pairs", type=int, default=62_500_000, help="clusters per GPU (default: configs[3] / 8)")
     ap.add_argument("--layout", choices=["soa", "blocked"], default=os.environ.get("SK_BENCH_LAYOUT", "soa"),
                     help="batch layout in HBM: row-major SoA matrices (with placement tuning the faster of the two) or tile-blocked "
                          "(one read range + one write range per 64-cluster tile)")
-    ap.add_argument("--cpu-sample", type=int, default=4_000_000, help="clusters timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=4_000_000, help="with --full: clusters checked against and timed on the CPU oracle (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=1,
                     help="threads for the CPU baseline (the reference's loops are single-threaded, so 1 is the faithful number; "
                          "more threads split the sample into slices)")
     ap.add_argument("--no-all-cores", action="store_true", help="skip cpu_baseline.all_cores (the restatement on every usable core)")
     ap.add_argument("--faithful-reads", type=int, default=1_000_000,
                     help="reads of cfg 2 / cfg 3 text run through the line-at-a-time oracle CLI for cpu_baseline.faithful (0 = skip)")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra.rates (device-resident rates of the other configs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip extra.rates (device-resident rates of the other configs)")
     ap.add_argument("--gen-chunk", type=int, default=2_000_000)
     ap.add_argument("--placements", type=int, default=None,
                     help="candidate device buffers per big matrix (SoA) / per buffer (blocked): allocated at start-up, the pass is timed "
@@ -287,6 +308,54 @@ def unpack_blocked(torch, lay, bout, nt):
     if lay.out_assign >= 0:
         res["assign"] = v[:, lay.out_assign:lay.out_assign + 256].contiguous().view(torch.int32).reshape(nt * 64)
     return res
+
+
+def dump_outputs(torch, out_dir, n, counts, lay=None, bout=None, assign=None, lowest_k=None, out_seq=None):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files (exact: every value is an
+    integer below 2^24, or 2^53 for the float64 sums).  counts = the u64[S+3] counters; rows = DUMP_ROWS clusters of this shard
+    drawn with DUMP_SEED (sorted), with their assign, lowest_k [mate] and out_seq [mate][150]; over the whole shard, per mate:
+    the byte sum and the 'N' count of every out_seq column, and the histogram of lowest_k (bin 151: anything above 150).
+    SoA: assign / lowest_k / out_seq are the timed pass's tensors; blocked: its output buffer bout, read through the layout."""
+    os.makedirs(out_dir, exist_ok=True)
+    dev = counts.device
+
+    def soa(r0, r1):
+        """(assign, [lowest_k], [out_seq]) of rows r0:r1 (r0 a multiple of 64)"""
+        if lay is None:
+            return assign[r0:r1], [x[r0:r1] for x in lowest_k], [x[r0:r1] for x in out_seq]
+        t0, t1 = r0 // 64, (r1 + 63) // 64
+        u = unpack_blocked(torch, lay, bout[t0 * lay.out_block:t1 * lay.out_block], t1 - t0)
+        m = r1 - r0
+        return u["assign"][:m], [x[:m] for x in u["lowest_k"]], [x[:m] for x in u["out_seq"]]
+
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_ROWS, n), replace=False))
+    idx = torch.from_numpy(rows).to(dev)
+    if lay is None:
+        s_assign, s_k, s_seq = assign[idx], [x[idx] for x in lowest_k], [x[idx] for x in out_seq]
+    else:
+        tiles, inv = torch.unique(idx // 64, return_inverse=True)
+        u = unpack_blocked(torch, lay, bout.view(-1, lay.out_block)[tiles].reshape(-1), tiles.numel())
+        pos = inv * 64 + idx % 64
+        s_assign, s_k, s_seq = u["assign"][pos], [x[pos] for x in u["lowest_k"]], [x[pos] for x in u["out_seq"]]
+    col_sum = torch.zeros((2, L_READ), dtype=torch.int64, device=dev)
+    col_n = torch.zeros((2, L_READ), dtype=torch.int64, device=dev)
+    k_hist = torch.zeros((2, L_READ + 2), dtype=torch.int64, device=dev)
+    chunk = 1 << 22
+    for r0 in range(0, n, chunk):
+        _, ks, ss = soa(r0, min(r0 + chunk, n))
+        for i in range(2):
+            col_sum[i] += ss[i].sum(0, dtype=torch.int64)
+            col_n[i] += (ss[i] == ord("N")).sum(0)
+            k = (ks[i].to(torch.int64) & 0xFFFF).clamp_(max=L_READ + 1)
+            k_hist[i] += torch.bincount(k, minlength=L_READ + 2)
+    arrays = {"counts": (counts.cpu().numpy(), np.float64), "rows": (rows, np.float64),
+              "assign": (s_assign.cpu().numpy(), np.float32),
+              "lowest_k": (np.stack([x.cpu().numpy().view(np.uint16) for x in s_k]), np.float32),
+              "out_seq": (np.stack([x.cpu().numpy() for x in s_seq]), np.float32),
+              "out_seq_column_sum": (col_sum.cpu().numpy(), np.float64), "out_seq_column_n": (col_n.cpu().numpy(), np.float64),
+              "lowest_k_hist": (k_hist.cpu().numpy(), np.float64)}
+    for name, (a, dt) in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(dt))
 
 
 def usable_cores() -> int:
@@ -890,7 +959,8 @@ def main():
         local_rank = 0
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    device = device_identity(local_rank)                             # a child process: started before this one touches the GPU (every rank: its id goes into its line of `ranks`)
+    # --full: a child process, started before this one touches the GPU (every rank: its id goes into its line of `ranks`)
+    device = device_identity(local_rank) if args.full else None
 
     import torch
     import torch.distributed as dist
@@ -983,9 +1053,10 @@ def main():
                 pass
 
     counts = torch.zeros((S_SAMPLES + 3,), dtype=torch.int64, device=dev)
+    cpu_sample = args.cpu_sample if args.full else 0            # the parity sample and cpu_baseline are --full's
     if lay is not None:
         vin = bin_.view(nt, lay.in_block)
-        ns_keep = (min(max(args.cpu_sample, 0), n) + 63) // 64 * 64
+        ns_keep = (min(max(cpu_sample, 0), n) + 63) // 64 * 64
         seq = [torch.empty((ns_keep, L_READ), dtype=torch.uint8, device=dev) for _ in range(2)]     # only the parity sample stays in SoA form
         qual = [torch.empty((ns_keep, L_READ), dtype=torch.uint8, device=dev) for _ in range(2)]
         bc = torch.empty((ns_keep, L_BC), dtype=torch.uint8, device=dev)
@@ -1116,11 +1187,16 @@ def main():
     S = S_SAMPLES
     assert int(total_counts[S]) == total_clusters, (int(total_counts[S]), total_clusters)
     assert int(total_counts[:S].sum()) == int(total_counts[S + 1])
+    if rank == 0 and args.dump_outputs:
+        if lay is not None:
+            dump_outputs(torch, args.dump_outputs, n, counts, lay=lay, bout=bout)
+        else:
+            dump_outputs(torch, args.dump_outputs, n, counts, assign=assign, lowest_k=lowest_k, out_seq=out_seq)
     cpu_baseline = None
     parity = None
-    if rank == 0 and args.cpu_sample > 0:
+    if rank == 0 and cpu_sample > 0:
         from oracle import oracle as orc
-        ns = min(args.cpu_sample, n)
+        ns = min(cpu_sample, n)
         if lay is not None:
             u = unpack_blocked(torch, lay, bout, (ns + 63) // 64)
             g_assign, g_k, g_m = u["assign"][:ns], [x[:ns] for x in u["lowest_k"]], [x[:ns] for x in u["out_seq"]]
@@ -1180,7 +1256,7 @@ def main():
                 cpu_baseline["faithful"] = {"error": str(e)}
 
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         if lay is not None:
             del bin_, bout
         else:
@@ -1224,7 +1300,7 @@ def main():
             "metric": "M reads/s demultiplex (150bp, 96 barcodes) at 1/8 GPUs; % HBM roofline",
             "value": round(value, 3), "unit": "M reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
+            "dtype": "u8", "data": "synthetic", "full": args.full,
             "config": {"workload": "fasta add barcode + demultiplex fused with trim+mask by quality: "
                                    f"{n} clusters/GPU x 2x150bp paired, 96 dual-index 8+8 barcodes (17 chars), <=1 mismatch, "
                                    "min_baseq 20 (= BASELINE configs[3], 500M clusters read-sharded over 8 GPUs)",

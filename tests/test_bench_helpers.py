@@ -19,3 +19,16 @@ def test_usable_cores_is_what_the_process_may_use():
     n = bench.usable_cores()
     assert 1 <= n <= (os.cpu_count() or 1)
     assert n <= len(os.sched_getaffinity(0))
+
+
+def test_a_plain_run_is_lean_and_steps_are_counted():
+    """--full is off by default (a plain run measures the headline only); --steps is the number of timed steps and must be one
+    at least (ms_per_step divides by it)."""
+    import pytest
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in ("0", "-3"):
+        with pytest.raises(SystemExit):
+            bench.parse(["--steps", bad])

@@ -75,3 +75,41 @@ def test_numpy_and_torch_packers_agree(hip_lib):
         assert np.array_equal(u["out_seq"][i], v["out_seq"][i].numpy()[:n])
         assert np.array_equal(u["lowest_k"][i], v["lowest_k"][i].numpy().view(np.uint16)[:n])
     assert np.array_equal(u["assign"], v["assign"].numpy()[:n])
+
+
+def test_dump_outputs_reads_soa_and_blocked_alike(hip_lib, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the same outputs held as SoA tensors or in a blocked output buffer give the same files, and the
+    files hold the sampled rows and the whole-shard sums exactly."""
+    import torch
+    import bench
+    lay = capi.blocked_layout(2, 150, 17, capi.SK_BLK_MASK | capi.SK_BLK_TRIM)
+    n = 64 * 5 + 11
+    nt = (n + 63) // 64
+    rng = np.random.default_rng(5)
+    out = rng.integers(0, 256, lay.out_bytes(n), dtype=np.uint8)
+    v = bench.unpack_blocked(torch, lay, torch.from_numpy(out), nt)
+    counts = torch.from_numpy(rng.integers(0, 1 << 40, 99, dtype=np.int64))
+    for rows in (100, 4096):                                                   # a sample of the rows, and all of them
+        monkeypatch.setattr(bench, "DUMP_ROWS", rows)
+        a, b = tmp_path / f"soa{rows}", tmp_path / f"blk{rows}"
+        bench.dump_outputs(torch, str(a), n, counts, assign=v["assign"], lowest_k=v["lowest_k"], out_seq=v["out_seq"])
+        bench.dump_outputs(torch, str(b), n, counts, lay=lay, bout=torch.from_numpy(out))
+        names = sorted(p.name for p in a.iterdir())
+        assert names == sorted(p.name for p in b.iterdir()) and len(names) == 8
+        f = {}
+        for name in names:
+            x, y = np.load(a / name), np.load(b / name)
+            assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and np.array_equal(x, y), name
+            f[name[:-4]] = x
+        r = f["rows"].astype(np.int64)
+        assert len(r) == min(rows, n) and np.all(np.diff(r) > 0) and r[-1] < n
+        assert np.array_equal(f["counts"], counts.numpy().astype(np.float64))
+        assert np.array_equal(f["assign"], v["assign"].numpy()[r].astype(np.float32))
+        for i in range(2):
+            seq = v["out_seq"][i].numpy()[:n]
+            k = v["lowest_k"][i].numpy().view(np.uint16)[:n]
+            assert np.array_equal(f["out_seq"][i], seq[r].astype(np.float32))
+            assert np.array_equal(f["lowest_k"][i], k[r].astype(np.float32))
+            assert np.array_equal(f["out_seq_column_sum"][i], seq.sum(0, dtype=np.int64).astype(np.float64))
+            assert np.array_equal(f["out_seq_column_n"][i], (seq == ord("N")).sum(0).astype(np.float64))
+            assert np.array_equal(f["lowest_k_hist"][i], np.bincount(np.minimum(k, 151), minlength=152).astype(np.float64))

@@ -143,7 +143,7 @@ def test_bench_two_ranks_on_one_gpu_take_the_gloo_fallback(hip_lib, oracle):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--pairs", "2000000", "--placements", "2", "--steps", "3", "--warmup", "1",
-                        "--no-extra", "--faithful-reads", "0", "--cpu-sample", "200000"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-extra", "--faithful-reads", "0", "--cpu-sample", "200000"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1

@@ -29,7 +29,7 @@ for x in d["extra"]["rates"]:
     if "reset_ms" in x:                                        # census: sk_census_reset before the count
         placed += f"; reset {x['reset_ms'] * 1000:.0f} µs, reset + count {x['reset_plus_count_ms'] * 1000:.0f} µs"
     rows.append(f"| {x['config']} | {x['ms'] * 1000:.1f} µs, {x['G_units_per_s']:.1f} G units/s | {x['frac']:.3f}{placed} | {b} |")
-table = "| config (device-resident; `bench.py` `extra.rates`) | rate | of 8 TB/s | bound |\n|---|---|---|---|\n" + "\n".join(rows)
+table = "| config (device-resident; `bench.py --full` `extra.rates`) | rate | of 8 TB/s | bound |\n|---|---|---|---|\n" + "\n".join(rows)
 r = d["roofline"]
 print(f"headline: value {d['value']} M reads/s, ms_per_step {d['ms_per_step']}, kernel_ms {r['kernel_ms']}, achieved {r['achieved']} GB/s, frac {r['frac']}, "
       f"frac_as_placed {r['frac_as_placed']}, read_frac {r['read_frac']}, traffic {r['traffic']}")

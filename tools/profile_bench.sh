@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/$TAG
 W=/tmp/skprof_$TAG
 rm -rf $W; mkdir -p $W $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py "$@" 2>/dev/null | tail -1 > $OUT/bench.json
+python3 $R/bench.py --full "$@" 2>/dev/null | tail -1 > $OUT/bench.json
 # the traced run keeps its own JSON line: its HIP-event kernel time and the trace's durations of its timed steps come from
 # the SAME process (placements — and with them the kernel time — differ from process to process)
 rocprofv3 --kernel-trace --stats --output-format csv -d $W/trace -- python3 $R/bench.py --steps 8 --warmup 2 --cpu-sample 0 --no-extra "$@" > $W/trace.log 2>$W/trace.err

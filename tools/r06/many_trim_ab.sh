@@ -1,7 +1,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 for E in 0 1; do
   echo "== SK_MANY_TWO_STREAMS=$E"
-  SK_MANY_TWO_STREAMS=$E timeout -k 10 600 python3 bench.py --pairs 1000000 --steps 2 --warmup 1 --cpu-sample 0 2>/dev/null | python3 -c "
+  SK_MANY_TWO_STREAMS=$E timeout -k 10 600 python3 bench.py --full --pairs 1000000 --steps 2 --warmup 1 --cpu-sample 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for x in d['extra']['rates']:
