@@ -341,6 +341,36 @@ int sk_bam_walk_reduce_dev(sk_ctx *ctx, const uint8_t *stream, uint64_t stream_l
 int sk_bam_file_reduce(sk_ctx *ctx, const char *path, int32_t max_frag, uint64_t counters[3], uint64_t *hist,
                        uint64_t *hist_total, int *handled, double info[8]);
 
+/* ---- B1 for the record commands: a BAM file as device SoA columns --------------------------------------------------------
+ * sk_bam_file_columns: what sk_bam_file_reduce does up to and including the verified walk (same files served, same knobs
+ * SK_BAMFILE_*, same *handled = 0 cases, info[] as there), then the fields `want` names of EVERY record, in file order, into SoA
+ * columns on the device: flag, mapq, refID, next_refID, pos, next_pos, tlen of the 32-byte core, and END = cigar end_pos as the
+ * reference's reader computes it for src/sam_count.rs:78-94 — pos plus the lengths of the ops M D N = X (codes 0 2 3 7 8) in 64
+ * bits, truncated to int32; pos itself when the record's variable part is shorter than its read name and CIGAR.  The columns stay
+ * with the ctx, 16-byte aligned (the _dev entries take them as they are), and hold until the next sk_bam_file_* call on the ctx
+ * or sk_destroy; a column not asked for is NULL.  header (HOST, also the ctx's) holds the BAM header from "BAM\1" to the end of the
+ * reference list (SAMv1 §4.2): the reference names, as src/sam_fragments.rs:22 and src/sam_count.rs:37 take them.  *handled = 0:
+ * every case sk_bam_file_reduce leaves to its caller, and also when the device has no room for the columns; cols is then zeroed. */
+#define SK_COL_FLAG 1u                 /* uint16 */
+#define SK_COL_MAPQ 2u                 /* uint8 */
+#define SK_COL_TID  4u                 /* int32 refID */
+#define SK_COL_MTID 8u                 /* int32 next_refID */
+#define SK_COL_POS  16u                /* int32 */
+#define SK_COL_MPOS 32u                /* int32 next_pos */
+#define SK_COL_TLEN 64u                /* int32 */
+#define SK_COL_END  128u               /* int32 cigar end_pos */
+#define SK_COL_ALL  255u
+typedef struct sk_bam_columns {
+	int64_t n;                         /* records in the file */
+	uint16_t *flag;                    /* DEVICE columns of n entries, NULL if not asked for */
+	uint8_t *mapq;
+	int32_t *tid, *mtid, *pos, *mpos, *tlen, *end_pos;
+	const uint8_t *header;             /* HOST: "BAM\1" .. the end of the reference list */
+	uint64_t header_len;
+	int32_t n_ref;
+} sk_bam_columns;
+int sk_bam_file_columns(sk_ctx *ctx, const char *path, uint32_t want, sk_bam_columns *cols, int *handled, double info[8]);
+
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is
  * the decompressed stream.  sk_bgzf_deflate compresses n independent blocks of at most SK_DEFLATE_MAX_IN bytes (in +
@@ -367,12 +397,21 @@ int sk_bgzf_deflate_dev(sk_ctx *ctx, const uint8_t *in, const sk_deflate_block *
 /* ---- f2: `sam fragments` record filter ---------------------------------------------------------------------
  * src/sam_fragments.rs:27-38: keep the forward mate of a converging, mapped, primary, non-duplicate, QC-passing pair on
  * one reference whose |tlen| lies in [min_size, max_size].  keep_bits: (n+7)/8 bytes, bit j of byte k <=> record 8k+j;
- * *kept is ADDED to.  The BED line of a kept record (:41) is text and stays on the host.  Columns must be 16-byte
+ * *kept is ADDED to.  The BED line of a kept record (:41): sk_bam_fragments_bed_dev.  Columns must be 16-byte
  * aligned for the _dev form.                                                                                */
 int sk_bam_fragments(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *tlen,
                      int64_t n, int64_t min_size, int64_t max_size, uint8_t *keep_bits, uint64_t *kept);
 int sk_bam_fragments_dev(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *tlen,
                          int64_t n, int64_t min_size, int64_t max_size, uint8_t *keep_bits, uint64_t *kept);
+/* The BED lines of the kept records (src/sam_fragments.rs:41: chr_names[tid] \t pos \t pos + |tlen| \n, the numbers signed
+ * 64-bit decimal), written on the device in record order.  keep_bits as sk_bam_fragments_dev writes them; tid, pos, tlen device
+ * columns of n records (16-byte aligned).  names: the n_ref reference names back to back (HOST), name r = names[name_off[r] ..
+ * name_off[r + 1]) copied verbatim.  Synchronous: *text points at *text_len bytes of page-locked HOST memory that stays with the
+ * ctx until the next call.  *bad = index of the first kept record whose tid is not in [0, n_ref) — where the reference panics —
+ * and *text then holds the lines before it; -1 when there is none.                                                         */
+int sk_bam_fragments_bed_dev(sk_ctx *ctx, const uint8_t *keep_bits, const int32_t *tid, const int32_t *pos, const int32_t *tlen,
+                             int64_t n, const uint8_t *names, const uint64_t *name_off, int32_t n_ref, const char **text,
+                             uint64_t *text_len, int64_t *bad);
 
 /* ---- f2 (second half): `sam count` ---------------------------------------------------------------------------
  * src/sam_count.rs:44-127.  sk_count_set_regions loads the BED regions grouped by BAM reference: regions of
@@ -383,7 +422,7 @@ int sk_bam_fragments_dev(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, 
  * chain (:46-50, :78-94), the fragment interval in the reference's u32 arithmetic (:75,97-107) and adds 1 to every
  * region of the record's reference that the interval overlaps (:122-126).  Columns: flag, mapq, refID, next_refID,
  * pos, next_pos, tlen of the BAM core and, for single_end only, cigar end_pos (NULL otherwise).  What depends on
- * record order — the "not coordinate sorted" error (:70-72) and chr_names[tid] (:55) — is the caller's.  The counts
+ * record order — the "not coordinate sorted" error (:70-72) and chr_names[tid] (:55) — is sk_count_order_check_dev's.  The counts
  * do not depend on the order of the records; the speed does: the region search of a record starts from its
  * predecessor's answer, which is two probes in a coordinate-sorted batch and more than a plain search otherwise.      */
 int sk_count_set_regions(sk_ctx *ctx, int n_chr, const int32_t *chr_off, const uint32_t *rstart, const uint32_t *rend,
@@ -395,6 +434,14 @@ int sk_count_add_dev(sk_ctx *ctx, const uint16_t *flag, const uint8_t *mapq, con
                      const int32_t *pos, const int32_t *mpos, const int32_t *tlen, const int32_t *end_pos, int64_t n,
                      uint8_t min_mapq, uint32_t max_frag_len, int single_end, int center);
 int sk_count_get(sk_ctx *ctx, uint32_t *region_frags /* n_regions */);
+/* The order checks of src/sam_count.rs:52-73 over device columns of n records, in file order: among the records the filter of
+ * :46-49 passes (none of 0x4 0x400 0x100 0x800, mapq >= min_mapq), starting from prev_chr = -1, prev_pos = 0, a record whose tid
+ * differs from prev_chr and is not in [0, n_ref) panics (:55), a record on the same tid with pos < prev_pos ends the command ("not
+ * coordinate sorted", :70-72); every passing record sets prev_chr and prev_pos.  Synchronous: *first_stop = index of the first
+ * record where that loop stops, -1 if it runs through; *code = 101 (the tid) or 255 (the order), 0 for -1.  Columns 16-byte
+ * aligned.                                                                                                                      */
+int sk_count_order_check_dev(sk_ctx *ctx, const uint16_t *flag, const uint8_t *mapq, const int32_t *tid, const int32_t *pos, int64_t n,
+                             uint8_t min_mapq, int32_t n_ref, int64_t *first_stop, int *code);
 
 /* ---- `fasta gc content` ------------------------------------------------------------------------------------------
  * src/fasta_gc_content.rs:41-46.  sk_gc_set_genome copies the concatenated sequences to the device once (it stays

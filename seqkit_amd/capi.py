@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 from typing import Optional
 
 import numpy as np
@@ -29,8 +30,8 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
-    "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_gc_set_genome", "sk_gc_count",
+    "sk_bam_file_columns", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
     "sk_timer_start", "sk_timer_stop",
 ]
@@ -38,6 +39,35 @@ EXPORTED_SYMBOLS = [
 
 class SeqkitHipError(RuntimeError):
     pass
+
+
+class _BamColumns(C.Structure):
+    _fields_ = [("n", C.c_int64), ("flag", C.c_void_p), ("mapq", C.c_void_p), ("tid", C.c_void_p), ("mtid", C.c_void_p), ("pos", C.c_void_p),
+                ("mpos", C.c_void_p), ("tlen", C.c_void_p), ("end_pos", C.c_void_p), ("header", C.c_void_p), ("header_len", C.c_uint64),
+                ("n_ref", C.c_int32)]
+
+
+# sk_bam_file_columns: SK_COL_* bit, column name, dtype (include/seqkit_hip.h)
+BAM_COLUMNS = (("flag", np.uint16), ("mapq", np.uint8), ("tid", np.int32), ("mtid", np.int32), ("pos", np.int32), ("mpos", np.int32),
+               ("tlen", np.int32), ("end_pos", np.int32))
+SK_COL = {name: 1 << k for k, (name, _) in enumerate(BAM_COLUMNS)}
+SK_COL_ALL = 255
+
+
+def bam_header_names(header: bytes) -> list:
+    """The reference names of a BAM header ("BAM\\1" .. the end of the reference list) as the hosts keep them: one trailing NUL
+    dropped, other bytes kept."""
+    (l_text,) = struct.unpack_from("<i", header, 4)
+    at = 8 + l_text
+    (n_ref,) = struct.unpack_from("<i", header, at)
+    at += 4
+    names = []
+    for _ in range(n_ref):
+        (l_name,) = struct.unpack_from("<i", header, at)
+        nm = header[at + 4:at + 4 + l_name]
+        names.append(nm[:-1] if nm.endswith(b"\0") else nm)
+        at += 8 + l_name
+    return names
 
 
 class _Mate(C.Structure):
@@ -190,6 +220,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_walk_dev": (i32, [vp, vp, C.c_uint64, vp, i64, C.c_uint64, i32, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(i32)]),
         "sk_bam_walk_reduce_dev": (i32, [vp, vp, C.c_uint64, vp, vp, i64, i32, i32, i32, vp]),
         "sk_bam_file_reduce": (i32, [vp, C.c_char_p, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_columns": (i32, [vp, C.c_char_p, C.c_uint32, C.POINTER(_BamColumns), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_fragments_bed_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(i64)]),
+        "sk_count_order_check_dev": (i32, [vp, vp, vp, vp, vp, i64, C.c_uint8, i32, C.POINTER(i64), C.POINTER(i32)]),
         "sk_bam_fragments": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]),
         "sk_bam_fragments_dev": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]),
         "sk_bam_sequence": (i32, [vp, vp, i32, vp, i32, vp, vp, i64, C.c_uint8, vp]),
@@ -335,6 +368,52 @@ class Context:
         self._check(self._lib.sk_bam_file_reduce(self._h, os.fsencode(path), max_frag, counters.ctypes.data if want_counters else None,
                                                  hist.ctypes.data if want_hist else None, total.ctypes.data, C.byref(handled), info), "sk_bam_file_reduce")
         return bool(handled.value), counters, hist, int(total[0]), [float(x) for x in info]
+
+    def bam_file_columns_dev(self, path: str, want: int = SK_COL_ALL):
+        """sk_bam_file_columns, the columns left on the device: (handled, {name: device address}, n, header bytes, info f64[8]).  The
+        addresses belong to the ctx and hold until its next sk_bam_file_* call; they compose with the _dev wrappers."""
+        cols = _BamColumns()
+        handled = C.c_int32(0)
+        info = (C.c_double * 8)()
+        self._check(self._lib.sk_bam_file_columns(self._h, os.fsencode(path), want, C.byref(cols), C.byref(handled), info), "sk_bam_file_columns")
+        if not handled.value:
+            return False, {}, 0, b"", [float(x) for x in info]
+        dev = {name: int(getattr(cols, name)) for name, _ in BAM_COLUMNS if getattr(cols, name)}
+        header = C.string_at(cols.header, cols.header_len) if cols.header_len else b""
+        return True, dev, int(cols.n), header, [float(x) for x in info]
+
+    def bam_file_columns(self, path: str, want: int = SK_COL_ALL):
+        """sk_bam_file_columns, copied to the host: (handled, {name: np.ndarray}, reference names [bytes], info f64[8])."""
+        handled, dev, n, header, info = self.bam_file_columns_dev(path, want)
+        if not handled:
+            return False, {}, [], info
+        out = {}
+        for name, dt in BAM_COLUMNS:
+            if name in dev:
+                a = np.empty(n, dtype=dt)
+                if n:
+                    self.copy_d2h(a, dev[name])
+                out[name] = a
+        return True, out, bam_header_names(header), info
+
+    def bam_fragments_bed_dev(self, keep_bits: int, tid: int, pos: int, tlen: int, n: int, names):
+        """sk_bam_fragments_bed_dev over device columns: (BED text bytes, index of the first kept record with a bad tid or -1).
+        names: the reference names (bytes)."""
+        names = [bytes(x) for x in names]
+        off = np.zeros(len(names) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in names]) if names else []
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        text, text_len, bad = C.c_void_p(), C.c_uint64(0), C.c_int64(0)
+        self._check(self._lib.sk_bam_fragments_bed_dev(self._h, keep_bits, tid, pos, tlen, n, blob.ctypes.data, off.ctypes.data, len(names),
+                                                       C.byref(text), C.byref(text_len), C.byref(bad)), "sk_bam_fragments_bed_dev")
+        return (C.string_at(text.value, text_len.value) if text_len.value else b""), int(bad.value)
+
+    def count_order_check_dev(self, flag: int, mapq: int, tid: int, pos: int, n: int, min_mapq: int, n_ref: int):
+        """sk_count_order_check_dev: (index of the record where src/sam_count.rs's loop stops or -1, code 101 / 255 / 0)."""
+        first, code = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.sk_count_order_check_dev(self._h, flag, mapq, tid, pos, n, min_mapq, n_ref, C.byref(first), C.byref(code)),
+                    "sk_count_order_check_dev")
+        return int(first.value), int(code.value)
 
     def stream(self) -> int:
         return int(self._lib.sk_stream(self._h) or 0)

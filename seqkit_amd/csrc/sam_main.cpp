@@ -10,7 +10,10 @@
 // The reference reads BAM through rust-htslib; this host walks the BGZF/BAM container itself (SAMv1 §4.2: BGZF is a
 // series of gzip members; after the header every record is block_size:u32 + a 32-byte fixed core) and hands the core
 // columns flag / refID / next_refID / tlen to the device as SoA batches.  Order-dependent pieces stay here, as
-// SURVEY.md §8(e) lists them: the --reads=N early stop and the --on-target sweep (S2, not part of the device path).
+// SURVEY.md §8(e) lists them: the --reads=N early stop and the --on-target sweep (S2, not part of the device path).  A regular
+// file is first offered to the device whole (sk_bam_file_reduce, sk_bam_file_columns): it inflates and walks it; `sam fragments`
+// and `sam count` then run their order checks and their text on the device too, and whatever is irregular falls back to the reader
+// here before anything has been written.
 #include <unistd.h>
 #include <malloc.h>
 #include <fcntl.h>
@@ -245,6 +248,40 @@ static std::string expand_home(const std::string &path)      // PathArgs::get_pa
 	return path;
 }
 
+// The reference names of a BAM header as BamStream keeps them (one trailing NUL dropped, other bytes kept), from the header bytes
+// sk_bam_file_columns returns ("BAM\1" .. the end of the reference list: checked there already).
+static std::vector<std::string> header_names(const uint8_t *h, uint64_t len)
+{
+	auto le32 = [&](uint64_t o) { return o + 4 <= len ? (uint32_t)h[o] | ((uint32_t)h[o + 1] << 8) | ((uint32_t)h[o + 2] << 16) | ((uint32_t)h[o + 3] << 24) : 0u; };
+	std::vector<std::string> names;
+	uint64_t o = 8 + (uint64_t)le32(4);
+	const uint32_t n_ref = le32(o);
+	o += 4;
+	for (uint32_t r = 0; r < n_ref && o + 4 <= len; r++) {
+		const uint32_t l_name = le32(o);
+		std::string name(reinterpret_cast<const char *>(h + o + 4), std::min<uint64_t>(l_name, len - o - 4));
+		if (!name.empty() && name.back() == '\0') name.pop_back();
+		names.push_back(name);
+		o += 4 + (uint64_t)l_name + 4;
+	}
+	return names;
+}
+
+// device buffers of one command's file path (sk_malloc_device), freed whichever way it is left
+struct DevBufs {
+	std::vector<void *> p;
+	~DevBufs() { for (void *q : p) (void)sk_free_device(host::gpu(), q); }
+	void *get(size_t bytes)
+	{
+		void *q = nullptr;
+		if (sk_malloc_device(host::gpu(), bytes ? bytes : 16, &q) != SK_OK) return nullptr;
+		p.push_back(q);
+		return q;
+	}
+};
+
+static bool file_path_wanted(const std::string &path) { return path != "-" && !getenv("SEQKIT_HOST_INFLATE"); }
+
 // ---- sam statistics ----------------------------------------------------------------------------------------------
 struct Region { int64_t start, end; };
 
@@ -450,6 +487,37 @@ static bool parse_i64(const std::string &s, int64_t &out)          // str::parse
 	return true;
 }
 
+// sam fragments over the FILE: the device inflates and walks it (sk_bam_file_columns), filters the records (sk_bam_fragments_dev) and
+// writes the BED text (sk_bam_fragments_bed_dev), which goes out in one write.  -1: nothing has been written, and the caller's reader
+// serves the file — one the file path does not take, a device without room, or a kept record whose tid has no name (the reader
+// writes the lines before it and panics where the reference does).  Otherwise the number of records.
+static int64_t fragments_from_file(const std::string &path, int64_t min_size, int64_t max_size)
+{
+	sk_ctx *c = host::gpu();
+	sk_bam_columns cols;
+	int handled = 0;
+	if (sk_bam_file_columns(c, path.c_str(), SK_COL_FLAG | SK_COL_TID | SK_COL_MTID | SK_COL_POS | SK_COL_TLEN, &cols, &handled, nullptr) != SK_OK || !handled) return -1;
+	const std::vector<std::string> names = header_names(cols.header, cols.header_len);
+	const int64_t n = cols.n;
+	DevBufs dev;
+	uint8_t *bits = (uint8_t *)dev.get((size_t)(n + 7) / 8 + 16);
+	uint64_t *kept = (uint64_t *)dev.get(16);
+	if (!bits || !kept) return -1;
+	const uint64_t zero = 0;
+	if (sk_copy_h2d(c, kept, &zero, 8) != SK_OK) return -1;
+	if (n && sk_bam_fragments_dev(c, cols.flag, cols.tid, cols.mtid, cols.tlen, n, min_size, max_size, bits, kept) != SK_OK) return -1;   // :27-38
+	std::string blob;
+	std::vector<uint64_t> off(1, 0);
+	for (const std::string &nm : names) { blob += nm; off.push_back(blob.size()); }
+	const char *text = nullptr;
+	uint64_t text_len = 0;
+	int64_t bad = -1;
+	if (sk_bam_fragments_bed_dev(c, bits, cols.tid, cols.pos, cols.tlen, n, reinterpret_cast<const uint8_t *>(blob.data()), off.data(), (int32_t)names.size(),
+	                             &text, &text_len, &bad) != SK_OK || bad >= 0) return -1;                                        // :41
+	if (text_len) host::out().write(text, (size_t)text_len);
+	return n;
+}
+
 static int fragments(int argc, char **argv)                        // src/sam_fragments.rs:14-43
 {
 	std::vector<host::Opt> opts = {{"--min-size", true, false, "0"}, {"--max-size", true, false, "5000"}};
@@ -459,6 +527,15 @@ static int fragments(int argc, char **argv)                        // src/sam_fr
 	if (!parse_i64(opts[0].value, min_size)) panic("called `Result::unwrap()` on an `Err` value: ParseIntError (--min-size)");   // :17
 	if (!parse_i64(opts[1].value, max_size)) panic("called `Result::unwrap()` on an `Err` value: ParseIntError (--max-size)");   // :18
 	host::gpu_warmup();
+	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
+	if (file_path_wanted(pos[0])) {
+		const int64_t n = fragments_from_file(pos[0], min_size, max_size);
+		if (n >= 0) {
+			if (trace) fprintf(stderr, "sam fragments: device path, %lld records\n", (long long)n);
+			return 0;
+		}
+	}
+	if (trace) fprintf(stderr, "sam fragments: host reader\n");
 	BamStream bam(pos[0]);
 	Columns col;
 	std::vector<BamCore> chunk;
@@ -502,6 +579,58 @@ static const char *USAGE_COUNT =
 	"that overlap each region described in the input BED file. The BAM file must\n"
 	"be position-sorted.\n";
 
+// the regions of every BAM reference (src/sam_count.rs:61-63), handed to the device once
+struct CountReg { std::string chr; uint32_t start, end; };
+static int count_load_regions(const std::vector<std::string> &names, const std::vector<CountReg> &regions)
+{
+	const int n_chr = (int)names.size();
+	std::vector<int32_t> chr_off(n_chr + 1, 0), ridx;
+	std::vector<uint32_t> rs, re;
+	for (int c = 0; c < n_chr; c++) {
+		for (size_t r = 0; r < regions.size(); r++)
+			if (regions[r].chr == names[c]) { rs.push_back(regions[r].start); re.push_back(regions[r].end); ridx.push_back((int32_t)r); }
+		chr_off[c + 1] = (int32_t)rs.size();
+	}
+	return sk_count_set_regions(host::gpu(), n_chr, chr_off.data(), rs.data(), re.data(), ridx.data(), (int64_t)rs.size(),
+	                            (int64_t)std::max(rs.size(), regions.size()));
+}
+
+static void count_print(const std::vector<CountReg> &regions)
+{
+	std::vector<uint32_t> region_frags(std::max<size_t>(regions.size(), 1));
+	check(sk_count_get(host::gpu(), region_frags.data()), "sk_count_get");
+	char buf[32];
+	for (size_t r = 0; r < regions.size(); r++) {                                                                          // :128-130
+		snprintf(buf, sizeof buf, "%u\n", region_frags[r]);
+		host::out().write(buf, strlen(buf));
+	}
+}
+
+// sam count over the FILE: the device inflates and walks it (sk_bam_file_columns), checks the order as :52-73 do
+// (sk_count_order_check_dev) and counts every record in one call (sk_count_add_dev).  -1: nothing has been written, and the caller's
+// reader serves the file — one the file path does not take, a device without room, a reference name that is not UTF-8 (:37-38), or a
+// file where the loop of :52-73 stops (the reader writes what the reference does).  Otherwise the number of records.
+static int64_t count_from_file(const std::string &path, const std::vector<CountReg> &regions, uint8_t min_mapq, uint32_t max_frag_len, bool single_end,
+                               bool center)
+{
+	sk_ctx *c = host::gpu();
+	sk_bam_columns cols;
+	int handled = 0;
+	const uint32_t want = SK_COL_FLAG | SK_COL_MAPQ | SK_COL_TID | SK_COL_MTID | SK_COL_POS | SK_COL_MPOS | SK_COL_TLEN | (single_end ? SK_COL_END : 0u);
+	if (sk_bam_file_columns(c, path.c_str(), want, &cols, &handled, nullptr) != SK_OK || !handled) return -1;
+	const std::vector<std::string> names = header_names(cols.header, cols.header_len);
+	for (const std::string &nm : names)
+		if (!host::utf8_valid(reinterpret_cast<const uint8_t *>(nm.data()), nm.size())) return -1;
+	if (count_load_regions(names, regions) != SK_OK) return -1;
+	int64_t stop = -1;
+	int code = 0;
+	if (sk_count_order_check_dev(c, cols.flag, cols.mapq, cols.tid, cols.pos, cols.n, min_mapq, (int32_t)names.size(), &stop, &code) != SK_OK || stop >= 0) return -1;
+	if (sk_count_add_dev(c, cols.flag, cols.mapq, cols.tid, cols.mtid, cols.pos, cols.mpos, cols.tlen, single_end ? cols.end_pos : nullptr, cols.n, min_mapq,
+	                     max_frag_len, single_end ? 1 : 0, center ? 1 : 0) != SK_OK || sk_sync(c) != SK_OK) return -1;
+	count_print(regions);
+	return cols.n;
+}
+
 static int count(int argc, char **argv)                            // src/sam_count.rs:20-130
 {
 	std::vector<host::Opt> opts = {{"--min-mapq", true, false, "0"}, {"--max-frag-len", true, false, "5000"}, {"--single-end", false, false, ""},
@@ -516,8 +645,7 @@ static int count(int argc, char **argv)                            // src/sam_co
 	const bool single_end = opts[2].present, count_centers = opts[3].present;                                              // :26-27
 
 	fputs("Reading target regions from BED file...\n", stderr);                                                            // :30
-	struct Reg { std::string chr; uint32_t start, end; };
-	std::vector<Reg> regions;                                                                                              // read_regions, src/common.rs:198-219
+	std::vector<CountReg> regions;                                                                                              // read_regions, src/common.rs:198-219
 	{
 		host::LineReader bed(pos[1]);
 		std::string line;
@@ -540,23 +668,19 @@ static int count(int argc, char **argv)                            // src/sam_co
 	}
 	fprintf(stderr, "Counting %s...\n", single_end ? "reads" : "DNA fragments");                                            // :34-35
 	host::gpu_warmup();
+	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
+	if (file_path_wanted(pos[0])) {
+		const int64_t n = count_from_file(pos[0], regions, min_mapq, max_frag_len, single_end, count_centers);
+		if (n >= 0) {
+			if (trace) fprintf(stderr, "sam count: device path, %lld records\n", (long long)n);
+			return 0;
+		}
+	}
+	if (trace) fprintf(stderr, "sam count: host reader\n");
 	BamStream bam(pos[0]);                                                                                                 // :36
 	for (const std::string &nm : bam.names)                                                                                // :37-38
 		if (!host::utf8_valid(reinterpret_cast<const uint8_t *>(nm.data()), nm.size())) panic("called `Result::unwrap()` on an `Err` value: Utf8Error");
-
-	// the regions of every BAM reference (:61-63), handed to the device once
-	{
-		const int n_chr = (int)bam.names.size();
-		std::vector<int32_t> chr_off(n_chr + 1, 0), ridx;
-		std::vector<uint32_t> rs, re;
-		for (int c = 0; c < n_chr; c++) {
-			for (size_t r = 0; r < regions.size(); r++)
-				if (regions[r].chr == bam.names[c]) { rs.push_back(regions[r].start); re.push_back(regions[r].end); ridx.push_back((int32_t)r); }
-			chr_off[c + 1] = (int32_t)rs.size();
-		}
-		check(sk_count_set_regions(host::gpu(), n_chr, chr_off.data(), rs.data(), re.data(), ridx.data(), (int64_t)rs.size(),
-		                           (int64_t)std::max(rs.size(), regions.size())), "sk_count_set_regions");
-	}
+	check(count_load_regions(bam.names, regions), "sk_count_set_regions");
 
 	int32_t prev_chr = -1;                                                                                                 // :40-41
 	int64_t prev_pos = 0;
@@ -591,13 +715,7 @@ static int count(int argc, char **argv)                            // src/sam_co
 	}
 	if (stop) { if (stop_code == 101) panic(stop); error("%s", stop); }
 	bam.raise_deferred();
-	std::vector<uint32_t> region_frags(std::max<size_t>(regions.size(), 1));
-	check(sk_count_get(host::gpu(), region_frags.data()), "sk_count_get");
-	char buf[32];
-	for (size_t r = 0; r < regions.size(); r++) {                                                                          // :128-130
-		snprintf(buf, sizeof buf, "%u\n", region_frags[r]);
-		host::out().write(buf, strlen(buf));
-	}
+	count_print(regions);
 	return 0;
 }
 

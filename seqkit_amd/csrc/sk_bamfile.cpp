@@ -171,6 +171,7 @@ struct Mapper {
 // what stays with the ctx: the range of the compressed file and the range of the inflated stream
 struct Ranges {
 	OutRange comp, out;
+	std::vector<uint8_t> header;                 // sk_bam_file_columns: the last file's header bytes (cols->header)
 	static void destroy(void *p) { Ranges *r = (Ranges *)p; r->comp.release(); r->out.release(); delete r; }
 };
 
@@ -247,16 +248,27 @@ struct Readers {
 		if (e_ != hipSuccess) return sk::ctx_fail(c, SK_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));               \
 	} while (0)
 
-extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag, uint64_t counters[3], uint64_t *hist, uint64_t *hist_total,
-                                  int *handled, double info[8])
+// What the front half of a file call leaves behind: the verified stream on the device (the inflated blocks back to back, readable
+// 64 bytes beyond; block_end and entry of the walk) and, on the host, the per-block record counts and the header bytes.  ready = false
+// (info[5] = -check): the file is not one this path serves.  The device buffers of d_bend / d_entry belong to the caller's Cleanup.
+struct Front {
+	bool ready = false;
+	const uint8_t *d_out = nullptr;
+	uint64_t stream_len = 0, first = 0, n_records = 0, fsize = 0, n_host = 0;
+	uint64_t *d_bend = nullptr, *d_entry = nullptr;
+	int64_t nb = 0;
+	int rounds = 0;
+	int32_t n_ref = -1;
+	std::vector<uint32_t> nrec;                  // records begun in block c
+	std::vector<uint8_t> header;                 // "BAM\1" .. the end of the reference list (first bytes)
+	double t0 = 0, t_alloc = 0, t_read = 0, t_inflated = 0, t_header = 0, t_walk = 0;
+};
+
+// open and stat, the buffers, the readers, the BGZF headers and the batches of inflate launches, zlib for the blocks the device gave up,
+// the BAM header, the walk and its verification: everything both file calls do before they read the records.  `who` names the caller
+// in trace lines.
+static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup &cl, Front &fr, double info[8])
 {
-	if (!c || !path || !handled) return SK_ERR_INVALID;
-	*handled = 0;
-	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
-	if (max_frag < 0) return sk::ctx_fail(c, SK_ERR_INVALID, "max_frag = %d", max_frag);
-	if (!counters && !hist) return sk::ctx_fail(c, SK_ERR_INVALID, "nothing to do");
-	if (int r = sk::ctx_bind(c)) return r;
-	Cleanup cl;
 	cl.fd = open(path, O_RDONLY);
 	if (cl.fd < 0) BF_LEAVE(1);                                        // (the caller's reader says so in the reference's words)
 	struct stat sb;
@@ -493,7 +505,7 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 		for (int64_t i = 0; i < nb; i++) {
 			if (status[(size_t)i] == 0) continue;
 			const sk_bgzf_block &b = blocks[(size_t)i];
-			if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_reduce: block %lld (in %u bytes at %llu, out %u) has status %#x: zlib\n", (long long)i, b.in_len, (unsigned long long)b.in_off, b.out_len, status[(size_t)i]);
+			if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "%s: block %lld (in %u bytes at %llu, out %u) has status %#x: zlib\n", who, (long long)i, b.in_len, (unsigned long long)b.in_off, b.out_len, status[(size_t)i]);
 			cbuf.resize(b.in_len ? b.in_len : 1);
 			obuf.resize(b.out_len ? b.out_len : 1);
 			if (b.in_len && !pread_full(cl.fd, cbuf.data(), b.in_len, b.in_off)) BF_LEAVE(14);
@@ -514,8 +526,9 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 	// ---- the BAM header: magic, text, references (SAMv1 §4.2) — where the first record begins
 	uint64_t first = 0;
 	int32_t n_ref_hdr = -1;
+	std::vector<uint8_t> hd_keep;
 	{
-		std::vector<uint8_t> hd;
+		std::vector<uint8_t> &hd = hd_keep;
 		size_t want = (size_t)std::min<uint64_t>(stream_len, (uint64_t)1 << 20);
 		for (;;) {
 			hd.resize(want);
@@ -546,17 +559,14 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 		}
 	}
 	const double t_header = now_ms();
-	// ---- the records: walk, verify, reduce
-	uint64_t *d_bend = nullptr, *d_entry = nullptr, *d_exit = nullptr, *d_red = nullptr;
+	// ---- the records: walk and verify
+	uint64_t *d_bend = nullptr, *d_entry = nullptr, *d_exit = nullptr;
 	uint32_t *d_nrec = nullptr;
 	BF_HIP(hipMalloc((void **)&d_bend, (size_t)(nb + 1) * 8)); cl.dev.push_back(d_bend);
 	BF_HIP(hipMalloc((void **)&d_entry, (size_t)(nb + 1) * 8)); cl.dev.push_back(d_entry);
 	BF_HIP(hipMalloc((void **)&d_exit, (size_t)(nb + 1) * 8)); cl.dev.push_back(d_exit);
 	BF_HIP(hipMalloc((void **)&d_nrec, (size_t)(nb + 2) * 4)); cl.dev.push_back(d_nrec);
-	const size_t nred = 4 + (size_t)max_frag + 1;
-	BF_HIP(hipMalloc((void **)&d_red, nred * 8)); cl.dev.push_back(d_red);
 	BF_HIP(hipMemcpyAsync(d_bend, bend.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-	BF_HIP(hipMemsetAsync(d_red, 0, nred * 8, st));
 	BF_HIP(hipMemsetAsync(d_out + stream_len, 0, 64, st));               // (the walk reads whole dwords)
 	int verified = 0, rounds = 0;
 	uint64_t n_records = 0;
@@ -564,8 +574,43 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 	if (const char *ev = getenv("SK_BAMFILE_MAX_ROUNDS")) { const int v = atoi(ev); if (v >= 1) max_rounds = v; }
 	if (int r = sk_bam_walk_dev(c, d_out, stream_len, d_bend, nb, first, n_ref_hdr, d_entry, d_exit, d_nrec, max_rounds, &verified, &n_records, &rounds)) return r;
 	if (!verified) BF_LEAVE(20);
-	const double t_walk = now_ms();
-	if (int r = sk_bam_walk_reduce_dev(c, d_out, stream_len, d_bend, d_entry, nb, max_frag, counters ? 1 : 0, hist ? 1 : 0, d_red)) return r;
+	fr.nrec.resize((size_t)nb);
+	if (nb) BF_HIP(hipMemcpy(fr.nrec.data(), d_nrec, (size_t)nb * 4, hipMemcpyDeviceToHost));
+	fr.header.assign(hd_keep.begin(), hd_keep.begin() + (ptrdiff_t)first);
+	fr.ready = true;
+	fr.d_out = d_out; fr.stream_len = stream_len; fr.first = first; fr.n_records = n_records; fr.fsize = fsize; fr.n_host = n_host;
+	fr.d_bend = d_bend; fr.d_entry = d_entry; fr.nb = nb; fr.rounds = rounds; fr.n_ref = n_ref_hdr;
+	fr.t0 = t0; fr.t_alloc = t_alloc; fr.t_read = t_read; fr.t_inflated = t_inflated; fr.t_header = t_header; fr.t_walk = now_ms();
+	return SK_OK;
+}
+
+static void front_info(const Front &fr, double info[8])
+{
+	if (!info) return;
+	info[0] = (double)fr.fsize; info[1] = (double)fr.stream_len; info[2] = (double)fr.nb; info[3] = (double)fr.n_records;
+	info[4] = (double)fr.n_host; info[5] = (double)fr.rounds; info[6] = fr.t_read - fr.t0; info[7] = now_ms() - fr.t_read;
+}
+
+extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag, uint64_t counters[3], uint64_t *hist, uint64_t *hist_total,
+                                  int *handled, double info[8])
+{
+	if (!c || !path || !handled) return SK_ERR_INVALID;
+	*handled = 0;
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (max_frag < 0) return sk::ctx_fail(c, SK_ERR_INVALID, "max_frag = %d", max_frag);
+	if (!counters && !hist) return sk::ctx_fail(c, SK_ERR_INVALID, "nothing to do");
+	if (int r = sk::ctx_bind(c)) return r;
+	Cleanup cl;
+	Front fr;
+	if (int r = bam_file_front(c, path, "sk_bam_file_reduce", cl, fr, info)) return r;
+	if (!fr.ready) return SK_OK;
+	// ---- the records: reduce
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *d_red = nullptr;
+	const size_t nred = 4 + (size_t)max_frag + 1;
+	BF_HIP(hipMalloc((void **)&d_red, nred * 8)); cl.dev.push_back(d_red);
+	BF_HIP(hipMemsetAsync(d_red, 0, nred * 8, st));
+	if (int r = sk_bam_walk_reduce_dev(c, fr.d_out, fr.stream_len, fr.d_bend, fr.d_entry, fr.nb, max_frag, counters ? 1 : 0, hist ? 1 : 0, d_red)) return r;
 	std::vector<uint64_t> red(nred);
 	BF_HIP(hipMemcpyAsync(red.data(), d_red, nred * 8, hipMemcpyDeviceToHost, st));
 	BF_HIP(hipStreamSynchronize(st));
@@ -577,10 +622,74 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 	*handled = 1;
 	if (getenv("SK_BAMFILE_TRACE"))
 		fprintf(stderr, "sk_bam_file_reduce: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, reduce %.1f ms; %lld blocks, %llu by zlib\n",
-		        t_alloc - t0, t_read - t_alloc, t_inflated - t_read, t_header - t_inflated, t_walk - t_header, now_ms() - t_walk, (long long)nb, (unsigned long long)n_host);
-	if (info) {
-		info[0] = (double)fsize; info[1] = (double)stream_len; info[2] = (double)nb; info[3] = (double)n_records;
-		info[4] = (double)n_host; info[5] = (double)rounds; info[6] = t_read - t0; info[7] = now_ms() - t_read;
+		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, fr.t_walk - fr.t_header, now_ms() - fr.t_walk,
+		        (long long)fr.nb, (unsigned long long)fr.n_host);
+	front_info(fr, info);
+	return SK_OK;
+}
+
+// The records of the verified stream as SoA columns (include/seqkit_hip.h): the front half above, then one gather launch.  The
+// columns stay with the ctx (one allocation, each column 256-byte aligned); what cannot be had — the file, or the memory for the
+// columns — leaves *handled = 0 for the caller's reader.
+extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, sk_bam_columns *cols, int *handled, double info[8])
+{
+	if (!c || !path || !handled || !cols) return SK_ERR_INVALID;
+	*handled = 0;
+	memset(cols, 0, sizeof *cols);
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (want & ~(uint32_t)SK_COL_ALL) return sk::ctx_fail(c, SK_ERR_INVALID, "want = %#x", want);
+	if (int r = sk::ctx_bind(c)) return r;
+	Cleanup cl;
+	Front fr;
+	if (int r = bam_file_front(c, path, "sk_bam_file_columns", cl, fr, info)) return r;
+	if (!fr.ready) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const double t_gather = now_ms();
+	// ---- the columns: one kept allocation
+	enum { kKeepCols = 6 };
+	const uint64_t n = fr.n_records;
+	static const size_t width[8] = {2, 1, 4, 4, 4, 4, 4, 4};               // SK_COL_FLAG .. SK_COL_END
+	size_t at[8], total = 0;
+	for (int k = 0; k < 8; k++) {
+		at[k] = total;
+		if (want & (1u << k)) total += ((size_t)n * width[k] + 16 + 255) & ~(size_t)255;
 	}
+	int krc = SK_OK;
+	uint8_t *base = (uint8_t *)sk::ctx_keep(c, kKeepCols, total ? total : 256, false, &krc);
+	if (!base) {                                                         // (a busy device: the caller's reader serves the file)
+		if (info) info[5] = -21.0;
+		return SK_OK;
+	}
+	void *col[8];
+	for (int k = 0; k < 8; k++) col[k] = (want & (1u << k)) ? (void *)(base + at[k]) : nullptr;
+	// ---- where every block's first record goes: the exclusive prefix of the walk's counts
+	std::vector<uint64_t> rb((size_t)fr.nb + 1);
+	uint64_t run = 0;
+	for (int64_t i = 0; i < fr.nb; i++) { rb[(size_t)i] = run; run += fr.nrec[(size_t)i]; }
+	rb[(size_t)fr.nb] = run;
+	if (run != n) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_columns: %llu records by the blocks' counts, %llu by the walk", (unsigned long long)run, (unsigned long long)n);
+	if (want && fr.nb) {
+		uint64_t *d_rb = nullptr;
+		BF_HIP(hipMalloc((void **)&d_rb, rb.size() * 8)); cl.dev.push_back(d_rb);
+		BF_HIP(hipMemcpyAsync(d_rb, rb.data(), rb.size() * 8, hipMemcpyHostToDevice, st));
+		BF_HIP(sk::launch_bam_gather(fr.d_out, fr.stream_len, fr.d_bend, fr.d_entry, d_rb, fr.nb, (uint16_t *)col[0], (uint8_t *)col[1], (int32_t *)col[2],
+		                             (int32_t *)col[3], (int32_t *)col[4], (int32_t *)col[5], (int32_t *)col[6], (int32_t *)col[7], st));
+	}
+	BF_HIP(hipStreamSynchronize(st));
+	Ranges *keep = (Ranges *)sk::ctx_ext(c);
+	if (!keep) { keep = new Ranges; sk::ctx_set_ext(c, keep, Ranges::destroy); }
+	keep->header.swap(fr.header);
+	cols->n = (int64_t)n;
+	cols->flag = (uint16_t *)col[0]; cols->mapq = (uint8_t *)col[1]; cols->tid = (int32_t *)col[2]; cols->mtid = (int32_t *)col[3];
+	cols->pos = (int32_t *)col[4]; cols->mpos = (int32_t *)col[5]; cols->tlen = (int32_t *)col[6]; cols->end_pos = (int32_t *)col[7];
+	cols->header = keep->header.data();
+	cols->header_len = keep->header.size();
+	cols->n_ref = fr.n_ref;
+	*handled = 1;
+	if (getenv("SK_BAMFILE_TRACE"))
+		fprintf(stderr, "sk_bam_file_columns: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, gather %.1f ms; %lld blocks, %llu by zlib\n",
+		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_gather - fr.t_header, now_ms() - t_gather,
+		        (long long)fr.nb, (unsigned long long)fr.n_host);
+	front_info(fr, info);
 	return SK_OK;
 }

@@ -1347,6 +1347,64 @@ __global__ __launch_bounds__(256) void bam_walk_reduce_kernel(const WalkArgs a, 
 	if (lds_hist) for (int i = threadIdx.x; i <= max_frag; i += blockDim.x) if (lh[i]) atomicAdd(&out[4 + i], (unsigned long long)lh[i]);
 }
 
+// The fixed-core fields of every record of a verified chain, in file order, into SoA columns (sk_bam_file_columns).  A wave per
+// BGZF block: lane 0 follows the chain from entry[c] to the block's end and leaves every record's offset in LDS (a record begins
+// inside the block and takes at least 36 bytes: at most 65536 / 36 + 1 of them), then the 64 lanes take consecutive records and
+// store each column coalesced.  rec_base[c] = index of block c's first record (exclusive prefix of the walk's counts).
+// end_pos is BamStream::next(..., want_end)'s (sam_main.cpp): pos plus the lengths of the ops M D N = X (0 2 3 7 8), summed in
+// 64 bits and truncated; pos itself when the variable part is shorter than the read name and the CIGAR.
+constexpr int kGatherWaves = 4, kGatherRecs = 1824;
+struct GatherCols {
+	uint16_t *flag;
+	uint8_t *mapq;
+	int32_t *tid, *mtid, *pos, *mpos, *tlen, *end_pos;
+};
+__global__ __launch_bounds__(kGatherWaves * 64) void bam_gather_kernel(const WalkArgs a, const u64 *rec_base, GatherCols g)
+{
+	__shared__ uint16_t offs[kGatherWaves][kGatherRecs];                // (a record that begins in the block begins < 65536 bytes behind its entry)
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const int64_t c = (int64_t)blockIdx.x * kGatherWaves + w;
+	const bool live = c < a.n;
+	const u64 entry = live ? a.entry[c] : 0ull, end = live ? a.bend[c] : 0ull;
+	uint16_t *off = offs[w];
+	if (live && lane == 0) {
+		u32 k = 0u;
+		for (u64 o = entry; o < end && k < (u32)kGatherRecs; k++) {
+			off[k] = (uint16_t)(o - entry);
+			o += 4 + (u64)bam_le32(a.stream + o);
+		}
+	}
+	__syncthreads();
+	if (!live) return;
+	const u64 base = rec_base[c];
+	const u32 n = (u32)(rec_base[c + 1] - base);
+	for (u32 j = (u32)lane; j < n && j < (u32)kGatherRecs; j += 64u) {
+		const uint8_t *r = a.stream + entry + off[j];
+		const int64_t i = (int64_t)(base + j);
+		const int32_t p = (int32_t)bam_le32(r + 8);
+		const u32 w12 = bam_le32(r + 12), w16 = bam_le32(r + 16);              // l_read_name | mapq << 8 | bin; n_cigar_op | flag << 16
+		if (g.flag) g.flag[i] = (uint16_t)(w16 >> 16);
+		if (g.mapq) g.mapq[i] = (uint8_t)(w12 >> 8);
+		if (g.tid) g.tid[i] = (int32_t)bam_le32(r + 4);
+		if (g.pos) g.pos[i] = p;
+		if (g.mtid) g.mtid[i] = (int32_t)bam_le32(r + 24);
+		if (g.mpos) g.mpos[i] = (int32_t)bam_le32(r + 28);
+		if (g.tlen) g.tlen[i] = (int32_t)bam_le32(r + 32);
+		if (g.end_pos) {
+			const u32 bs = bam_le32(r), l_name = w12 & 0xffu, n_cigar = w16 & 0xffffu;
+			int64_t e = p;
+			if (bs - 32u >= l_name + 4u * n_cigar) {
+				const uint8_t *cg = r + 36 + l_name;
+				for (u32 k = 0; k < n_cigar; k++) {
+					const u32 op = bam_le32(cg + 4 * k), code = op & 15u;
+					if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) e += (int64_t)(op >> 4);
+				}
+			}
+			g.end_pos[i] = (int32_t)e;
+		}
+	}
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------------
 hipError_t launch_bgzf_inflate(const uint8_t *comp, const void *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status, int check_crc, int n_cu, hipStream_t st)
 {
@@ -1393,6 +1451,19 @@ hipError_t launch_bam_walk_reduce(const uint8_t *stream, uint64_t stream_len, co
 	a.stream = stream; a.stream_len = stream_len; a.bend = reinterpret_cast<const u64 *>(bend); a.entry = const_cast<u64 *>(reinterpret_cast<const u64 *>(entry));
 	a.exitp = nullptr; a.nrec = nullptr; a.n = n; a.first = 0; a.changed = nullptr;
 	bam_walk_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(a, max_frag, want_counters, want_hist, out);
+	return hipGetLastError();
+}
+
+hipError_t launch_bam_gather(const uint8_t *stream, uint64_t stream_len, const uint64_t *bend, const uint64_t *entry, const uint64_t *rec_base, int64_t n,
+                             uint16_t *flag, uint8_t *mapq, int32_t *tid, int32_t *mtid, int32_t *pos, int32_t *mpos, int32_t *tlen, int32_t *end_pos,
+                             hipStream_t st)
+{
+	if (n <= 0) return hipSuccess;
+	WalkArgs a;
+	a.stream = stream; a.stream_len = stream_len; a.bend = reinterpret_cast<const u64 *>(bend); a.entry = const_cast<u64 *>(reinterpret_cast<const u64 *>(entry));
+	a.exitp = nullptr; a.nrec = nullptr; a.n = n; a.first = 0; a.changed = nullptr;
+	GatherCols g{flag, mapq, tid, mtid, pos, mpos, tlen, end_pos};
+	bam_gather_kernel<<<(unsigned)((n + kGatherWaves - 1) / kGatherWaves), kGatherWaves * 64, 0, st>>>(a, reinterpret_cast<const u64 *>(rec_base), g);
 	return hipGetLastError();
 }
 

@@ -163,6 +163,9 @@ hipError_t launch_bam_walk(const uint8_t *stream, uint64_t stream_len, const uin
                            uint64_t first, uint32_t *changed, int fix_round /* 0 first walk, 1 fix, 2 guess */, int32_t n_ref, hipStream_t st);
 hipError_t launch_bam_walk_reduce(const uint8_t *stream, uint64_t stream_len, const uint64_t *bend, const uint64_t *entry, int64_t n, int32_t max_frag,
                                   int want_counters, int want_hist, unsigned long long *out, hipStream_t st);
+hipError_t launch_bam_gather(const uint8_t *stream, uint64_t stream_len, const uint64_t *bend, const uint64_t *entry, const uint64_t *rec_base, int64_t n,
+                             uint16_t *flag, uint8_t *mapq, int32_t *tid, int32_t *mtid, int32_t *pos, int32_t *mpos, int32_t *tlen, int32_t *end_pos,
+                             hipStream_t st);
 
 // ---- BGZF deflate on the device (sk_deflate.hip) ----
 // blocks: device array of sk_deflate_block; out: n_blocks slots of out_stride bytes (a block's payload from the slot's first byte on);
@@ -197,7 +200,7 @@ namespace sk {
 hipStream_t ctx_stream(sk_ctx *c);
 hipStream_t ctx_stream2(sk_ctx *c);
 int ctx_n_cu(sk_ctx *c);
-void *ctx_keep(sk_ctx *c, int slot, size_t bytes, bool pinned, int *rc);      // a buffer that stays with the ctx from call to call (freed by sk_destroy)
+void *ctx_keep(sk_ctx *c, int slot, size_t bytes, bool pinned, int *rc);      // a buffer that stays with the ctx from call to call, slot 0..11 (freed by sk_destroy)
 size_t ctx_kept_bytes(sk_ctx *c, int slot);
 void *ctx_ext(sk_ctx *c);                                       // an object kept with the ctx (freed by sk_destroy through free_fn)
 void ctx_set_ext(sk_ctx *c, void *p, void (*free_fn)(void *));

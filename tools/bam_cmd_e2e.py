@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""`sam fragments`, `sam count` and `sam count --single-end --center` from a BAM FILE: the device path (sk_bam_file_columns and the
+kernels behind it) against the host reader (SEQKIT_HOST_INFLATE=1), alternating, several runs each: wall time and CPU-seconds of
+every run, outputs of both paths and of the oracle command line checked identical.  Then sk_bam_file_columns' library-call time next
+to sk_bam_file_reduce's on the same file in one process.
+
+The fragments file is tools/bam_e2e.py's (100 k paired records, one in two kept, repeated); the count file is the same unit once per
+reference, with tid = the repeat's index, so it is coordinate-sorted with positions restarting per reference; the BED file holds
+about 20 k regions over those references.  usage: bam_cmd_e2e.py [million records (20)] [runs per path (3)] [--lib-only: the library
+calls alone, e.g. under rocprofv3 --kernel-trace --stats]"""
+import os
+import struct
+import subprocess
+import sys
+import tempfile
+import time
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+from hashlib import sha256
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+from oracle import oracle as orc  # noqa: E402
+from seqkit_amd import build  # noqa: E402
+
+orc.build()
+build.build_all()
+SAM = os.path.join(build.BINDIR, "sam")
+lib_only = "--lib-only" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--lib-only"]
+millions = int(argv[0]) if len(argv) > 0 else 20
+runs = int(argv[1]) if len(argv) > 1 else 3
+PAIRS = 50_000
+reps = millions * 1_000_000 // (2 * PAIRS)
+rng = np.random.default_rng(3)
+codes = np.array([1, 2, 4, 8], dtype=np.uint8)
+d = tempfile.mkdtemp(prefix="sk_bamcmd_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+bam, bed, out = os.path.join(d, "in.bam"), os.path.join(d, "r.bed"), os.path.join(d, "out.txt")
+
+
+def bgzf(data, level=1):
+    c = zlib.compressobj(level, zlib.DEFLATED, -15)
+    comp = c.compress(data) + c.flush()
+    return struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(comp) + 25) + comp + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data))
+
+
+unit = bytearray()
+starts, ends = [], []
+for i in range(PAIRS):
+    tl = int(rng.lognormal(np.log(170), 0.35))
+    for mate in (0, 1):
+        name = b"read%d\0" % i
+        nib = codes[rng.integers(0, 4, size=150)]
+        packed = ((nib[0::2] << 4) | nib[1::2]).astype(np.uint8).tobytes()
+        q = rng.integers(2, 41, size=150, dtype=np.uint8).tobytes()
+        flag = 1 | 2 | (64 | 32 if mate == 0 else 128 | 16)
+        body = struct.pack("<iiBBHHHiiii", 0, i, len(name), 60 if i % 7 else 10, 4680, 1, flag, 150, 0, i + (tl if mate == 0 else -tl),
+                           tl if mate == 0 else -tl) + name + struct.pack("<I", 150 << 4) + packed + q
+        starts.append(len(unit))
+        unit += struct.pack("<i", len(body)) + body
+        ends.append(len(unit))
+unit = bytes(unit)
+
+
+def blocks_of(u):
+    # what htslib writes: a block is flushed rather than a record split
+    out_, lo, prev = [], 0, 0
+    for e in ends:
+        if e - lo > 0xff00:
+            out_.append(bgzf(u[lo:prev]))
+            lo = prev
+        prev = e
+    out_.append(bgzf(u[lo:]))
+    return b"".join(out_)
+
+
+def header(n_ref):
+    text = b"@HD\tVN:1.6\tSO:coordinate\n"
+    h = b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", n_ref)
+    for r in range(n_ref):
+        nm = b"chr%d\0" % (r + 1)
+        h += struct.pack("<i", len(nm)) + nm + struct.pack("<i", 1 << 28)
+    return bgzf(h)
+
+
+def with_tid(t):
+    u = np.frombuffer(unit, dtype=np.uint8).copy()
+    o = np.array(starts, dtype=np.int64)
+    tb = np.frombuffer(struct.pack("<i", t), dtype=np.uint8)
+    for k in range(4):
+        u[o + 4 + k] = tb[k]
+        u[o + 24 + k] = tb[k]
+    return blocks_of(u.tobytes())
+
+
+def timed(args, env=None):
+    """one run: (wall s, CPU s of the child, rc, sha256 of stdout, stderr)"""
+    e = dict(os.environ)
+    e.pop("SEQKIT_HOST_INFLATE", None)
+    if env:
+        e.update(env)
+    with open(out, "wb") as fo:
+        t0 = time.perf_counter()
+        p = subprocess.Popen(args, stdout=fo, stderr=subprocess.PIPE, env=e)
+        err = p.stderr.read()
+        _, status, ru = os.wait4(p.pid, 0)
+        dt = time.perf_counter() - t0
+    p.returncode = os.waitstatus_to_exitcode(status)
+    h = sha256(open(out, "rb").read()).hexdigest()[:16]
+    return dt, ru.ru_utime + ru.ru_stime, p.returncode, h, err
+
+
+def compare(label, args):
+    rows = {"device": [], "host": []}
+    seen = set()
+    for _ in range(runs):
+        for path, env in (("device", None), ("host", {"SEQKIT_HOST_INFLATE": "1"})):
+            dt, cpu, rc, h, err = timed([SAM] + args, env)
+            rows[path].append((dt, cpu))
+            seen.add((rc, h, err))
+    dt, cpu, rc, h, err = timed([orc.SAM_BIN] + args)
+    seen.add((rc, h, err))
+    assert len(seen) == 1, f"{label}: outputs differ: {seen}"
+    tr = subprocess.run([SAM] + args, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, env=dict(os.environ, SK_BAMFILE_TRACE="1")).stderr
+    served = [ln for ln in tr.decode(errors="replace").split("\n") if ln.startswith("sam ")]
+    for path in ("device", "host"):
+        w = [r[0] for r in rows[path]]
+        c = [r[1] for r in rows[path]]
+        print(f"{label:34s} {path:6s} wall {min(w):6.2f} s (median {float(np.median(w)):6.2f})  CPU {float(np.median(c)):6.2f} s   "
+              + " ".join(f"{x:.2f}" for x in w), flush=True)
+    print(f"{label:34s} oracle wall {dt:6.2f} s  CPU {cpu:6.2f} s; outputs identical (rc {rc}, stdout sha256 {h}); trace: {served}", flush=True)
+    dev, host = float(np.median([r[0] for r in rows['device']])), float(np.median([r[0] for r in rows['host']]))
+    print(f"{label:34s} device / host wall (medians) = {dev / host:.2f}", flush=True)
+
+
+n = reps * 2 * PAIRS
+t0 = time.perf_counter()
+with open(bam, "wb") as f:
+    f.write(header(1))
+    body = blocks_of(unit)
+    for _ in range(reps):
+        f.write(body)
+    f.write(bgzf(b""))
+print(f"fragments file: {n} BAM records, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; {runs} runs per path", flush=True)
+if not lib_only:
+    compare("sam fragments", ["fragments", bam])
+
+# the library calls on the same file, one process
+import seqkit_amd  # noqa: E402
+from seqkit_amd import capi  # noqa: E402
+with seqkit_amd.Context(0) as ctx:
+    tc, tr_ = [], []
+    for _ in range(runs + 1):
+        t0 = time.perf_counter()
+        h, _, _, _, info = ctx.bam_file_reduce(bam, 5000)
+        tr_.append(time.perf_counter() - t0)
+        assert h
+        t0 = time.perf_counter()
+        h, dev, nn, _, info = ctx.bam_file_columns_dev(bam, capi.SK_COL_ALL)
+        tc.append(time.perf_counter() - t0)
+        assert h and nn == n
+    tr_, tc = tr_[1:], tc[1:]                                               # (the first pair: the buffers are taken)
+    print(f"library call, {n} records: sk_bam_file_reduce {1e3 * min(tr_):.0f} ms (median {1e3 * float(np.median(tr_)):.0f}), "
+          f"sk_bam_file_columns (all 8 fields) {1e3 * min(tc):.0f} ms (median {1e3 * float(np.median(tc)):.0f}): "
+          f"columns / reduce = {float(np.median(tc)) / float(np.median(tr_)):.2f}", flush=True)
+os.remove(bam)
+if lib_only:
+    os.rmdir(d)
+    sys.exit(0)
+
+t0 = time.perf_counter()
+with open(bam, "wb") as f:
+    f.write(header(reps))
+    with ThreadPoolExecutor(16) as ex:
+        for blob in ex.map(with_tid, range(reps)):
+            f.write(blob)
+    f.write(bgzf(b""))
+brng = np.random.default_rng(5)
+with open(bed, "w") as f:
+    for k in range(20_000):
+        s = int(brng.integers(0, PAIRS))
+        f.write(f"chr{int(brng.integers(1, reps + 1))}\t{s}\t{s + int(brng.integers(50, 3000))}\n")
+print(f"count file: {n} BAM records on {reps} references, sorted, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; "
+      f"20000 BED regions", flush=True)
+compare("sam count", ["count", bam, bed])
+compare("sam count --single-end --center", ["count", "--single-end", "--center", bam, bed])
+os.remove(bam)
+os.remove(bed)
+if os.path.exists(out):
+    os.remove(out)
+os.rmdir(d)
