@@ -371,6 +371,34 @@ typedef struct sk_bam_columns {
 } sk_bam_columns;
 int sk_bam_file_columns(sk_ctx *ctx, const char *path, uint32_t want, sk_bam_columns *cols, int *handled, double info[8]);
 
+/* ---- B1 for `sam to [interleaved] raw|fasta|fastq` (src/sam_to_fastq.rs:61-149) ------------------------
+ * sk_bam_file_reads: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0
+ * cases, info[] as there), then a device sizing pass over every record.  Records kept: neither 0x100 nor 0x800 (:102), and either
+ * not paired (flag & 0x1 == 0; only with want_unpaired) or paired and flagged 0x40 or 0x80 (:114-130).  The text of a kept record is
+ * what write_read (:138-149) writes for it — format 0 raw "SEQ\n", 1 fasta ">name\nSEQ\n", 2 fastq "@name\nSEQ\n+\nQUAL\n" — with SEQ
+ * = sequence(read, min_baseq) (:31-59) and QUAL = 33 + q in u8 arithmetic, in stored order.  *n_kept, *text_bytes: the kept records
+ * and their text.  *handled = 0 also, decided before any text is written, when a primary record's qname has a byte >= 0x80, when in
+ * fastq mode a primary record has a quality q with 33 + q >= 0x80, when a primary record has l_seq > 65532, when a record's
+ * variable part is shorter than its read name, CIGAR, bases and qualities, and when the device or host memory the call needs cannot
+ * be had.  A bad format: SK_ERR_INVALID.  window_bytes (0: 64 MiB) bounds the text + name bytes of one window (a single record may
+ * go beyond it).
+ * sk_bam_file_reads_next: the next window of kept records, in file order; w->n == 0 at the end.  The window's HOST arrays (the
+ * ctx's, page-locked) hold until the next call on the ctx; the device writes and copies the following window while the caller
+ * works on this one.  Calling it after another sk_bam_file_* call, or without sk_bam_file_reads: SK_ERR_INVALID.               */
+typedef struct sk_bam_reads_window {
+	int64_t first, n;              /* kept records first .. first + n - 1 (numbered in file order); n == 0: the end */
+	const uint8_t *text;           /* HOST, page-locked: the n records' write_read() texts back to back */
+	const uint64_t *text_off;      /* HOST: n + 1 offsets into text */
+	const uint8_t *kind;           /* HOST: 0 not paired (flag & 0x1 == 0), 1 first in template, 2 last in template */
+	const uint64_t *key;           /* HOST: 64-bit hash of the qname, computed on the device */
+	const uint8_t *names;          /* HOST: the qnames (no NUL) back to back ... */
+	const uint32_t *name_off;      /* ... n + 1 offsets */
+} sk_bam_reads_window;
+int sk_bam_file_reads(sk_ctx *ctx, const char *path, int format /* 0 raw, 1 fasta, 2 fastq */, uint8_t min_baseq,
+                      int want_unpaired, uint64_t window_bytes /* 0 = default */, int64_t *n_kept, uint64_t *text_bytes,
+                      int *handled, double info[8]);
+int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
+
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is
  * the decompressed stream.  sk_bgzf_deflate compresses n independent blocks of at most SK_DEFLATE_MAX_IN bytes (in +

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
     "sk_timer_start", "sk_timer_stop",
@@ -68,6 +68,15 @@ def bam_header_names(header: bytes) -> list:
         names.append(nm[:-1] if nm.endswith(b"\0") else nm)
         at += 8 + l_name
     return names
+
+
+class _ReadsWindow(C.Structure):
+    _fields_ = [("first", C.c_int64), ("n", C.c_int64), ("text", C.c_void_p), ("text_off", C.c_void_p), ("kind", C.c_void_p), ("key", C.c_void_p),
+                ("names", C.c_void_p), ("name_off", C.c_void_p)]
+
+
+# sk_bam_file_reads: output formats
+READS_FORMAT = {"raw": 0, "fasta": 1, "fastq": 2}
 
 
 class _Mate(C.Structure):
@@ -221,6 +230,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_walk_reduce_dev": (i32, [vp, vp, C.c_uint64, vp, vp, i64, i32, i32, i32, vp]),
         "sk_bam_file_reduce": (i32, [vp, C.c_char_p, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_columns": (i32, [vp, C.c_char_p, C.c_uint32, C.POINTER(_BamColumns), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_reads": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
         "sk_bam_fragments_bed_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(i64)]),
         "sk_count_order_check_dev": (i32, [vp, vp, vp, vp, vp, i64, C.c_uint8, i32, C.POINTER(i64), C.POINTER(i32)]),
         "sk_bam_fragments": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]),
@@ -395,6 +406,33 @@ class Context:
                     self.copy_d2h(a, dev[name])
                 out[name] = a
         return True, out, bam_header_names(header), info
+
+    def bam_file_reads(self, path: str, fmt: str = "fastq", min_baseq: int = 10, want_unpaired: bool = True, window_bytes: int = 0):
+        """sk_bam_file_reads: (handled, kept records, text bytes, info f64[8]); then bam_file_reads_windows() yields the windows."""
+        n_kept, text_bytes, handled = C.c_int64(0), C.c_uint64(0), C.c_int32(0)
+        info = (C.c_double * 8)()
+        f = READS_FORMAT[fmt] if isinstance(fmt, str) else int(fmt)
+        self._check(self._lib.sk_bam_file_reads(self._h, os.fsencode(path), f, min_baseq, 1 if want_unpaired else 0, window_bytes, C.byref(n_kept),
+                                                C.byref(text_bytes), C.byref(handled), info), "sk_bam_file_reads")
+        return bool(handled.value), int(n_kept.value), int(text_bytes.value), [float(x) for x in info]
+
+    def bam_file_reads_windows(self):
+        """sk_bam_file_reads_next until the end: one dict of numpy copies per window (first, n, text, text_off, kind, key, names,
+        name_off)."""
+        while True:
+            w = _ReadsWindow()
+            self._check(self._lib.sk_bam_file_reads_next(self._h, C.byref(w)), "sk_bam_file_reads_next")
+            if w.n == 0:
+                return
+            n = int(w.n)
+
+            def arr(ptr, count, dt):
+                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(count,)).copy() if count else np.empty(0, dt)
+            text_off = arr(w.text_off, n + 1, np.uint64)
+            name_off = arr(w.name_off, n + 1, np.uint32)
+            yield {"first": int(w.first), "n": n, "text": C.string_at(w.text, int(text_off[-1])) if text_off[-1] else b"", "text_off": text_off,
+                   "kind": arr(w.kind, n, np.uint8), "key": arr(w.key, n, np.uint64),
+                   "names": C.string_at(w.names, int(name_off[-1])) if name_off[-1] else b"", "name_off": name_off}
 
     def bam_fragments_bed_dev(self, keep_bits: int, tid: int, pos: int, tlen: int, n: int, names):
         """sk_bam_fragments_bed_dev over device columns: (BED text bytes, index of the first kept record with a bad tid or -1).

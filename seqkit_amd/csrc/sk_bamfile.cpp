@@ -168,10 +168,32 @@ struct Mapper {
 	bool wait_for(size_t bytes) { std::unique_lock<std::mutex> lk(m); if (bytes > want) { want = std::min(bytes, r->reserved); cv.notify_all(); } cv.wait(lk, [&] { return failed || have >= bytes; }); return !failed; }
 	~Mapper() { if (th.joinable()) { { std::lock_guard<std::mutex> lk(m); stop = true; cv.notify_all(); } th.join(); } }
 };
+// sk_bam_file_reads / sk_bam_file_reads_next: the kept records' columns (device, ctx slot kKeepReadCols), the window plan, and two
+// window buffers on each side (ctx slots kKeepReadWin / kKeepReadPin), one window in flight while the caller works on the other
+struct ReadsState {
+	bool live = false;
+	uint64_t gen = 0;                            // Ranges::gen of the file call that set it up
+	int fmt = 0;
+	uint8_t min_baseq = 10;
+	const uint8_t *d_out = nullptr;
+	uint64_t *krec = nullptr, *ktoff = nullptr, *knoff = nullptr, *kkey = nullptr;
+	uint8_t *kkind = nullptr;
+	std::vector<uint64_t> ws, wt, wn;            // window w: kept records ws[w] .., text bytes wt[w] .., name bytes wn[w] .. (up to w + 1)
+	size_t next_w = 0;                           // the next window to issue
+	uint8_t *d_win[2] = {nullptr, nullptr}, *h_win[2] = {nullptr, nullptr};
+	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	int64_t first[2] = {0, 0}, n[2] = {0, 0};
+	int cur = -1;                                // the buffer whose window is in flight, -1: none (the end)
+	~ReadsState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 // what stays with the ctx: the range of the compressed file and the range of the inflated stream
 struct Ranges {
 	OutRange comp, out;
 	std::vector<uint8_t> header;                 // sk_bam_file_columns: the last file's header bytes (cols->header)
+	uint64_t gen = 0;                            // file calls so far: a reads state of an earlier call is stale
+	ReadsState reads;
 	static void destroy(void *p) { Ranges *r = (Ranges *)p; r->comp.release(); r->out.release(); delete r; }
 };
 
@@ -269,6 +291,14 @@ struct Front {
 // in trace lines.
 static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup &cl, Front &fr, double info[8])
 {
+	Ranges *both = (Ranges *)sk::ctx_ext(c);
+	if (!both) { both = new Ranges; sk::ctx_set_ext(c, both, Ranges::destroy); }
+	// an earlier sk_bam_file_reads may have left a window in flight on the ctx stream: its text kernel reads the inflated stream and its
+	// copies write the page-locked window buffers.  It ends before this call remaps the ranges or takes the kept buffers again.
+	if (both->reads.live || both->reads.cur >= 0) BF_HIP(hipStreamSynchronize(sk::ctx_stream(c)));
+	both->gen++;                                                        // (what an earlier sk_bam_file_reads left is no longer read)
+	both->reads.live = false;
+	both->reads.cur = -1;
 	cl.fd = open(path, O_RDONLY);
 	if (cl.fd < 0) BF_LEAVE(1);                                        // (the caller's reader says so in the reference's words)
 	struct stat sb;
@@ -288,12 +318,10 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 	uint64_t out_cap = std::max<uint64_t>(fsize * 6, (uint64_t)256 << 20);
 	if (const char *ev = getenv("SK_BAMFILE_OUT_FACTOR")) { const int f = atoi(ev); if (f >= 1 && f <= 1100) out_cap = std::max<uint64_t>(fsize * (uint64_t)f, (uint64_t)1 << 20); }
 	uint8_t *d_out = nullptr, *d_comp = nullptr;
-	Ranges *both = (Ranges *)sk::ctx_ext(c);
 	OutRange *range = nullptr, *crange = nullptr;
 	if (!getenv("SK_BAMFILE_NO_VMM")) {
 		int dev = 0;
 		BF_HIP(hipGetDevice(&dev));
-		if (!both) { both = new Ranges; sk::ctx_set_ext(c, both, Ranges::destroy); }
 		if (both->out.va && both->out.reserved < out_cap + 256) both->out.release();
 		if (both->comp.va && both->comp.reserved < fsize + 64) both->comp.release();
 		// (the compressed file's range only for big files: mapping costs ~12 ms per 512 MiB whoever asks, a plain allocation of a few GB
@@ -691,5 +719,156 @@ extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, s
 		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_gather - fr.t_header, now_ms() - t_gather,
 		        (long long)fr.nb, (unsigned long long)fr.n_host);
 	front_info(fr, info);
+	return SK_OK;
+}
+
+// ---- sam to raw|fasta|fastq (include/seqkit_hip.h: sk_bam_file_reads, sk_bam_file_reads_next) ----------------------------------
+// The front half above, then the sizing pass (per block: kept records, text bytes, name bytes, decline bits) and its scans; the
+// decision to serve the file is taken there, before any text exists.  Then the kept records' columns, the windows, and the first
+// window's text on its way.  Every allocation that fails leaves the file to the caller's reader (info[5] = -21).
+
+// window w of the plan (the next non-empty one) into buffer b: the text kernel, then the copies back; false: no window left
+static bool reads_issue(sk_ctx *c, ReadsState &s, int b, int *rc)
+{
+	*rc = SK_OK;
+	while (s.next_w + 1 < s.ws.size() && s.ws[s.next_w + 1] == s.ws[s.next_w]) s.next_w++;
+	if (s.next_w + 1 >= s.ws.size()) return false;
+	const size_t w = s.next_w++;
+	const int64_t first = (int64_t)s.ws[w], n = (int64_t)(s.ws[w + 1] - s.ws[w]);
+	const uint64_t t0 = s.wt[w], tb = s.wt[w + 1] - t0, n0 = s.wn[w], nbytes = s.wn[w + 1] - n0;
+	hipStream_t st = sk::ctx_stream(c);
+	uint8_t *d = s.d_win[b], *h = s.h_win[b];
+	hipError_t e = sk::launch_bam_reads_text(s.d_out, s.krec, s.ktoff, s.knoff, first, n, t0, n0, s.fmt, s.min_baseq, d, (uint64_t *)(d + s.at_toff),
+	                                         d + s.at_names, (uint32_t *)(d + s.at_noff), sk::ctx_n_cu(c), st);
+	if (e == hipSuccess && tb) e = hipMemcpyAsync(h, d, (size_t)tb, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(h + s.at_toff, d + s.at_toff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(h + s.at_noff, d + s.at_noff, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && nbytes) e = hipMemcpyAsync(h + s.at_names, d + s.at_names, (size_t)nbytes, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(h + s.at_kind, s.kkind + first, (size_t)n, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(h + s.at_key, s.kkey + first, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipEventRecord(s.ev[b], st);
+	if (e != hipSuccess) { *rc = sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_reads: window %zu: %s", w, hipGetErrorString(e)); return false; }
+	s.first[b] = first; s.n[b] = n;
+	return true;
+}
+
+extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_t min_baseq, int want_unpaired, uint64_t window_bytes, int64_t *n_kept,
+                                 uint64_t *text_bytes, int *handled, double info[8])
+{
+	if (!c || !path || !handled) return SK_ERR_INVALID;
+	*handled = 0;
+	if (n_kept) *n_kept = 0;
+	if (text_bytes) *text_bytes = 0;
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (format < 0 || format > 2) return sk::ctx_fail(c, SK_ERR_INVALID, "format = %d", format);
+	if (int r = sk::ctx_bind(c)) return r;
+	Cleanup cl;
+	Front fr;
+	if (int r = bam_file_front(c, path, "sk_bam_file_reads", cl, fr, info)) return r;
+	if (!fr.ready) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const double t_size = now_ms();
+	const int64_t nb = fr.nb;
+	// ---- the sizing pass: per block kept records, text and name bytes (then their exclusive offsets), the decline bits, the longest record
+	uint64_t *d_blk = nullptr;
+	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 24 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+	cl.dev.push_back(d_blk);
+	uint64_t *bk = d_blk, *bt = bk + nb + 1, *bn = bt + nb + 1;
+	uint32_t *d_decline = (uint32_t *)(bn + nb + 1);
+	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
+	BF_HIP(sk::launch_bam_reads_size(fr.d_out, fr.d_bend, fr.d_entry, nb, format, want_unpaired ? 1 : 0, bk, bt, bn, d_decline, st));
+	uint64_t tot[3] = {0, 0, 0};                                        // kept, text, names
+	uint32_t decline = 0;
+	BF_HIP(hipMemcpyAsync(tot, bk + nb, 8, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipMemcpyAsync(tot + 1, bt + nb, 8, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipMemcpyAsync(tot + 2, bn + nb, 8, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipStreamSynchronize(st));
+	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_reads: declined (bits %#x)\n", decline);
+	if (decline) BF_LEAVE(30 + decline);                                // (1 qname, 2 fastq quality, 4 l_seq, 8 invalid record: info[5] = -31 .. -45)
+	const int64_t K = (int64_t)tot[0];
+	const uint64_t T = tot[1], N = tot[2];
+	// ---- the kept records' columns (ctx slot 9): stream offset, text offset, name offset, key, kind
+	enum { kKeepReadCols = 9, kKeepReadWin = 10, kKeepReadPin = 11 };
+	int krc = SK_OK;
+	const size_t kcol = ((size_t)K * 8 + 255) & ~(size_t)255;
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, kKeepReadCols, kcol * 4 + (((size_t)K + 255) & ~(size_t)255) + 256, false, &krc);
+	if (!kb) BF_LEAVE(21);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	ReadsState &s = R->reads;
+	s.krec = (uint64_t *)kb; s.ktoff = (uint64_t *)(kb + kcol); s.knoff = (uint64_t *)(kb + 2 * kcol); s.kkey = (uint64_t *)(kb + 3 * kcol); s.kkind = kb + 4 * kcol;
+	BF_HIP(sk::launch_bam_reads_index(fr.d_out, fr.d_bend, fr.d_entry, nb, format, want_unpaired ? 1 : 0, bk, bt, bn, s.krec, s.ktoff, s.knoff, s.kkey, s.kkind, st));
+	// ---- the windows: at most W text + name bytes each (one record may go beyond)
+	uint64_t W = window_bytes ? window_bytes : (uint64_t)64 << 20;
+	W = std::min<uint64_t>(std::max<uint64_t>(W, 256), (uint64_t)1 << 30);
+	const int64_t nw = K ? (int64_t)((T + N) / W + 2) : 1;
+	s.ws.assign((size_t)nw, (uint64_t)K); s.wt.assign((size_t)nw, T); s.wn.assign((size_t)nw, N);
+	if (K) {
+		uint64_t *d_w = nullptr;
+		if (hipMalloc((void **)&d_w, (size_t)nw * 24) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+		cl.dev.push_back(d_w);
+		BF_HIP(sk::launch_bam_reads_windows(s.ktoff, s.knoff, K, W, T, N, d_w, d_w + nw, d_w + 2 * nw, nw, st));
+		BF_HIP(hipMemcpyAsync(s.ws.data(), d_w, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipMemcpyAsync(s.wt.data(), d_w + nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipMemcpyAsync(s.wn.data(), d_w + 2 * nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	uint64_t max_n = 0, max_t = 0, max_nm = 0;
+	for (int64_t w = 0; w + 1 < nw; w++) {
+		max_n = std::max(max_n, s.ws[(size_t)w + 1] - s.ws[(size_t)w]);
+		max_t = std::max(max_t, s.wt[(size_t)w + 1] - s.wt[(size_t)w]);
+		max_nm = std::max(max_nm, s.wn[(size_t)w + 1] - s.wn[(size_t)w]);
+	}
+	// ---- two window buffers, on the device and page-locked, in one layout
+	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
+	s.at_toff = up(max_t + 16);
+	s.at_noff = s.at_toff + up((max_n + 1) * 8);
+	s.at_names = s.at_noff + up((max_n + 1) * 4);
+	s.at_kind = s.at_names + up(max_nm + 16);
+	s.at_key = s.at_kind + up(max_n + 16);
+	const size_t wbytes = s.at_key + up(max_n * 8 + 16);
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, kKeepReadWin, 2 * wbytes, false, &krc);
+	if (!dw) BF_LEAVE(21);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, kKeepReadPin, 2 * wbytes, true, &krc);
+	if (!hw) BF_LEAVE(21);
+	for (int b = 0; b < 2; b++) {
+		s.d_win[b] = dw + (size_t)b * wbytes; s.h_win[b] = hw + (size_t)b * wbytes;
+		if (!s.ev[b] && hipEventCreateWithFlags(&s.ev[b], hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); s.ev[b] = nullptr; BF_LEAVE(21); }
+	}
+	s.fmt = format; s.min_baseq = min_baseq; s.d_out = fr.d_out; s.next_w = 0; s.cur = -1;
+	s.gen = R->gen;
+	int rc = SK_OK;
+	if (reads_issue(c, s, 0, &rc)) s.cur = 0;
+	if (rc) return rc;
+	s.live = true;
+	if (n_kept) *n_kept = K;
+	if (text_bytes) *text_bytes = T;
+	*handled = 1;
+	if (getenv("SK_BAMFILE_TRACE"))
+		fprintf(stderr, "sk_bam_file_reads: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, size + index + plan %.1f ms; %lld blocks, %llu by zlib; %lld kept, %llu text bytes, %lld windows\n",
+		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_size - fr.t_header, now_ms() - t_size,
+		        (long long)fr.nb, (unsigned long long)fr.n_host, (long long)K, (unsigned long long)T, (long long)(nw - 1));
+	front_info(fr, info);
+	return SK_OK;
+}
+
+extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
+{
+	if (!c || !w) return SK_ERR_INVALID;
+	memset(w, 0, sizeof *w);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	if (!R || !R->reads.live || R->reads.gen != R->gen) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_reads_next: no sk_bam_file_reads in progress");
+	if (int r = sk::ctx_bind(c)) return r;
+	ReadsState &s = R->reads;
+	const int b = s.cur;
+	if (b < 0) return SK_OK;                                            // the end
+	int rc = SK_OK;
+	s.cur = reads_issue(c, s, b ^ 1, &rc) ? (b ^ 1) : -1;                 // (the buffer of the window returned last time: the caller is done with it)
+	if (rc) { s.live = false; return rc; }
+	BF_HIP(hipEventSynchronize(s.ev[b]));
+	const uint8_t *h = s.h_win[b];
+	w->first = s.first[b]; w->n = s.n[b];
+	w->text = h; w->text_off = (const uint64_t *)(h + s.at_toff); w->kind = h + s.at_kind; w->key = (const uint64_t *)(h + s.at_key);
+	w->names = h + s.at_names; w->name_off = (const uint32_t *)(h + s.at_noff);
 	return SK_OK;
 }

@@ -1,5 +1,5 @@
 // sk_bamtext.hip — the order-dependent and text halves of `sam fragments` and `sam count` over device columns
-// (include/seqkit_hip.h: sk_bam_fragments_bed_dev, sk_count_order_check_dev).
+// (include/seqkit_hip.h: sk_bam_fragments_bed_dev, sk_count_order_check_dev), and the passes behind sk_bam_file_reads (`sam to`).
 //
 // bam_bed_len_kernel / bam_bed_write_kernel — the BED line of every kept record (src/sam_fragments.rs:41), in record order.  A lane
 // owns one byte of keep bits: 8 records.  The first pass sums each workgroup's line lengths, one workgroup turns the sums into
@@ -254,6 +254,240 @@ __global__ __launch_bounds__(kScanThreads) void count_order_join_kernel(const Or
 	}
 }
 
+// ---- sam to raw|fasta|fastq: the reads of a verified BAM stream (sk_bam_file_reads) ------------------------------------------
+// bam_reads_size_kernel / bam_reads_index_kernel — a wave per BGZF block follows the chain from entry[c] (bam_gather_kernel's shape:
+// lane 0 leaves the records' offsets in LDS, then the lanes take consecutive records).  The first pass sums, per block, the kept
+// records, their text bytes and their name bytes, and ORs every record's decline bits; after the scans, the second pass writes the
+// kept records' columns at their kept index: stream offset, text offset, name offset, kind and qname key.
+// bam_reads_window_kernel — where each window of at most W text + name bytes begins.
+// bam_reads_text_kernel — the text of one window: a 16-lane group owns a record and covers its output in consecutive dwords, each
+// composed by output address (the dwords it shares with its neighbours are written bytewise).
+constexpr int kReadsWaves = 4, kReadsRecs = 1824;                      // (a record that begins in a block takes >= 36 bytes of its 64 KiB)
+
+struct ReadsArgs {
+	const uint8_t *stream;
+	const u64 *bend, *entry;
+	int64_t nb;
+	int fmt, want_unpaired;
+	u64 *bk, *bt, *bn;       // [nb + 1]: per block kept records / text bytes / name bytes, then (bam_scan_u64_kernel) exclusive offsets
+	uint32_t *decline;       // OR of the records' decline bits: 1 qname byte >= 0x80, 2 fastq quality, 4 l_seq > 65532, 8 invalid record
+	u64 *krec, *ktoff, *knoff, *kkey;
+	uint8_t *kkind;
+};
+
+__device__ __forceinline__ uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+struct ReadRec { uint32_t kept, kind, tlen, nlen; };
+
+// the record at r: kept or not, its kind and text length (src/sam_to_fastq.rs:102,114-130,138-149); with `decline`, the reasons the
+// host reader must serve the file instead (include/seqkit_hip.h)
+__device__ __forceinline__ ReadRec reads_rec(const uint8_t *r, int fmt, int want_unpaired, uint32_t *decline)
+{
+	ReadRec o{0u, 0u, 0u, 0u};
+	const uint32_t bs = rd32(r), w12 = rd32(r + 12), w16 = rd32(r + 16), S = rd32(r + 20);
+	const uint32_t l_name = w12 & 0xffu, n_cigar = w16 & 0xffffu, f = w16 >> 16;
+	if (bs < 32u || l_name < 1u || S > 0x7fffffffu || 4ull * n_cigar + l_name + (((u64)S + 1) >> 1) + S > (u64)(bs - 32u)) {
+		if (decline) *decline |= 8u;                                       // htslib: "Invalid BAM record."
+		return o;
+	}
+	if (f & (0x100u | 0x800u)) return o;                                   // :102
+	const uint32_t L = l_name - 1u;
+	if (decline) {
+		uint32_t d = 0u;
+		if (S > 65532u) d |= 4u;
+		const uint8_t *nm = r + 36;
+		for (uint32_t k = 0; k < L; k++) d |= (nm[k] & 0x80u) ? 1u : 0u;                  // :104 str::from_utf8
+		if (fmt == 2 && S <= 65532u) {
+			const uint8_t *q = nm + l_name + 4u * n_cigar + ((S + 1u) >> 1);
+			uint32_t hi = 0u;
+			for (uint32_t k = 0; k < S; k++) hi |= (uint32_t)(uint8_t)(33u + q[k]);     // char::from(33 + q) >= 0x80: two bytes
+			if (hi & 0x80u) d |= 2u;
+		}
+		*decline |= d;
+	}
+	o.kind = !(f & 0x1u) ? 0u : (f & 0x40u) ? 1u : (f & 0x80u) ? 2u : 3u;
+	o.kept = o.kind == 0u ? (want_unpaired ? 1u : 0u) : (o.kind != 3u ? 1u : 0u);
+	if (!o.kept) return o;
+	o.nlen = L;
+	o.tlen = fmt == 2 ? L + 2u * S + 6u : fmt == 1 ? L + S + 3u : S + 1u;
+	return o;
+}
+
+__device__ __forceinline__ uint32_t reads_offsets(const ReadsArgs &a, int64_t c, uint16_t *off, int lane)
+{
+	uint32_t k = 0u;
+	if (lane == 0) {
+		const u64 entry = a.entry[c], end = a.bend[c];
+		for (u64 o = entry; o < end && k < (uint32_t)kReadsRecs; k++) {
+			off[k] = (uint16_t)(o - entry);
+			o += 4 + (u64)rd32(a.stream + o);
+		}
+	}
+	__builtin_amdgcn_wave_barrier();
+	return (uint32_t)__shfl((int)k, 0);
+}
+
+__global__ __launch_bounds__(kReadsWaves * 64) void bam_reads_size_kernel(const ReadsArgs a)
+{
+	__shared__ uint16_t offs[kReadsWaves][kReadsRecs];
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const int64_t c = (int64_t)blockIdx.x * kReadsWaves + w;
+	if (c >= a.nb) return;                                                 // (no workgroup barrier below: each wave uses its own LDS)
+	uint16_t *off = offs[w];
+	const uint32_t n = reads_offsets(a, c, off, lane);
+	const u64 entry = a.entry[c];
+	u64 kept = 0, tb = 0, nb = 0;
+	uint32_t dec = 0u;
+	for (uint32_t j = (uint32_t)lane; j < n; j += 64u) {
+		const ReadRec rr = reads_rec(a.stream + entry + off[j], a.fmt, a.want_unpaired, &dec);
+		kept += rr.kept; tb += rr.tlen; nb += rr.nlen;
+	}
+	for (int s = 32; s > 0; s >>= 1) {
+		kept += __shfl_xor(kept, s); tb += __shfl_xor(tb, s); nb += __shfl_xor(nb, s);
+		dec |= (uint32_t)__shfl_xor((int)dec, s);
+	}
+	if (lane == 0) {
+		a.bk[c] = kept; a.bt[c] = tb; a.bn[c] = nb;
+		if (dec) atomicOr(a.decline, dec);
+	}
+}
+
+// FNV-1a over the qname, then a finalizer (murmur3's fmix64)
+__device__ __forceinline__ u64 qname_key(const uint8_t *p, uint32_t n)
+{
+	u64 h = 0xcbf29ce484222325ull;
+	for (uint32_t k = 0; k < n; k++) h = (h ^ p[k]) * 0x100000001b3ull;
+	h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+	return h;
+}
+
+__device__ __forceinline__ u64 wave_incl_scan(u64 x, int lane)
+{
+	for (int s = 1; s < 64; s <<= 1) {
+		const u64 y = __shfl_up(x, s);
+		if (lane >= s) x += y;
+	}
+	return x;
+}
+
+__global__ __launch_bounds__(kReadsWaves * 64) void bam_reads_index_kernel(const ReadsArgs a)
+{
+	__shared__ uint16_t offs[kReadsWaves][kReadsRecs];
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const int64_t c = (int64_t)blockIdx.x * kReadsWaves + w;
+	if (c >= a.nb) return;
+	uint16_t *off = offs[w];
+	const uint32_t n = reads_offsets(a, c, off, lane);
+	const u64 entry = a.entry[c];
+	u64 kb = a.bk[c], tb = a.bt[c], nb = a.bn[c];                       // where the block's first kept record goes
+	for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
+		const uint32_t j = j0 + (uint32_t)lane;
+		ReadRec rr{0u, 0u, 0u, 0u};
+		const uint8_t *r = a.stream + entry + (j < n ? off[j] : 0);
+		if (j < n) rr = reads_rec(r, a.fmt, a.want_unpaired, nullptr);
+		const u64 ik = wave_incl_scan(rr.kept, lane), it = wave_incl_scan(rr.tlen, lane), in = wave_incl_scan(rr.nlen, lane);
+		if (rr.kept) {
+			const u64 k = kb + ik - 1;
+			a.krec[k] = entry + off[j];
+			a.ktoff[k] = tb + it - rr.tlen;
+			a.knoff[k] = nb + in - rr.nlen;
+			a.kkind[k] = (uint8_t)rr.kind;
+			a.kkey[k] = qname_key(r + 36, rr.nlen);
+		}
+		kb += __shfl(ik, 63); tb += __shfl(it, 63); nb += __shfl(in, 63);
+	}
+}
+
+// window w = the kept records whose text + name offset lies in [w W, (w + 1) W): ws[w] its first record, wt[w] / wn[w] its first text /
+// name byte; entries past the last record's window hold (n, total text, total names).  nw entries in all.
+__global__ __launch_bounds__(256) void bam_reads_window_kernel(const u64 *ktoff, const u64 *knoff, int64_t n, u64 W, u64 total_t, u64 total_n,
+                                                               u64 *ws, u64 *wt, u64 *wn, int64_t nw)
+{
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= n) return;
+	const u64 cur = (ktoff[j] + knoff[j]) / W;
+	const u64 from = j ? (ktoff[j - 1] + knoff[j - 1]) / W + 1 : 0;
+	for (u64 v = from; v <= cur && (int64_t)v < nw; v++) { ws[v] = (u64)j; wt[v] = ktoff[j]; wn[v] = knoff[j]; }
+	if (j == n - 1)
+		for (int64_t v = (int64_t)cur + 1; v < nw; v++) { ws[v] = (u64)n; wt[v] = total_t; wn[v] = total_n; }
+}
+
+struct ReadsText {
+	const uint8_t *stream;
+	const u64 *krec, *ktoff, *knoff;
+	int64_t first, n;
+	u64 t0, n0;
+	int fmt;
+	uint32_t min_baseq;
+	uint8_t *text, *names;
+	u64 *toff;
+	uint32_t *noff;
+};
+
+// byte p of a record's text (write_read, src/sam_to_fastq.rs:138-149; SEQ as sequence(), :31-59)
+__device__ __forceinline__ uint32_t reads_byte(uint32_t p, int fmt, const uint8_t *name, uint32_t L, const uint8_t *seq4, const uint8_t *qual, uint32_t S,
+                                               bool rev, uint32_t min_baseq)
+{
+	if (fmt != 0) {
+		if (p == 0u) return fmt == 2 ? '@' : '>';
+		if (p <= L) return name[p - 1u];
+		if (p == L + 1u) return '\n';
+		p -= L + 2u;
+	}
+	if (p < S) {
+		const uint32_t s = rev ? S - 1u - p : p;
+		if (qual[s] < min_baseq) return 'N';
+		const uint32_t code = (seq4[s >> 1] >> ((s & 1u) ? 0 : 4)) & 15u;
+		// 1 2 4 8 -> A C G T (reverse strand: T G C A), anything else N
+		const uint32_t fw = code == 1u ? 'A' : code == 2u ? 'C' : code == 4u ? 'G' : code == 8u ? 'T' : 'N';
+		if (!rev) return fw;
+		return fw == 'A' ? 'T' : fw == 'C' ? 'G' : fw == 'G' ? 'C' : fw == 'T' ? 'A' : 'N';
+	}
+	if (p == S || fmt != 2) return '\n';
+	if (p == S + 1u) return '+';
+	if (p == S + 2u) return '\n';
+	p -= S + 3u;
+	if (p < S) return (uint8_t)(33u + qual[p]);
+	return '\n';
+}
+
+constexpr int kTextThreads = 256;
+__global__ __launch_bounds__(kTextThreads) void bam_reads_text_kernel(const ReadsText a)
+{
+	const int gl = threadIdx.x & 15;
+	const int64_t gstride = ((int64_t)gridDim.x * kTextThreads) >> 4;
+	for (int64_t j = ((int64_t)blockIdx.x * kTextThreads + threadIdx.x) >> 4; j < a.n; j += gstride) {
+		const int64_t k = a.first + j;
+		const uint8_t *r = a.stream + a.krec[k];
+		const uint32_t w12 = rd32(r + 12), w16 = rd32(r + 16), S = rd32(r + 20);
+		const uint32_t l_name = w12 & 0xffu, n_cigar = w16 & 0xffffu, L = l_name - 1u;
+		const bool rev = (w16 >> 16) & 0x10u;
+		const uint8_t *name = r + 36, *seq4 = name + l_name + 4u * n_cigar, *qual = seq4 + ((S + 1u) >> 1);
+		const uint32_t tlen = a.fmt == 2 ? L + 2u * S + 6u : a.fmt == 1 ? L + S + 3u : S + 1u;
+		const u64 tb = a.ktoff[k] - a.t0, nbo = a.knoff[k] - a.n0;
+		if (gl == 0) {
+			a.toff[j] = tb; a.noff[j] = (uint32_t)nbo;
+			if (j == a.n - 1) { a.toff[a.n] = tb + tlen; a.noff[a.n] = (uint32_t)(nbo + L); }
+		}
+		for (uint32_t q = (uint32_t)gl; q < L; q += 16u) a.names[nbo + q] = name[q];
+		const u64 te = tb + tlen, d0 = tb >> 2, d1 = (te - 1) >> 2;
+		for (u64 d = d0 + (u64)gl; d <= d1; d += 16u) {
+			const u64 p0 = d << 2;
+			if (p0 >= tb && p0 + 4 <= te) {
+				const uint32_t p = (uint32_t)(p0 - tb);
+				uint32_t wv = 0u;
+				for (uint32_t b = 0; b < 4u; b++) wv |= reads_byte(p + b, a.fmt, name, L, seq4, qual, S, rev, a.min_baseq) << (8u * b);
+				*reinterpret_cast<uint32_t *>(a.text + p0) = wv;
+			} else {
+				for (uint32_t b = 0; b < 4u; b++) {
+					const u64 pp = p0 + b;
+					if (pp >= tb && pp < te) a.text[pp] = (uint8_t)reads_byte((uint32_t)(pp - tb), a.fmt, name, L, seq4, qual, S, rev, a.min_baseq);
+				}
+			}
+		}
+	}
+}
+
 }  // namespace sk
 
 namespace {
@@ -373,3 +607,60 @@ extern "C" int sk_count_order_check_dev(sk_ctx *c, const uint16_t *flag, const u
 	if (s != ~0ull) { *first_stop = (int64_t)(s >> 1); *code = (s & 1ull) ? 255 : 101; }
 	return SK_OK;
 }
+
+// ---- launchers of the reads passes (sk_bamfile.cpp: sk_bam_file_reads) ---------------------------------------------------------
+namespace sk {
+hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
+                                 uint64_t *bk, uint64_t *bt, uint64_t *bn, uint32_t *decline, hipStream_t st)
+{
+	ReadsArgs a{};
+	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.fmt = fmt; a.want_unpaired = want_unpaired;
+	a.bk = (u64 *)bk; a.bt = (u64 *)bt; a.bn = (u64 *)bn; a.decline = decline;
+	if (nb > 0) {
+		bam_reads_size_kernel<<<(unsigned)((nb + kReadsWaves - 1) / kReadsWaves), kReadsWaves * 64, 0, st>>>(a);
+		if (hipError_t e = hipGetLastError()) return e;
+	}
+	for (u64 *v : {a.bk, a.bt, a.bn}) {
+		bam_scan_u64_kernel<<<1, kScanThreads, 0, st>>>(v, nb);
+		if (hipError_t e = hipGetLastError()) return e;
+	}
+	return hipSuccess;
+}
+
+hipError_t launch_bam_reads_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
+                                  const uint64_t *bk, const uint64_t *bt, const uint64_t *bn, uint64_t *krec, uint64_t *ktoff, uint64_t *knoff,
+                                  uint64_t *kkey, uint8_t *kkind, hipStream_t st)
+{
+	if (nb <= 0) return hipSuccess;
+	ReadsArgs a{};
+	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.fmt = fmt; a.want_unpaired = want_unpaired;
+	a.bk = (u64 *)bk; a.bt = (u64 *)bt; a.bn = (u64 *)bn;
+	a.krec = (u64 *)krec; a.ktoff = (u64 *)ktoff; a.knoff = (u64 *)knoff; a.kkey = (u64 *)kkey; a.kkind = kkind;
+	bam_reads_index_kernel<<<(unsigned)((nb + kReadsWaves - 1) / kReadsWaves), kReadsWaves * 64, 0, st>>>(a);
+	return hipGetLastError();
+}
+
+hipError_t launch_bam_reads_windows(const uint64_t *ktoff, const uint64_t *knoff, int64_t n, uint64_t W, uint64_t total_t, uint64_t total_n,
+                                    uint64_t *ws, uint64_t *wt, uint64_t *wn, int64_t nw, hipStream_t st)
+{
+	if (n <= 0) return hipSuccess;
+	bam_reads_window_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((const u64 *)ktoff, (const u64 *)knoff, n, W, total_t, total_n,
+	                                                                      (u64 *)ws, (u64 *)wt, (u64 *)wn, nw);
+	return hipGetLastError();
+}
+
+hipError_t launch_bam_reads_text(const uint8_t *stream, const uint64_t *krec, const uint64_t *ktoff, const uint64_t *knoff, int64_t first, int64_t n,
+                                 uint64_t t0, uint64_t n0, int fmt, uint8_t min_baseq, uint8_t *text, uint64_t *toff, uint8_t *names, uint32_t *noff,
+                                 int n_cu, hipStream_t st)
+{
+	if (n <= 0) return hipSuccess;
+	ReadsText a;
+	a.stream = stream; a.krec = (const u64 *)krec; a.ktoff = (const u64 *)ktoff; a.knoff = (const u64 *)knoff; a.first = first; a.n = n;
+	a.t0 = t0; a.n0 = n0; a.fmt = fmt; a.min_baseq = min_baseq; a.text = text; a.toff = (u64 *)toff; a.names = names; a.noff = noff;
+	int64_t grid = (n + kTextThreads / 16 - 1) / (kTextThreads / 16);
+	const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 256) * 16;
+	if (grid > cap) grid = cap;
+	bam_reads_text_kernel<<<(unsigned)grid, kTextThreads, 0, st>>>(a);
+	return hipGetLastError();
+}
+}  // namespace sk

@@ -166,6 +166,18 @@ hipError_t launch_bam_walk_reduce(const uint8_t *stream, uint64_t stream_len, co
 hipError_t launch_bam_gather(const uint8_t *stream, uint64_t stream_len, const uint64_t *bend, const uint64_t *entry, const uint64_t *rec_base, int64_t n,
                              uint16_t *flag, uint8_t *mapq, int32_t *tid, int32_t *mtid, int32_t *pos, int32_t *mpos, int32_t *tlen, int32_t *end_pos,
                              hipStream_t st);
+// sam to raw|fasta|fastq over a verified stream (sk_bamtext.hip): the sizing pass + the scans of its per-block sums, the kept records'
+// columns, the windows, and one window's text
+hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
+                                 uint64_t *bk, uint64_t *bt, uint64_t *bn, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_reads_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
+                                  const uint64_t *bk, const uint64_t *bt, const uint64_t *bn, uint64_t *krec, uint64_t *ktoff, uint64_t *knoff,
+                                  uint64_t *kkey, uint8_t *kkind, hipStream_t st);
+hipError_t launch_bam_reads_windows(const uint64_t *ktoff, const uint64_t *knoff, int64_t n, uint64_t W, uint64_t total_t, uint64_t total_n,
+                                    uint64_t *ws, uint64_t *wt, uint64_t *wn, int64_t nw, hipStream_t st);
+hipError_t launch_bam_reads_text(const uint8_t *stream, const uint64_t *krec, const uint64_t *ktoff, const uint64_t *knoff, int64_t first, int64_t n,
+                                 uint64_t t0, uint64_t n0, int fmt, uint8_t min_baseq, uint8_t *text, uint64_t *toff, uint8_t *names, uint32_t *noff,
+                                 int n_cu, hipStream_t st);
 
 // ---- BGZF deflate on the device (sk_deflate.hip) ----
 // blocks: device array of sk_deflate_block; out: n_blocks slots of out_stride bytes (a block's payload from the slot's first byte on);

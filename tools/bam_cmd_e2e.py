@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""`sam fragments`, `sam count` and `sam count --single-end --center` from a BAM FILE: the device path (sk_bam_file_columns and the
-kernels behind it) against the host reader (SEQKIT_HOST_INFLATE=1), alternating, several runs each: wall time and CPU-seconds of
-every run, outputs of both paths and of the oracle command line checked identical.  Then sk_bam_file_columns' library-call time next
+"""`sam fragments`, `sam count`, `sam count --single-end --center`, `sam to interleaved fastq` and `sam to fastq <prefix>` from a BAM
+FILE: the device path (sk_bam_file_columns / sk_bam_file_reads and the kernels behind them) against the host reader (SEQKIT_HOST_INFLATE=1), alternating, several runs each: wall time and CPU-seconds of
+every run, outputs of both paths and of the oracle command line checked identical (the .gz files of `sam to fastq` decompressed).  Then sk_bam_file_columns' library-call time next
 to sk_bam_file_reduce's on the same file in one process.
 
 The fragments file is tools/bam_e2e.py's (100 k paired records, one in two kept, repeated); the count file is the same unit once per
 reference, with tid = the repeat's index, so it is coordinate-sorted with positions restarting per reference; the BED file holds
 about 20 k regions over those references.  usage: bam_cmd_e2e.py [million records (20)] [runs per path (3)] [--lib-only: the library
-calls alone, e.g. under rocprofv3 --kernel-trace --stats]"""
+calls alone, e.g. under rocprofv3 --kernel-trace --stats] [--no-gz: without the `sam to fastq <prefix>` row]
+
+The `sam to interleaved fastq` row is also run with stdout to /dev/null (no oracle there: the row before checked the outputs), which
+takes the writer's cost out of both paths."""
 import os
 import struct
 import subprocess
@@ -28,7 +31,8 @@ orc.build()
 build.build_all()
 SAM = os.path.join(build.BINDIR, "sam")
 lib_only = "--lib-only" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--lib-only"]
+no_gz = "--no-gz" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--lib-only", "--no-gz")]
 millions = int(argv[0]) if len(argv) > 0 else 20
 runs = int(argv[1]) if len(argv) > 1 else 3
 PAIRS = 50_000
@@ -94,21 +98,68 @@ def with_tid(t):
     return blocks_of(u.tobytes())
 
 
-def timed(args, env=None):
-    """one run: (wall s, CPU s of the child, rc, sha256 of stdout, stderr)"""
+def timed(args, env=None, sink=None):
+    """one run: (wall s, CPU s of the child, rc, sha256 of stdout, stderr); sink: where stdout goes instead (not hashed)"""
     e = dict(os.environ)
     e.pop("SEQKIT_HOST_INFLATE", None)
     if env:
         e.update(env)
-    with open(out, "wb") as fo:
+    with open(sink or out, "wb") as fo:
         t0 = time.perf_counter()
         p = subprocess.Popen(args, stdout=fo, stderr=subprocess.PIPE, env=e)
         err = p.stderr.read()
         _, status, ru = os.wait4(p.pid, 0)
         dt = time.perf_counter() - t0
     p.returncode = os.waitstatus_to_exitcode(status)
-    h = sha256(open(out, "rb").read()).hexdigest()[:16]
+    h = sha256(open(out, "rb").read()).hexdigest()[:16] if not sink else None
     return dt, ru.ru_utime + ru.ru_stime, p.returncode, h, err
+
+
+def gz_digest(prefix):
+    """sha256 of the decompressed .gz files that begin with prefix (sorted by name)"""
+    h = sha256()
+    for f in sorted(os.listdir(d)):
+        if f.startswith(os.path.basename(prefix)) and f.endswith(".gz"):
+            zc = subprocess.run(["gzip", "-dc", os.path.join(d, f)], stdout=subprocess.PIPE, check=True).stdout
+            h.update(f.encode() + sha256(zc).digest())
+            os.remove(os.path.join(d, f))
+    return h.hexdigest()[:16]
+
+
+def compare_to(label, args, prefix=None, sink=None):
+    """compare() for `sam to`: with a prefix, the decompressed .gz files are the output (checked on the first run of each path); with
+    a sink (/dev/null), the times alone"""
+    rows = {"device": [], "host": []}
+    seen = set()
+    for k in range(runs):
+        for path, env in (("device", None), ("host", {"SEQKIT_HOST_INFLATE": "1"})):
+            dt, cpu, rc, h, err = timed([SAM] + args, env, sink)
+            rows[path].append((dt, cpu))
+            if sink:
+                h = None
+            elif prefix:
+                h = gz_digest(prefix) if k == 0 else None
+            if h is not None:
+                seen.add((rc, h, err))
+    if sink:
+        dt = cpu = float("nan")
+        seen.add((0, "not compared", b""))
+    else:
+        dt, cpu, rc, h, err = timed([orc.SAM_BIN] + args)
+        seen.add((rc, gz_digest(prefix) if prefix else h, err))
+    assert len(seen) == 1, f"{label}: outputs differ: {seen}"
+    tr = subprocess.run([SAM] + args, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, env=dict(os.environ, SK_BAMFILE_TRACE="1")).stderr
+    if prefix:
+        gz_digest(prefix)
+    served = [ln for ln in tr.decode(errors="replace").split("\n") if ln.startswith("sam ")]
+    for path in ("device", "host"):
+        w = [r[0] for r in rows[path]]
+        c = [r[1] for r in rows[path]]
+        print(f"{label:34s} {path:6s} wall {min(w):6.2f} s (median {float(np.median(w)):6.2f})  CPU {float(np.median(c)):6.2f} s   "
+              + " ".join(f"{x:.2f}" for x in w), flush=True)
+    print(f"{label:34s} oracle wall {dt:6.2f} s  CPU {cpu:6.2f} s; outputs identical (rc {rc}, output sha256 {next(iter(seen))[1]}); trace: {served}", flush=True)
+    dev, host = float(np.median([r[0] for r in rows['device']])), float(np.median([r[0] for r in rows['host']]))
+    print(f"{label:34s} device / host wall (medians) = {dev / host:.2f}", flush=True)
 
 
 def compare(label, args):
@@ -145,6 +196,10 @@ with open(bam, "wb") as f:
 print(f"fragments file: {n} BAM records, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; {runs} runs per path", flush=True)
 if not lib_only:
     compare("sam fragments", ["fragments", bam])
+    compare_to("sam to interleaved fastq", ["to", "interleaved", "fastq", bam])
+    compare_to("sam to interleaved fastq >/dev/null", ["to", "interleaved", "fastq", bam], sink=os.devnull)
+    if not no_gz:
+        compare_to("sam to fastq <prefix>", ["to", "fastq", bam, os.path.join(d, "o")], prefix=os.path.join(d, "o"))
 
 # the library calls on the same file, one process
 import seqkit_amd  # noqa: E402
@@ -164,6 +219,21 @@ with seqkit_amd.Context(0) as ctx:
     print(f"library call, {n} records: sk_bam_file_reduce {1e3 * min(tr_):.0f} ms (median {1e3 * float(np.median(tr_)):.0f}), "
           f"sk_bam_file_columns (all 8 fields) {1e3 * min(tc):.0f} ms (median {1e3 * float(np.median(tc)):.0f}): "
           f"columns / reduce = {float(np.median(tc)) / float(np.median(tr_)):.2f}", flush=True)
+    # sk_bam_file_reads (fastq) and its windows, the text left in the page-locked buffers: the device side of `sam to fastq`
+    t0 = time.perf_counter()
+    h, kept, tb, _ = ctx.bam_file_reads(bam, "fastq")
+    t1 = time.perf_counter()
+    w = capi._ReadsWindow()
+    nw = 0
+    while True:
+        ctx._check(ctx._lib.sk_bam_file_reads_next(ctx._h, capi.C.byref(w)), "sk_bam_file_reads_next")
+        if w.n == 0:
+            break
+        nw += 1
+    t2 = time.perf_counter()
+    assert h
+    print(f"library call, {n} records: sk_bam_file_reads (fastq) {1e3 * (t1 - t0):.0f} ms, {kept} kept, {tb / 1e9:.2f} GB of text; "
+          f"{nw} windows drained in {1e3 * (t2 - t1):.0f} ms", flush=True)
 os.remove(bam)
 if lib_only:
     os.rmdir(d)
