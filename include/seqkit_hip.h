@@ -399,6 +399,40 @@ int sk_bam_file_reads(sk_ctx *ctx, const char *path, int format /* 0 raw, 1 fast
                       int *handled, double info[8]);
 int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
 
+/* ---- BAM out for `sam trim qnames`, `sam tags from qname`, `sam qname from tags` (src/sam_trim_qnames.rs:20-30,
+ * src/sam_tags_from_qname.rs:33-52, src/sam_qname_from_tags.rs:32-41) ------------------------------------------------------
+ * sk_bam_file_rewrite: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0
+ * cases, info[] as there), then a device pass that rewrites every record and BGZF-compresses the result where it lies.  "qname" is the
+ * read name without its final NUL.  op SK_REWRITE_TRIM_QNAMES: a name with a space at index t becomes qname[..t], or qname[..t - 2]
+ * when "/1" or "/2" precedes the space.  SK_REWRITE_TAGS_FROM_QNAME: the name is split on every ' ', the first part stays the name,
+ * each further part "UMI:v" appends RX:Z:v and "XY:v" appends XY:Z:v at the end of the aux data.  SK_REWRITE_QNAME_FROM_TAGS: when
+ * the first RX field has type Z or H, the name becomes qname + " RX:" + its value (the field stays).  A changed record gets
+ * l_read_name = its name + 1 and block_size to match, every other byte as it was; the other records pass byte for byte.  The header:
+ * the text up to its first NUL with trailing '\n's stripped and one '\n' appended when not empty, the reference list as read (htslib's
+ * Header::from_template would rebuild that list from the @SQ lines; this keeps the binary list).
+ * *handled = 0 also, decided before any window exists, when a record would end the reference's loop (trim: a space at index 0 or 1;
+ * tags from qname: a part that is neither "UMI:.." nor "XY:.."; qname from tags: a new name of more than 254 bytes, or aux data that
+ * do not parse to the record's end), when a record's variable part is shorter than its fields, and when the device or page-locked
+ * memory the call needs cannot be had.  A bad op or level: SK_ERR_INVALID.  level 0: every member is a stored block; 1: deflated on
+ * the device (a block that does not shrink is stored).  window_bytes (0: 64 MiB) bounds the rewritten bytes of one window (a single
+ * record may go beyond it).  *n_records: the records; *raw_bytes: the whole output BAM, inflated.
+ * sk_bam_file_rewrite_next: the next window, in file order: first the header's members (n == 0, bytes > 0), then the records', the
+ * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
+ * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
+ * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
+ * sk_bam_file_rewrite: SK_ERR_INVALID.                                                                                          */
+#define SK_REWRITE_TRIM_QNAMES     1
+#define SK_REWRITE_QNAME_FROM_TAGS 2
+#define SK_REWRITE_TAGS_FROM_QNAME 3
+typedef struct sk_bam_out_window {
+	int64_t first, n;          /* records first .. first + n - 1; n == 0 && bytes == 0: the end */
+	const uint8_t *bgzf;       /* HOST, page-locked: complete BGZF members back to back */
+	uint64_t bytes, raw_bytes; /* compressed bytes; the BAM bytes they inflate to */
+} sk_bam_out_window;
+int sk_bam_file_rewrite(sk_ctx *ctx, const char *path, int op, int level /* 0 stored, 1 deflate */, uint64_t window_bytes /* 0 = default */,
+                        int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
+int sk_bam_file_rewrite_next(sk_ctx *ctx, sk_bam_out_window *w);
+
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is
  * the decompressed stream.  sk_bgzf_deflate compresses n independent blocks of at most SK_DEFLATE_MAX_IN bytes (in +

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
     "sk_timer_start", "sk_timer_stop",
@@ -77,6 +77,14 @@ class _ReadsWindow(C.Structure):
 
 # sk_bam_file_reads: output formats
 READS_FORMAT = {"raw": 0, "fasta": 1, "fastq": 2}
+
+
+class _OutWindow(C.Structure):
+    _fields_ = [("first", C.c_int64), ("n", C.c_int64), ("bgzf", C.c_void_p), ("bytes", C.c_uint64), ("raw_bytes", C.c_uint64)]
+
+
+# sk_bam_file_rewrite: the commands
+REWRITE_OP = {"trim qnames": 1, "qname from tags": 2, "tags from qname": 3}
 
 
 class _Mate(C.Structure):
@@ -230,6 +238,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_walk_reduce_dev": (i32, [vp, vp, C.c_uint64, vp, vp, i64, i32, i32, i32, vp]),
         "sk_bam_file_reduce": (i32, [vp, C.c_char_p, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_columns": (i32, [vp, C.c_char_p, C.c_uint32, C.POINTER(_BamColumns), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_rewrite": (i32, [vp, C.c_char_p, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_rewrite_next": (i32, [vp, C.POINTER(_OutWindow)]),
         "sk_bam_file_reads": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
         "sk_bam_fragments_bed_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(i64)]),
@@ -433,6 +443,25 @@ class Context:
             yield {"first": int(w.first), "n": n, "text": C.string_at(w.text, int(text_off[-1])) if text_off[-1] else b"", "text_off": text_off,
                    "kind": arr(w.kind, n, np.uint8), "key": arr(w.key, n, np.uint64),
                    "names": C.string_at(w.names, int(name_off[-1])) if name_off[-1] else b"", "name_off": name_off}
+
+    def bam_file_rewrite(self, path: str, op, level: int = 1, window_bytes: int = 0):
+        """sk_bam_file_rewrite: (handled, records, inflated output bytes, info f64[8]); then bam_file_rewrite_windows() yields the windows.
+        op: a REWRITE_OP key or its number."""
+        n_rec, raw_bytes, handled = C.c_int64(0), C.c_uint64(0), C.c_int32(0)
+        info = (C.c_double * 8)()
+        o = REWRITE_OP[op] if isinstance(op, str) else int(op)
+        self._check(self._lib.sk_bam_file_rewrite(self._h, os.fsencode(path), o, level, window_bytes, C.byref(n_rec), C.byref(raw_bytes),
+                                                  C.byref(handled), info), "sk_bam_file_rewrite")
+        return bool(handled.value), int(n_rec.value), int(raw_bytes.value), [float(x) for x in info]
+
+    def bam_file_rewrite_windows(self):
+        """sk_bam_file_rewrite_next until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""
+        while True:
+            w = _OutWindow()
+            self._check(self._lib.sk_bam_file_rewrite_next(self._h, C.byref(w)), "sk_bam_file_rewrite_next")
+            if w.n == 0 and w.bytes == 0:
+                return
+            yield {"first": int(w.first), "n": int(w.n), "bgzf": C.string_at(w.bgzf, int(w.bytes)), "raw_bytes": int(w.raw_bytes)}
 
     def bam_fragments_bed_dev(self, keep_bits: int, tid: int, pos: int, tlen: int, n: int, names):
         """sk_bam_fragments_bed_dev over device columns: (BED text bytes, index of the first kept record with a bad tid or -1).

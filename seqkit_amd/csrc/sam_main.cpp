@@ -17,6 +17,7 @@
 // window, and the mate pairing stays here.
 #include <unistd.h>
 #include <malloc.h>
+#include <zlib.h>
 #include <fcntl.h>
 
 #include <algorithm>
@@ -56,26 +57,41 @@ struct BamCore { int32_t tid, pos; uint16_t flag; int32_t mtid, mpos, tlen, end_
 
 class BamStream {
 public:
-	explicit BamStream(const std::string &path) : path_(path)
+	// keep_header: the header's bytes as read ("BAM\1" .. the end of the reference list) stay in header_raw
+	explicit BamStream(const std::string &path, bool keep_header = false) : path_(path)
 	{
 		int fd = 0;
 		if (path != "-") fd = open(path.c_str(), O_RDONLY);
 		if (fd < 0) error("Cannot open BAM file '%s'", path.c_str());
 		bz_.reset(new host::BgzfStream(fd, true));
 		uint8_t h[8];
+		auto keep = [&](const uint8_t *p, size_t n) { if (keep_header) header_raw.insert(header_raw.end(), p, p + n); };
 		if (!get(h, 8) || memcmp(h, "BAM\1", 4) != 0) open_fail();
-		if (!skip(le32(h + 4))) open_fail();
+		keep(h, 8);
+		if (keep_header) {
+			const uint32_t l_text = le32(h + 4);
+			for (uint32_t done = 0; done < l_text;) {                 // (in steps: a damaged l_text runs into the end of the data first)
+				const uint32_t step = std::min<uint32_t>(l_text - done, 16u << 20);
+				header_raw.resize(header_raw.size() + step);
+				if (!get(header_raw.data() + header_raw.size() - step, step)) open_fail();
+				done += step;
+			}
+		} else if (!skip(le32(h + 4))) open_fail();
 		if (!get(h, 4)) open_fail();
+		keep(h, 4);
 		const uint32_t n_ref = le32(h);
 		for (uint32_t i = 0; i < n_ref; i++) {
 			if (!get(h, 4)) open_fail();
+			keep(h, 4);
 			const uint32_t l_name = le32(h);
 			if (l_name > (1u << 20)) open_fail();               // a reference name of megabytes is a damaged header, not an allocation to attempt
 			std::string name(l_name, '\0');
 			if (l_name && !get(reinterpret_cast<uint8_t *>(&name[0]), l_name)) open_fail();
+			keep(reinterpret_cast<const uint8_t *>(name.data()), l_name);
 			if (!name.empty() && name.back() == '\0') name.pop_back();
 			names.push_back(name);
 			if (!get(h, 4)) open_fail();
+			keep(h, 4);
 		}
 	}
 	// Record errors ("BAM file ended prematurely." / "Invalid BAM record.", src/common.rs:150-154) end the stream: next()
@@ -158,6 +174,7 @@ public:
 		const uint32_t block_size = le32(hc);
 		if (block_size < 32) return rd_fail("Invalid BAM record.");
 		if (r < 36 && !need(hc + r, (size_t)(36 - r))) return false;
+		memcpy(head, hc, 36);
 		const uint8_t *core = hc + 4;
 		c.tid = (int32_t)le32(core + 0);
 		c.pos = (int32_t)le32(core + 4);
@@ -186,6 +203,8 @@ public:
 		return true;
 	}
 	std::vector<std::string> names;
+	std::vector<uint8_t> header_raw;
+	uint8_t head[36];                                         // next_full: the record's block_size and core as read
 private:
 	[[noreturn]] void open_fail() { error("Cannot open BAM file '%s'", path_.c_str()); }
 	static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -1042,6 +1061,248 @@ static int to_reads(int argc, char **argv)
 	return 0;
 }
 
+// ---- sam trim qnames / tags from qname / qname from tags ------------------------------------------------------------
+// src/sam_trim_qnames.rs, src/sam_tags_from_qname.rs, src/sam_qname_from_tags.rs: every record is read, its name (and for tags from
+// qname its aux data) rewritten, and written to stdout as BAM (Header::from_template + Writer::from_stdout).  A regular file goes to the
+// device whole (sk_bam_file_rewrite): it rewrites and compresses every window, and this host writes the members as they arrive.
+// Stdin, SEQKIT_HOST_INFLATE=1 and every file the device declines — among them each one with a record the reference would stop at —
+// are read record by record below and written through BamOut, which reproduces the reference's messages, statuses and partial output.
+static const char *USAGE_TRIM = "\nUsage:\n  sam trim qnames [options] <bam_file>\n";
+static const char *USAGE_TAGS_FROM_QNAME =
+	"\nUsage:\n  sam tags from qname [options] <bam_file>\n\nOptions:\n  --uncompressed     Output in uncompressed BAM format\n\n"
+	"Finds tags (e.g. \"UMI:xxxx\") in the qname of each BAM record, and turns\nthem into actual SAM format tags.\n";
+static const char *USAGE_QNAME_FROM_TAGS =
+	"\nUsage:\n  sam qname from tags [options] <bam_file>\n\nOptions:\n  --uncompressed     Output in uncompressed BAM format\n\n"
+	"Finds tags (e.g. \"RX:xxxx\") in each BAM record, and appends them to the QNAME.\n";
+
+// A BAM file on stdout: raw BAM bytes are cut into blocks of 0xff00 bytes and written as BGZF members, deflated on the device
+// (sk_bgzf_deflate) or, at level 0, stored; finish() writes what is left and the EOF block.  The header goes in members of its own.
+class BamOut {
+public:
+	explicit BamOut(int level) : level_(level) { buf_.reserve(kBatch + 8); }
+	void put(const uint8_t *p, size_t n)
+	{
+		buf_.insert(buf_.end(), p, p + n);
+		if (buf_.size() >= kBatch) flush();
+	}
+	void flush()
+	{
+		if (buf_.empty()) return;
+		const size_t n = buf_.size(), nblk = (n + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN;
+		buf_.resize(n + 8, 0);                                       // (the device reads whole dwords)
+		std::vector<sk_deflate_block> blocks(nblk);
+		for (size_t i = 0; i < nblk; i++) { blocks[i].in_off = i * SK_DEFLATE_MAX_IN; blocks[i].in_len = (uint32_t)std::min<size_t>(SK_DEFLATE_MAX_IN, n - i * SK_DEFLATE_MAX_IN); blocks[i].reserved = 0; }
+		std::vector<uint64_t> off(nblk + 1);
+		if (level_) {
+			comp_.resize(nblk * SK_DEFLATE_MAX_MEMBER);
+			check(sk_bgzf_deflate(host::gpu(), buf_.data(), n, blocks.data(), (int64_t)nblk, comp_.data(), comp_.size(), off.data()), "sk_bgzf_deflate");
+		} else {
+			comp_.resize(nblk * (SK_DEFLATE_MAX_IN + 31));
+			size_t at = 0;
+			static const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+			for (size_t i = 0; i < nblk; i++) {
+				const uint32_t len = blocks[i].in_len, bsize = len + 31;
+				uint8_t *m = comp_.data() + at;
+				memcpy(m, head, 16);
+				m[16] = (uint8_t)((bsize - 1) & 0xff); m[17] = (uint8_t)((bsize - 1) >> 8);
+				m[18] = 1; m[19] = (uint8_t)(len & 0xff); m[20] = (uint8_t)(len >> 8); m[21] = (uint8_t)(~len & 0xff); m[22] = (uint8_t)((~len >> 8) & 0xff);
+				memcpy(m + 23, buf_.data() + blocks[i].in_off, len);
+				const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), buf_.data() + blocks[i].in_off, len);
+				for (int k = 0; k < 4; k++) { m[23 + len + k] = (uint8_t)(crc >> (8 * k)); m[27 + len + k] = (uint8_t)(len >> (8 * k)); }
+				at += bsize;
+			}
+			off[nblk] = at;
+		}
+		write_all(comp_.data(), (size_t)off[nblk]);
+		buf_.clear();
+	}
+	void finish()
+	{
+		if (done_) return;
+		done_ = true;
+		flush();
+		static const uint8_t eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		write_all(eof, 28);
+	}
+	static void write_all(const uint8_t *p, size_t n)
+	{
+		while (n) {
+			const ssize_t w = ::write(1, p, n);
+			if (w <= 0) error("Output stream closed unexpectedly.");
+			p += w; n -= (size_t)w;
+		}
+	}
+private:
+	static constexpr size_t kBatch = (size_t)256 * SK_DEFLATE_MAX_IN;
+	int level_;
+	bool done_ = false;
+	std::vector<uint8_t> buf_, comp_;
+};
+
+// Header::from_template: the text up to its first NUL, trailing '\n's stripped, one '\n' appended when anything is left; the reference
+// list as read (htslib would rebuild it from the @SQ lines: DESIGN.md §10)
+static std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h)
+{
+	auto le32 = [&](size_t o) { return (uint32_t)h[o] | ((uint32_t)h[o + 1] << 8) | ((uint32_t)h[o + 2] << 16) | ((uint32_t)h[o + 3] << 24); };
+	const uint32_t l_text = le32(4);
+	size_t n = 0;
+	while (n < l_text && h[8 + n] != 0) n++;
+	while (n > 0 && h[8 + n - 1] == '\n') n--;
+	const uint32_t l_new = n ? (uint32_t)n + 1 : 0;
+	std::vector<uint8_t> o(h.begin(), h.begin() + 4);
+	for (int k = 0; k < 4; k++) o.push_back((uint8_t)(l_new >> (8 * k)));
+	o.insert(o.end(), h.begin() + 8, h.begin() + 8 + (ptrdiff_t)n);
+	if (n) o.push_back('\n');
+	o.insert(o.end(), h.begin() + 8 + (ptrdiff_t)l_text, h.end());
+	return o;
+}
+
+static BamOut *g_bam_out = nullptr;
+static void finish_bam_out() { if (g_bam_out) g_bam_out->finish(); }    // a panic unwinds through the Writer's drop: what was written stays valid BAM
+
+// The first RX field's value when its type is Z or H (bam_aux_get: the walk stops, not finding it, where the aux data stop parsing)
+static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
+{
+	size_t o = 0;
+	while (o + 3 <= n) {
+		const uint8_t t0 = a[o], t1 = a[o + 1], ty = a[o + 2];
+		size_t v = o + 3, e;
+		if (ty == 'A' || ty == 'c' || ty == 'C') e = v + 1;
+		else if (ty == 's' || ty == 'S') e = v + 2;
+		else if (ty == 'i' || ty == 'I' || ty == 'f') e = v + 4;
+		else if (ty == 'Z' || ty == 'H') {
+			const void *z = v < n ? memchr(a + v, 0, n - v) : nullptr;
+			if (!z) return false;
+			e = (size_t)((const uint8_t *)z - a) + 1;
+		} else if (ty == 'B') {
+			if (v + 5 > n) return false;
+			const uint8_t sub = a[v];
+			const uint32_t cnt = (uint32_t)a[v + 1] | ((uint32_t)a[v + 2] << 8) | ((uint32_t)a[v + 3] << 16) | ((uint32_t)a[v + 4] << 24);
+			const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+			if (!es) return false;
+			e = v + 5 + (size_t)cnt * es;
+		} else return false;
+		if (e > n) return false;
+		if (t0 == 'R' && t1 == 'X') {
+			if (ty != 'Z' && ty != 'H') return false;
+			val = a + v; vl = e - v - 1;
+			return true;
+		}
+		o = e;
+	}
+	return false;
+}
+
+static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usage, bool has_uncompressed)
+{
+	std::vector<host::Opt> opts;
+	if (has_uncompressed) opts.push_back({"--uncompressed", false, false, ""});
+	std::vector<std::string> pos;
+	if (!host::parse_args(argc, argv, first, opts, pos, 1) || pos.size() != 1) error("Invalid arguments.\n%s", usage);
+	const std::string path = expand_home(pos[0]);
+	const int level = has_uncompressed && opts[0].present ? 0 : 1;
+	const char *who = op == SK_REWRITE_TRIM_QNAMES ? "sam trim qnames" : op == SK_REWRITE_TAGS_FROM_QNAME ? "sam tags from qname" : "sam qname from tags";
+	host::gpu_warmup();
+	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
+	if (file_path_wanted(path)) {
+		sk_ctx *c = host::gpu();
+		static const uint64_t window = [] { const char *ev = getenv("SK_BAMFILE_WINDOW"); return ev ? (uint64_t)strtoull(ev, nullptr, 10) : (uint64_t)0; }();
+		int64_t n_rec = 0;
+		uint64_t raw = 0;
+		int handled = 0;
+		if (sk_bam_file_rewrite(c, path.c_str(), op, level, window, &n_rec, &raw, &handled, nullptr) == SK_OK && handled) {
+			sk_bam_out_window w;
+			for (;;) {
+				check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
+				if (w.n == 0 && w.bytes == 0) break;
+				BamOut::write_all(w.bgzf, (size_t)w.bytes);
+			}
+			if (trace) fprintf(stderr, "%s: device path, %lld records\n", who, (long long)n_rec);
+			return 0;
+		}
+	}
+	if (trace) fprintf(stderr, "%s: host reader\n", who);
+	BamStream bam(path, true);
+	BamOut out(level);
+	g_bam_out = &out;
+	host::at_exit_flush(finish_bam_out);
+	const std::vector<uint8_t> hdr = rewrite_header(bam.header_raw);
+	out.put(hdr.data(), hdr.size());
+	out.flush();                                                                // (the header in members of its own)
+	BamCore c;
+	BamStream::Var v;
+	std::vector<uint8_t> body, rec, app;
+	std::string name;
+	while (bam.next_full(c, v, body)) {
+		const size_t L = v.l_read_name - 1;
+		const uint8_t *nm = body.data();
+		const uint8_t *sp = static_cast<const uint8_t *>(op != SK_REWRITE_QNAME_FROM_TAGS ? memchr(nm, ' ', L) : nullptr);
+		bool changed = false;
+		app.clear();
+		if (op == SK_REWRITE_TRIM_QNAMES && sp) {                                   // src/sam_trim_qnames.rs:20-26
+			size_t t = (size_t)(sp - nm);
+			if (t < 2) panic("index out of bounds: qname[trim - 2]");
+			if (nm[t - 2] == '/' && (nm[t - 1] == '1' || nm[t - 1] == '2')) t -= 2;
+			name.assign(reinterpret_cast<const char *>(nm), t);
+			changed = true;
+		} else if (op == SK_REWRITE_TAGS_FROM_QNAME && sp) {                        // src/sam_tags_from_qname.rs:33-48
+			const size_t t = (size_t)(sp - nm);
+			name.assign(reinterpret_cast<const char *>(nm), t);
+			for (size_t s0 = t + 1;;) {
+				size_t e = s0;
+				while (e < L && nm[e] != ' ') e++;
+				const uint8_t *pt = nm + s0;
+				const size_t m = e - s0;
+				if (m >= 4 && memcmp(pt, "UMI:", 4) == 0) {
+					app.insert(app.end(), {'R', 'X', 'Z'});
+					app.insert(app.end(), pt + 4, pt + m);
+					app.push_back(0);
+				} else if (m >= 3 && pt[2] == ':') {
+					app.insert(app.end(), {pt[0], pt[1], 'Z'});
+					app.insert(app.end(), pt + 3, pt + m);
+					app.push_back(0);
+				} else {
+					if (!host::utf8_valid(pt, m)) panic("called `Result::unwrap()` on an `Err` value: Utf8Error");
+					error("Tag '%.*s' is not supported.", (int)m, reinterpret_cast<const char *>(pt));
+				}
+				if (e >= L) break;
+				s0 = e + 1;
+			}
+			changed = true;
+		} else if (op == SK_REWRITE_QNAME_FROM_TAGS) {                               // src/sam_qname_from_tags.rs:32-38
+			const size_t aux = (size_t)v.l_read_name + 4 * (size_t)v.n_cigar + (((size_t)v.l_seq + 1) >> 1) + v.l_seq;
+			const uint8_t *val = nullptr;
+			size_t vl = 0;
+			if (find_rx(body.data() + aux, body.size() - aux, val, vl)) {
+				name.assign(reinterpret_cast<const char *>(nm), L);
+				name += " RX:";
+				name.append(reinterpret_cast<const char *>(val), vl);
+				if (name.size() > 254) panic("assertion failed: new_qname.len() < 255");
+				changed = true;
+			}
+		}
+		if (!changed) {
+			out.put(bam.head, 36);
+			out.put(body.data(), body.size());
+			continue;
+		}
+		const size_t tail = body.size() - v.l_read_name;
+		const uint32_t bs = (uint32_t)(32 + name.size() + 1 + tail + app.size());
+		rec.assign(bam.head, bam.head + 36);
+		for (int k = 0; k < 4; k++) rec[k] = (uint8_t)(bs >> (8 * k));
+		rec[12] = (uint8_t)(name.size() + 1);
+		rec.insert(rec.end(), name.begin(), name.end());
+		rec.push_back(0);
+		rec.insert(rec.end(), body.begin() + v.l_read_name, body.end());
+		rec.insert(rec.end(), app.begin(), app.end());
+		out.put(rec.data(), rec.size());
+	}
+	bam.raise_deferred();
+	out.finish();
+	g_bam_out = nullptr;
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	// blocks, per-sample strings and gzip jobs are hundreds of KiB each: above glibc's default mmap threshold every one of them was a
@@ -1060,6 +1321,9 @@ int main(int argc, char **argv)
 	else if (argc >= 3 && is(1, "fragment") && is(2, "lengths")) rc = fragment_lengths(argc, argv);
 	else if (argc >= 3 && is(1, "to") && (is(2, "raw") || is(2, "fasta") || is(2, "fastq"))) rc = to_reads(argc, argv);
 	else if (argc >= 4 && is(1, "to") && is(2, "interleaved") && (is(3, "raw") || is(3, "fasta") || is(3, "fastq"))) rc = to_reads(argc, argv);
+	else if (argc >= 4 && is(1, "tags") && is(2, "from") && is(3, "qname")) rc = rewrite_cmd(argc, argv, SK_REWRITE_TAGS_FROM_QNAME, 4, USAGE_TAGS_FROM_QNAME, true);
+	else if (argc >= 4 && is(1, "qname") && is(2, "from") && is(3, "tags")) rc = rewrite_cmd(argc, argv, SK_REWRITE_QNAME_FROM_TAGS, 4, USAGE_QNAME_FROM_TAGS, true);
+	else if (argc >= 3 && is(1, "trim") && is(2, "qnames")) rc = rewrite_cmd(argc, argv, SK_REWRITE_TRIM_QNAMES, 3, USAGE_TRIM, false);
 	else fprintf(stderr, "%s\n", USAGE_TOP);
 	host::out().flush();
 	// everything is written and closed: what is left is taking the process apart (static destructors, the HIP runtime's exit handlers,

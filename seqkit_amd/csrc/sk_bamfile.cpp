@@ -188,12 +188,37 @@ struct ReadsState {
 	~ReadsState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// sk_bam_file_rewrite / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot kKeepRwCols), the window
+// plan, one device area for the window being rewritten and compressed (raw bytes, deflate scratch, blocks) and two packed-member
+// buffers on each side (ctx slots kKeepRwWin / kKeepRwPin): one window in flight while the caller writes the other
+struct RewriteState {
+	bool live = false;
+	uint64_t gen = 0;                            // Ranges::gen of the file call that set it up
+	int op = 0, level = 1;
+	const uint8_t *d_out = nullptr;
+	uint64_t *krec = nullptr, *kout = nullptr;
+	std::vector<uint64_t> ws, wo;                // window w: records ws[w] .., output bytes wo[w] .. (up to w + 1)
+	std::vector<uint8_t> header;                 // the output header (the first window)
+	size_t next_w = 0;
+	bool header_done = false;
+	uint8_t *d_raw = nullptr, *d_slots = nullptr, *d_pack[2] = {nullptr, nullptr}, *h_pin[2] = {nullptr, nullptr};
+	uint32_t *d_tokens = nullptr, *d_result = nullptr, *d_crc = nullptr;
+	uint64_t *d_msz = nullptr, *h_size = nullptr;   // h_size[b]: window b's packed bytes (page-locked)
+	void *d_blocks = nullptr;
+	hipEvent_t ev[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+	int64_t first[2] = {0, 0}, n[2] = {0, 0};
+	uint64_t raw[2] = {0, 0};
+	int cur = -1;                                // the buffer whose window is in flight, -1: none (the end)
+	~RewriteState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
+};
+
 // what stays with the ctx: the range of the compressed file and the range of the inflated stream
 struct Ranges {
 	OutRange comp, out;
 	std::vector<uint8_t> header;                 // sk_bam_file_columns: the last file's header bytes (cols->header)
 	uint64_t gen = 0;                            // file calls so far: a reads state of an earlier call is stale
 	ReadsState reads;
+	RewriteState rw;
 	static void destroy(void *p) { Ranges *r = (Ranges *)p; r->comp.release(); r->out.release(); delete r; }
 };
 
@@ -295,10 +320,16 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 	if (!both) { both = new Ranges; sk::ctx_set_ext(c, both, Ranges::destroy); }
 	// an earlier sk_bam_file_reads may have left a window in flight on the ctx stream: its text kernel reads the inflated stream and its
 	// copies write the page-locked window buffers.  It ends before this call remaps the ranges or takes the kept buffers again.
-	if (both->reads.live || both->reads.cur >= 0) BF_HIP(hipStreamSynchronize(sk::ctx_stream(c)));
+	// (the same for an sk_bam_file_rewrite, whose window copies run on the second stream)
+	if (both->reads.live || both->reads.cur >= 0 || both->rw.live || both->rw.cur >= 0) {
+		BF_HIP(hipStreamSynchronize(sk::ctx_stream(c)));
+		BF_HIP(hipStreamSynchronize(sk::ctx_stream2(c)));
+	}
 	both->gen++;                                                        // (what an earlier sk_bam_file_reads left is no longer read)
 	both->reads.live = false;
 	both->reads.cur = -1;
+	both->rw.live = false;
+	both->rw.cur = -1;
 	cl.fd = open(path, O_RDONLY);
 	if (cl.fd < 0) BF_LEAVE(1);                                        // (the caller's reader says so in the reference's words)
 	struct stat sb;
@@ -870,5 +901,201 @@ extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
 	w->first = s.first[b]; w->n = s.n[b];
 	w->text = h; w->text_off = (const uint64_t *)(h + s.at_toff); w->kind = h + s.at_kind; w->key = (const uint64_t *)(h + s.at_key);
 	w->names = h + s.at_names; w->name_off = (const uint32_t *)(h + s.at_noff);
+	return SK_OK;
+}
+
+// ---- sam trim qnames / tags from qname / qname from tags (include/seqkit_hip.h: sk_bam_file_rewrite, sk_bam_file_rewrite_next) ---
+// The front half above, then the sizing pass (per block: rewritten bytes, decline bits) and its scan; the decision to serve the file is
+// taken there, before any window exists.  Then every record's stream and output offsets, the windows, and the header's members on their
+// way.  A window is rewritten into one device buffer, cut into blocks of at most 0xff00 bytes, deflated where it lies and packed into
+// complete members; only the members' bytes are copied back.  Every allocation that fails leaves the file to the caller's reader
+// (info[5] = -21).
+
+static const uint8_t kBgzfEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// Header::from_template + Writer (htslib sam_hdr_write): the text up to its first NUL, trailing '\n's stripped and one appended when
+// anything is left; the reference list as read.  h: "BAM\1" .. the end of the reference list (checked by the front half).
+static std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h)
+{
+	const uint64_t l_text = le32(h.data() + 4);
+	const uint8_t *text = h.data() + 8;
+	uint64_t n = 0;
+	while (n < l_text && text[n] != 0) n++;
+	while (n > 0 && text[n - 1] == '\n') n--;
+	const uint64_t l_new = n ? n + 1 : 0;
+	std::vector<uint8_t> o(h.begin(), h.begin() + 4);
+	for (int k = 0; k < 4; k++) o.push_back((uint8_t)(l_new >> (8 * k)));
+	o.insert(o.end(), text, text + n);
+	if (n) o.push_back('\n');
+	o.insert(o.end(), h.begin() + 8 + (ptrdiff_t)l_text, h.end());
+	return o;
+}
+
+// the header (first) or window w of the plan (the next non-empty one) into packed buffer b: rewrite, cut, deflate, pack, and the packed
+// size back; false: nothing left
+static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
+{
+	*rc = SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	int64_t first = 0, n = 0;
+	uint64_t raw_len = 0;
+	hipError_t e = hipSuccess;
+	if (!s.header_done) {
+		s.header_done = true;
+		raw_len = s.header.size();
+		e = hipMemcpyAsync(s.d_raw, s.header.data(), (size_t)raw_len, hipMemcpyHostToDevice, st);
+	} else {
+		while (s.next_w + 1 < s.ws.size() && s.ws[s.next_w + 1] == s.ws[s.next_w]) s.next_w++;
+		if (s.next_w + 1 >= s.ws.size()) return false;
+		const size_t w = s.next_w++;
+		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
+		raw_len = s.wo[w + 1] - s.wo[w];
+		e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st);
+	}
+	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
+	if (e == hipSuccess) e = hipStreamWaitEvent(st, s.ev_copy[b], 0);                   // (the copy out of this packed buffer)
+	if (e == hipSuccess) e = sk::launch_bgzf_cut(raw_len, s.d_blocks, nblk, st);
+	if (e == hipSuccess) e = s.level ? sk::launch_bgzf_deflate(s.d_raw, s.d_blocks, nblk, s.d_slots, SK_DEFLATE_SLOT, s.d_tokens, s.d_result, s.d_crc, sk::ctx_n_cu(c), st)
+	                                 : sk::launch_bgzf_crc(s.d_raw, s.d_blocks, nblk, s.d_crc, sk::ctx_n_cu(c), st);
+	if (e == hipSuccess) e = sk::launch_bgzf_pack(s.d_raw, s.d_blocks, nblk, s.d_slots, SK_DEFLATE_SLOT, s.d_result, s.d_crc, s.level ? 0 : 1, s.d_msz,
+	                                              s.d_pack[b], sk::ctx_n_cu(c), st);
+	if (e == hipSuccess) e = hipMemcpyAsync(s.h_size + b, s.d_msz + nblk, 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipEventRecord(s.ev[b], st);
+	if (e != hipSuccess) { *rc = sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_rewrite: window at record %lld: %s", (long long)first, hipGetErrorString(e)); return false; }
+	s.first[b] = first; s.n[b] = n; s.raw[b] = raw_len;
+	return true;
+}
+
+extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int level, uint64_t window_bytes, int64_t *n_records, uint64_t *raw_bytes,
+                                   int *handled, double info[8])
+{
+	if (!c || !path || !handled) return SK_ERR_INVALID;
+	*handled = 0;
+	if (n_records) *n_records = 0;
+	if (raw_bytes) *raw_bytes = 0;
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (op < SK_REWRITE_TRIM_QNAMES || op > SK_REWRITE_TAGS_FROM_QNAME) return sk::ctx_fail(c, SK_ERR_INVALID, "op = %d", op);
+	if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+	if (int r = sk::ctx_bind(c)) return r;
+	Cleanup cl;
+	Front fr;
+	if (int r = bam_file_front(c, path, "sk_bam_file_rewrite", cl, fr, info)) return r;
+	if (!fr.ready) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const double t_size = now_ms();
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	// ---- the sizing pass: per block the rewritten bytes (then their exclusive offsets), the decline bits
+	uint64_t *d_blk = nullptr;
+	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 16 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+	cl.dev.push_back(d_blk);
+	uint64_t *bo = d_blk, *d_rb = bo + nb + 1;
+	uint32_t *d_decline = (uint32_t *)(d_rb + nb);
+	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
+	BF_HIP(sk::launch_bam_rw_size(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, d_decline, st));
+	uint64_t total = 0;
+	uint32_t decline = 0;
+	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipStreamSynchronize(st));
+	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_rewrite: declined (bits %#x)\n", decline);
+	if (decline) BF_LEAVE(30 + decline);                                // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
+	// ---- every record's stream and output offsets (ctx slot 9)
+	enum { kKeepRwCols = 9, kKeepRwWin = 10, kKeepRwPin = 11 };
+	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
+	int krc = SK_OK;
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, kKeepRwCols, 2 * up(N * 8 + 8), false, &krc);
+	if (!kb) BF_LEAVE(21);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	RewriteState &s = R->rw;
+	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
+	{
+		std::vector<uint64_t> rb((size_t)nb + 1);
+		uint64_t run = 0;
+		for (int64_t i = 0; i < nb; i++) { rb[(size_t)i] = run; run += fr.nrec[(size_t)i]; }
+		if (run != N) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_rewrite: %llu records by the blocks' counts, %llu by the walk", (unsigned long long)run, (unsigned long long)N);
+		if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+		BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, d_rb, s.krec, s.kout, st));
+		BF_HIP(hipStreamSynchronize(st));                              // (rb is this scope's)
+	}
+	// ---- the windows: at most W rewritten bytes each (one record may go beyond)
+	uint64_t W = window_bytes ? window_bytes : (uint64_t)64 << 20;
+	W = std::min<uint64_t>(std::max<uint64_t>(W, 256), (uint64_t)1 << 30);
+	const int64_t nw = N ? (int64_t)(total / W + 2) : 1;
+	s.ws.assign((size_t)nw, N); s.wo.assign((size_t)nw, total);
+	if (N) {
+		uint64_t *d_w = nullptr;
+		if (hipMalloc((void **)&d_w, (size_t)nw * 16) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+		cl.dev.push_back(d_w);
+		BF_HIP(sk::launch_bam_rw_windows(s.kout, (int64_t)N, W, total, d_w, d_w + nw, nw, st));
+		BF_HIP(hipMemcpyAsync(s.ws.data(), d_w, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipMemcpyAsync(s.wo.data(), d_w + nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	s.header = rewrite_header(fr.header);
+	uint64_t max_raw = s.header.size();
+	for (int64_t w = 0; w + 1 < nw; w++) max_raw = std::max(max_raw, s.wo[(size_t)w + 1] - s.wo[(size_t)w]);
+	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
+	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	const uint64_t pack = max_raw + nblk * 31 + 64;
+	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
+	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, kKeepRwWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
+	if (!dw) BF_LEAVE(21);
+	const size_t p_pack = up(pack + 28);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, kKeepRwPin, 2 * p_pack + 64, true, &krc);
+	if (!hw) BF_LEAVE(21);
+	s.d_raw = dw; s.d_blocks = dw + a_raw; s.d_result = (uint32_t *)(dw + a_raw + a_blk); s.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
+	s.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
+	uint8_t *dp = dw + a_raw + a_blk + a_res + a_crc + a_msz;
+	s.d_pack[0] = dp; s.d_pack[1] = dp + a_pack;
+	s.d_slots = level ? dp + 2 * a_pack : nullptr;
+	s.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
+	s.h_pin[0] = hw; s.h_pin[1] = hw + p_pack; s.h_size = (uint64_t *)(hw + 2 * p_pack);
+	for (int b = 0; b < 2; b++) {
+		if (!s.ev[b] && hipEventCreateWithFlags(&s.ev[b], hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); s.ev[b] = nullptr; BF_LEAVE(21); }
+		if (!s.ev_copy[b] && hipEventCreateWithFlags(&s.ev_copy[b], hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); s.ev_copy[b] = nullptr; BF_LEAVE(21); }
+	}
+	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
+	s.op = op; s.level = level; s.d_out = fr.d_out; s.next_w = 0; s.header_done = false; s.cur = -1;
+	s.gen = R->gen;
+	int rc = SK_OK;
+	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
+	if (rc) return rc;
+	s.live = true;
+	if (n_records) *n_records = (int64_t)N;
+	if (raw_bytes) *raw_bytes = s.header.size() + total;
+	*handled = 1;
+	if (getenv("SK_BAMFILE_TRACE"))
+		fprintf(stderr, "sk_bam_file_rewrite: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, size + index + plan %.1f ms; %lld blocks, %llu by zlib; %llu records, %llu rewritten bytes, %lld windows\n",
+		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_size - fr.t_header, now_ms() - t_size,
+		        (long long)fr.nb, (unsigned long long)fr.n_host, (unsigned long long)N, (unsigned long long)total, (long long)(nw - 1));
+	front_info(fr, info);
+	return SK_OK;
+}
+
+extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
+{
+	if (!c || !w) return SK_ERR_INVALID;
+	memset(w, 0, sizeof *w);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	if (!R || !R->rw.live || R->rw.gen != R->gen) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_rewrite_next: no sk_bam_file_rewrite in progress");
+	if (int r = sk::ctx_bind(c)) return r;
+	RewriteState &s = R->rw;
+	const int b = s.cur;
+	if (b < 0) return SK_OK;                                            // the end
+	BF_HIP(hipEventSynchronize(s.ev[b]));
+	uint64_t bytes = s.h_size[b];
+	int rc = SK_OK;
+	s.cur = rw_issue(c, s, b ^ 1, &rc) ? (b ^ 1) : -1;                    // (the buffer of the window returned last time: the caller is done with it)
+	if (rc) { s.live = false; return rc; }
+	hipStream_t st2 = sk::ctx_stream2(c);
+	if (bytes) BF_HIP(hipMemcpyAsync(s.h_pin[b], s.d_pack[b], (size_t)bytes, hipMemcpyDeviceToHost, st2));
+	BF_HIP(hipEventRecord(s.ev_copy[b], st2));
+	BF_HIP(hipEventSynchronize(s.ev_copy[b]));
+	if (s.cur < 0) { memcpy(s.h_pin[b] + bytes, kBgzfEofBlock, 28); bytes += 28; }   // the last window ends with the EOF block
+	w->first = s.first[b]; w->n = s.n[b];
+	w->bgzf = s.h_pin[b]; w->bytes = bytes; w->raw_bytes = s.raw[b];
 	return SK_OK;
 }

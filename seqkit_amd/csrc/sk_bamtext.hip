@@ -627,6 +627,13 @@ hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, co
 	return hipSuccess;
 }
 
+// v[0 .. n) -> exclusive offsets, v[n] = the sum (sk_bamwrite.hip's passes)
+hipError_t launch_scan_u64(uint64_t *v, int64_t n, hipStream_t st)
+{
+	bam_scan_u64_kernel<<<1, kScanThreads, 0, st>>>((u64 *)v, n);
+	return hipGetLastError();
+}
+
 hipError_t launch_bam_reads_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
                                   const uint64_t *bk, const uint64_t *bt, const uint64_t *bn, uint64_t *krec, uint64_t *ktoff, uint64_t *knoff,
                                   uint64_t *kkey, uint8_t *kkind, hipStream_t st)

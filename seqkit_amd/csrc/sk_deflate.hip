@@ -492,6 +492,16 @@ hipError_t launch_bgzf_deflate(const uint8_t *in, const void *blocks, int64_t n_
 	return hipGetLastError();
 }
 
+// the CRC-32 alone (stored members: sk_bam_file_rewrite at level 0)
+hipError_t launch_bgzf_crc(const uint8_t *in, const void *blocks, int64_t n_blocks, uint32_t *crc, int n_cu, hipStream_t st)
+{
+	if (n_blocks <= 0) return hipSuccess;
+	int64_t cgrid = (n_blocks + 3) / 4;
+	if (cgrid > (int64_t)n_cu * 16) cgrid = (int64_t)n_cu * 16;
+	bgzf_crc_out_kernel<<<dim3((unsigned)cgrid), dim3(256), 0, st>>>(in, reinterpret_cast<const DefBlock *>(blocks), n_blocks, crc);
+	return hipGetLastError();
+}
+
 size_t deflate_tokens_per_block() { return kDefMaxIn; }
 
 }  // namespace sk

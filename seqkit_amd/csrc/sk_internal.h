@@ -185,6 +185,25 @@ hipError_t launch_bam_reads_text(const uint8_t *stream, const uint64_t *krec, co
 hipError_t launch_bgzf_deflate(const uint8_t *in, const void *blocks, int64_t n_blocks, uint8_t *out, uint32_t out_stride, uint32_t *tokens, uint32_t *result,
                                uint32_t *crc, int n_cu, hipStream_t st);
 size_t deflate_tokens_per_block();
+hipError_t launch_bgzf_crc(const uint8_t *in, const void *blocks, int64_t n_blocks, uint32_t *crc, int n_cu, hipStream_t st);
+
+hipError_t launch_scan_u64(uint64_t *v, int64_t n, hipStream_t st);     // sk_bamtext.hip: v[0 .. n) -> exclusive offsets, v[n] the sum
+// ---- BAM out: the per-record rewrite of sk_bam_file_rewrite and the BGZF member packing (sk_bamwrite.hip) ----
+// size: per block the rewritten bytes of the records that begin in it (then exclusive offsets, bo[nb] the total) and the OR of the
+// records' decline bits; index: every record's stream offset and output offset (rb: the blocks' first record indices);
+// windows: where each window of at most W rewritten bytes begins; write: records first .. first + n - 1 into out (out offset o0 at 0)
+hipError_t launch_bam_rw_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int op, uint64_t *bo, uint32_t *decline,
+                              hipStream_t st);
+hipError_t launch_bam_rw_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int op, const uint64_t *bo,
+                               const uint64_t *rb, uint64_t *krec, uint64_t *kout, hipStream_t st);
+hipError_t launch_bam_rw_windows(const uint64_t *kout, int64_t n, uint64_t W, uint64_t total, uint64_t *ws, uint64_t *wo, int64_t nw, hipStream_t st);
+hipError_t launch_bam_rw_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, int op,
+                               uint8_t *out, int n_cu, hipStream_t st);
+// BGZF members of raw[0 .. raw_len): the cut into blocks of at most 0xff00 bytes (blocks: device sk_deflate_block[n]), and, after the
+// deflate (or at level 0 the CRC alone), the members back to back into out: msz[n + 1] scratch, msz[n] = their total bytes afterwards
+hipError_t launch_bgzf_cut(uint64_t raw_len, void *blocks, int64_t n, hipStream_t st);
+hipError_t launch_bgzf_pack(const uint8_t *raw, const void *blocks, int64_t n, const uint8_t *slots, uint32_t slot_stride, const uint32_t *result,
+                            const uint32_t *crc, int stored_only, uint64_t *msz, uint8_t *out, int n_cu, hipStream_t st);
 
 // ---- barcode census (sk_census.hip) ----
 struct Census;
