@@ -1,5 +1,6 @@
 // host_common.cpp — see host_common.h.
 #include "host_common.h"
+#include "sk_bamfmt.h"
 
 #include <dlfcn.h>
 #include <immintrin.h>
@@ -484,7 +485,6 @@ struct Deflater {
 // build's own BgzfStream behind every *.gz input — finds the block boundaries without inflating and inflates the
 // blocks in parallel.
 constexpr size_t kBgzfInput = 0xff00;                       // input bytes per block, as htslib cuts them: the block stays under 64 KiB whatever the data
-static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 static void bgzf_append_block(std::string &out, const char *in, size_t n)
 {
@@ -1198,8 +1198,8 @@ void GzWriter::close()
 	}
 	// BGZF's end-of-file marker: an empty block (also what an empty file consists of: one empty member, like
 	// `gzip -c < /dev/null`)
-	for (size_t off = 0; off < sizeof kBgzfEof;) {
-		const ssize_t w = ::write(impl_->fd, kBgzfEof + off, sizeof kBgzfEof - off);
+	for (size_t off = 0; off < sizeof bamfmt::kBgzfEof;) {
+		const ssize_t w = ::write(impl_->fd, bamfmt::kBgzfEof + off, sizeof bamfmt::kBgzfEof - off);
 		if (w <= 0) break;
 		off += (size_t)w;
 	}

@@ -29,7 +29,9 @@
 #include <vector>
 
 #include "host_common.h"
+#include "sk_bamfmt.h"
 
+using bamfmt::le32;
 using host::error;
 using host::panic;
 
@@ -98,31 +100,15 @@ public:
 	// returns false and the caller, once it has written what the records before the error produce, calls
 	// raise_deferred() — the point the record-at-a-time reference would have reached.
 	void raise_deferred() const { if (!err_.empty()) error("%s", err_.c_str()); }
+	// the sizes of a record's variable part (qname, cigar, packed bases, qualities, aux)
+	struct Var { uint32_t l_read_name, n_cigar, l_seq; };
 	// next record; want_end computes cigar().end_pos() (needed only by the on-target sweep for unpaired reads)
 	bool next(BamCore &c, bool want_end)
 	{
-		if (!err_.empty()) return false;
-		// block_size and the 32-byte core in one read; a short one is sorted out by the rules of the two reads it replaces
-		uint8_t hc[36];
-		const long r = bz_->read(hc, 36);
-		if (r == 0) return false;
-		if (r < 0) return rd_fail("Invalid BAM record.");
-		if (r < 4) return rd_fail("BAM file ended prematurely.");
-		const uint32_t block_size = le32(hc);
-		if (block_size < 32) return rd_fail("Invalid BAM record.");
-		if (r < 36 && !need(hc + r, (size_t)(36 - r))) return false;
-		const uint8_t *core = hc + 4;
-		c.tid = (int32_t)le32(core + 0);
-		c.pos = (int32_t)le32(core + 4);
-		const uint32_t l_read_name = core[8];
-		c.mapq = core[9];
-		const uint32_t n_cigar = (uint32_t)core[12] | ((uint32_t)core[13] << 8);
-		c.flag = (uint16_t)(core[14] | (core[15] << 8));
-		c.mtid = (int32_t)le32(core + 20);
-		c.mpos = (int32_t)le32(core + 24);
-		c.tlen = (int32_t)le32(core + 28);
-		c.end_pos = c.pos;
-		uint32_t rest = block_size - 32;
+		Var v;
+		if (!next_core(c, v)) return false;
+		const uint32_t l_read_name = v.l_read_name, n_cigar = v.n_cigar;
+		uint32_t rest = le32(head) - 32;
 		if (want_end && rest >= l_read_name + 4 * n_cigar) {
 			var_.resize(l_read_name + 4 * n_cigar);
 			if (!need(var_.data(), var_.size())) return false;
@@ -161,33 +147,11 @@ public:
 		out.push_back(c);
 		return true;
 	}
-	// next record with its variable part (qname, cigar, packed bases, qualities, aux) in `body`
-	struct Var { uint32_t l_read_name, n_cigar, l_seq; };
+	// next record with its variable part in `body`
 	bool next_full(BamCore &c, Var &v, std::vector<uint8_t> &body)
 	{
-		if (!err_.empty()) return false;
-		uint8_t hc[36];                                          // block_size and the core in one read, as in next()
-		const long r = bz_->read(hc, 36);
-		if (r == 0) return false;
-		if (r < 0) return rd_fail("Invalid BAM record.");
-		if (r < 4) return rd_fail("BAM file ended prematurely.");
-		const uint32_t block_size = le32(hc);
-		if (block_size < 32) return rd_fail("Invalid BAM record.");
-		if (r < 36 && !need(hc + r, (size_t)(36 - r))) return false;
-		memcpy(head, hc, 36);
-		const uint8_t *core = hc + 4;
-		c.tid = (int32_t)le32(core + 0);
-		c.pos = (int32_t)le32(core + 4);
-		v.l_read_name = core[8];
-		c.mapq = core[9];
-		v.n_cigar = (uint32_t)core[12] | ((uint32_t)core[13] << 8);
-		c.flag = (uint16_t)(core[14] | (core[15] << 8));
-		v.l_seq = le32(core + 16);
-		c.mtid = (int32_t)le32(core + 20);
-		c.mpos = (int32_t)le32(core + 24);
-		c.tlen = (int32_t)le32(core + 28);
-		c.end_pos = c.pos;
-		const uint32_t rest = block_size - 32;
+		if (!next_core(c, v)) return false;
+		const uint32_t rest = le32(head) - 32;
 		// htslib bam_read1: a record whose variable part cannot hold its own fields is invalid
 		if (v.l_read_name < 1 || v.l_seq > 0x7fffffffu ||
 		    (uint64_t)v.n_cigar * 4 + v.l_read_name + (((uint64_t)v.l_seq + 1) >> 1) + v.l_seq > rest) return rd_fail("Invalid BAM record.");
@@ -204,10 +168,34 @@ public:
 	}
 	std::vector<std::string> names;
 	std::vector<uint8_t> header_raw;
-	uint8_t head[36];                                         // next_full: the record's block_size and core as read
+	uint8_t head[36];                                         // the last record's block_size and core as read
 private:
 	[[noreturn]] void open_fail() { error("Cannot open BAM file '%s'", path_.c_str()); }
-	static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+	// block_size and the 32-byte core in one read into head (a short one is sorted out by the rules of the two reads it replaces), and
+	// the core's fields; false as next()
+	bool next_core(BamCore &c, Var &v)
+	{
+		if (!err_.empty()) return false;
+		const long r = bz_->read(head, 36);
+		if (r == 0) return false;
+		if (r < 0) return rd_fail("Invalid BAM record.");
+		if (r < 4) return rd_fail("BAM file ended prematurely.");
+		if (le32(head) < 32) return rd_fail("Invalid BAM record.");
+		if (r < 36 && !need(head + r, (size_t)(36 - r))) return false;
+		const uint8_t *core = head + 4;
+		c.tid = (int32_t)le32(core + 0);
+		c.pos = (int32_t)le32(core + 4);
+		v.l_read_name = core[8];
+		c.mapq = core[9];
+		v.n_cigar = (uint32_t)core[12] | ((uint32_t)core[13] << 8);
+		c.flag = (uint16_t)(core[14] | (core[15] << 8));
+		v.l_seq = le32(core + 16);
+		c.mtid = (int32_t)le32(core + 20);
+		c.mpos = (int32_t)le32(core + 24);
+		c.tlen = (int32_t)le32(core + 28);
+		c.end_pos = c.pos;
+		return true;
+	}
 	bool get(uint8_t *dst, size_t n)
 	{
 		size_t got = 0;
@@ -272,13 +260,13 @@ static std::string expand_home(const std::string &path)      // PathArgs::get_pa
 // sk_bam_file_columns returns ("BAM\1" .. the end of the reference list: checked there already).
 static std::vector<std::string> header_names(const uint8_t *h, uint64_t len)
 {
-	auto le32 = [&](uint64_t o) { return o + 4 <= len ? (uint32_t)h[o] | ((uint32_t)h[o + 1] << 8) | ((uint32_t)h[o + 2] << 16) | ((uint32_t)h[o + 3] << 24) : 0u; };
+	auto u32_at = [&](uint64_t o) { return o + 4 <= len ? le32(h + o) : 0u; };
 	std::vector<std::string> names;
-	uint64_t o = 8 + (uint64_t)le32(4);
-	const uint32_t n_ref = le32(o);
+	uint64_t o = 8 + (uint64_t)u32_at(4);
+	const uint32_t n_ref = u32_at(o);
 	o += 4;
 	for (uint32_t r = 0; r < n_ref && o + 4 <= len; r++) {
-		const uint32_t l_name = le32(o);
+		const uint32_t l_name = u32_at(o);
 		std::string name(reinterpret_cast<const char *>(h + o + 4), std::min<uint64_t>(l_name, len - o - 4));
 		if (!name.empty() && name.back() == '\0') name.pop_back();
 		names.push_back(name);
@@ -301,6 +289,13 @@ struct DevBufs {
 };
 
 static bool file_path_wanted(const std::string &path) { return path != "-" && !getenv("SEQKIT_HOST_INFLATE"); }
+
+// the window size the windowed file calls are asked for (SK_BAMFILE_WINDOW bytes; 0: the library's default)
+static uint64_t file_window_bytes()
+{
+	static const uint64_t window = [] { const char *ev = getenv("SK_BAMFILE_WINDOW"); return ev ? (uint64_t)strtoull(ev, nullptr, 10) : (uint64_t)0; }();
+	return window;
+}
 
 // ---- sam statistics ----------------------------------------------------------------------------------------------
 struct Region { int64_t start, end; };
@@ -328,7 +323,7 @@ static int statistics(int argc, char **argv)
 	// (include/seqkit_hip.h: sk_bam_file_reduce).  It serves well-formed regular files only and says so (handled): everything else —
 	// stdin, plain gzip, a file cut short, a record chain that does not verify — is read record by record below, which reports it as
 	// the reference does.  (--on-target needs pos / cigar of every record in order: the host's sweep, below.)
-	if (targets_path.empty() && bam_path != "-" && !getenv("SEQKIT_HOST_INFLATE")) {
+	if (targets_path.empty() && file_path_wanted(bam_path)) {
 		int handled = 0;
 		uint64_t fc[3] = {0, 0, 0};
 		const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
@@ -446,7 +441,7 @@ static int fragment_lengths(int argc, char **argv)
 	host::gpu_warmup();
 	// H1 over the file on the device (see statistics()); the --reads=N stop depends on record order and keeps the host's path
 	bool by_file = false;
-	if (stop == UINT64_MAX && pos[0] != "-" && !getenv("SEQKIT_HOST_INFLATE")) {
+	if (stop == UINT64_MAX && file_path_wanted(pos[0])) {
 		int handled = 0;
 		uint64_t ft = 0;
 		std::vector<uint64_t> fh(max_frag + 1, 0);
@@ -897,13 +892,12 @@ struct PendingTexts {
 static int64_t to_reads_from_file(const std::string &path, OutFmt format, bool interleaved, ReadSink &out_1, ReadSink &out_2, ReadSink &out_single)
 {
 	sk_ctx *c = host::gpu();
-	static const uint64_t window = [] { const char *ev = getenv("SK_BAMFILE_WINDOW"); return ev ? (uint64_t)strtoull(ev, nullptr, 10) : (uint64_t)0; }();
 	int64_t n_kept = 0;
 	uint64_t text_bytes = 0;
 	int handled = 0;
 	double info[8];
 	const int fmt = format == OutFmt::RAW ? 0 : format == OutFmt::FASTA ? 1 : 2;
-	if (sk_bam_file_reads(c, path.c_str(), fmt, 10 /* :103 */, interleaved ? 0 : 1, window, &n_kept, &text_bytes, &handled, info) != SK_OK || !handled) return -1;
+	if (sk_bam_file_reads(c, path.c_str(), fmt, 10 /* :103 */, interleaved ? 0 : 1, file_window_bytes(), &n_kept, &text_bytes, &handled, info) != SK_OK || !handled) return -1;
 	PendingTexts reads_1, reads_2;
 	sk_bam_reads_window w;
 	for (;;) {
@@ -1121,8 +1115,7 @@ public:
 		if (done_) return;
 		done_ = true;
 		flush();
-		static const uint8_t eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-		write_all(eof, 28);
+		write_all(bamfmt::kBgzfEof, sizeof bamfmt::kBgzfEof);
 	}
 	static void write_all(const uint8_t *p, size_t n)
 	{
@@ -1138,24 +1131,6 @@ private:
 	bool done_ = false;
 	std::vector<uint8_t> buf_, comp_;
 };
-
-// Header::from_template: the text up to its first NUL, trailing '\n's stripped, one '\n' appended when anything is left; the reference
-// list as read (htslib would rebuild it from the @SQ lines: DESIGN.md §10)
-static std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h)
-{
-	auto le32 = [&](size_t o) { return (uint32_t)h[o] | ((uint32_t)h[o + 1] << 8) | ((uint32_t)h[o + 2] << 16) | ((uint32_t)h[o + 3] << 24); };
-	const uint32_t l_text = le32(4);
-	size_t n = 0;
-	while (n < l_text && h[8 + n] != 0) n++;
-	while (n > 0 && h[8 + n - 1] == '\n') n--;
-	const uint32_t l_new = n ? (uint32_t)n + 1 : 0;
-	std::vector<uint8_t> o(h.begin(), h.begin() + 4);
-	for (int k = 0; k < 4; k++) o.push_back((uint8_t)(l_new >> (8 * k)));
-	o.insert(o.end(), h.begin() + 8, h.begin() + 8 + (ptrdiff_t)n);
-	if (n) o.push_back('\n');
-	o.insert(o.end(), h.begin() + 8 + (ptrdiff_t)l_text, h.end());
-	return o;
-}
 
 static BamOut *g_bam_out = nullptr;
 static void finish_bam_out() { if (g_bam_out) g_bam_out->finish(); }    // a panic unwinds through the Writer's drop: what was written stays valid BAM
@@ -1177,7 +1152,7 @@ static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
 		} else if (ty == 'B') {
 			if (v + 5 > n) return false;
 			const uint8_t sub = a[v];
-			const uint32_t cnt = (uint32_t)a[v + 1] | ((uint32_t)a[v + 2] << 8) | ((uint32_t)a[v + 3] << 16) | ((uint32_t)a[v + 4] << 24);
+			const uint32_t cnt = le32(a + v + 1);
 			const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
 			if (!es) return false;
 			e = v + 5 + (size_t)cnt * es;
@@ -1193,6 +1168,25 @@ static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
 	return false;
 }
 
+// the rewrite over the FILE: the device rewrites and compresses every window (sk_bam_file_rewrite), and the members go to stdout as they
+// arrive.  -1: nothing has been written, and the caller's reader serves the file (one the file path does not take, a device without room,
+// or a record the reference would stop at).  Otherwise the number of records.
+static int64_t rewrite_from_file(const std::string &path, int op, int level)
+{
+	sk_ctx *c = host::gpu();
+	int64_t n_rec = 0;
+	uint64_t raw = 0;
+	int handled = 0;
+	if (sk_bam_file_rewrite(c, path.c_str(), op, level, file_window_bytes(), &n_rec, &raw, &handled, nullptr) != SK_OK || !handled) return -1;
+	sk_bam_out_window w;
+	for (;;) {
+		check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
+		if (w.n == 0 && w.bytes == 0) break;
+		BamOut::write_all(w.bgzf, (size_t)w.bytes);
+	}
+	return n_rec;
+}
+
 static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usage, bool has_uncompressed)
 {
 	std::vector<host::Opt> opts;
@@ -1205,19 +1199,9 @@ static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usa
 	host::gpu_warmup();
 	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
 	if (file_path_wanted(path)) {
-		sk_ctx *c = host::gpu();
-		static const uint64_t window = [] { const char *ev = getenv("SK_BAMFILE_WINDOW"); return ev ? (uint64_t)strtoull(ev, nullptr, 10) : (uint64_t)0; }();
-		int64_t n_rec = 0;
-		uint64_t raw = 0;
-		int handled = 0;
-		if (sk_bam_file_rewrite(c, path.c_str(), op, level, window, &n_rec, &raw, &handled, nullptr) == SK_OK && handled) {
-			sk_bam_out_window w;
-			for (;;) {
-				check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
-				if (w.n == 0 && w.bytes == 0) break;
-				BamOut::write_all(w.bgzf, (size_t)w.bytes);
-			}
-			if (trace) fprintf(stderr, "%s: device path, %lld records\n", who, (long long)n_rec);
+		const int64_t n = rewrite_from_file(path, op, level);
+		if (n >= 0) {
+			if (trace) fprintf(stderr, "%s: device path, %lld records\n", who, (long long)n);
 			return 0;
 		}
 	}
@@ -1226,7 +1210,7 @@ static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usa
 	BamOut out(level);
 	g_bam_out = &out;
 	host::at_exit_flush(finish_bam_out);
-	const std::vector<uint8_t> hdr = rewrite_header(bam.header_raw);
+	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
 	out.put(hdr.data(), hdr.size());
 	out.flush();                                                                // (the header in members of its own)
 	BamCore c;

@@ -29,7 +29,10 @@
 #include <vector>
 
 #include "../../include/seqkit_hip.h"
+#include "sk_bamfmt.h"
 #include "sk_internal.h"
+
+using bamfmt::le32;
 
 namespace {
 
@@ -66,9 +69,6 @@ bool pread_full(int fd, uint8_t *dst, size_t n, uint64_t off)
 	}
 	return true;
 }
-
-// [off, off + n) of the file into dst, by `threads` threads
-inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 }  // namespace
 
@@ -168,48 +168,66 @@ struct Mapper {
 	bool wait_for(size_t bytes) { std::unique_lock<std::mutex> lk(m); if (bytes > want) { want = std::min(bytes, r->reserved); cv.notify_all(); } cv.wait(lk, [&] { return failed || have >= bytes; }); return !failed; }
 	~Mapper() { if (th.joinable()) { { std::lock_guard<std::mutex> lk(m); stop = true; cv.notify_all(); } th.join(); } }
 };
-// sk_bam_file_reads / sk_bam_file_reads_next: the kept records' columns (device, ctx slot kKeepReadCols), the window plan, and two
-// window buffers on each side (ctx slots kKeepReadWin / kKeepReadPin), one window in flight while the caller works on the other
-struct ReadsState {
+// an event the host sleeps on (created once, kept with the state); false: the runtime refused it
+static bool blocking_event(hipEvent_t &e)
+{
+	if (!e && hipEventCreateWithFlags(&e, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = nullptr; return false; }
+	return true;
+}
+
+// The double buffer of a windowed file call (sk_bam_file_reads, sk_bam_file_rewrite): the window plan, the next window to issue, and per
+// buffer the window in it and the event its work ends with.  One window is in flight while the caller works on the other.
+struct WindowedState {
 	bool live = false;
 	uint64_t gen = 0;                            // Ranges::gen of the file call that set it up
-	int fmt = 0;
-	uint8_t min_baseq = 10;
-	const uint8_t *d_out = nullptr;
-	uint64_t *krec = nullptr, *ktoff = nullptr, *knoff = nullptr, *kkey = nullptr;
-	uint8_t *kkind = nullptr;
-	std::vector<uint64_t> ws, wt, wn;            // window w: kept records ws[w] .., text bytes wt[w] .., name bytes wn[w] .. (up to w + 1)
+	const uint8_t *d_out = nullptr;              // the verified stream
+	std::vector<uint64_t> ws;                    // window w: records ws[w] .. ws[w + 1]
 	size_t next_w = 0;                           // the next window to issue
-	uint8_t *d_win[2] = {nullptr, nullptr}, *h_win[2] = {nullptr, nullptr};
-	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
 	hipEvent_t ev[2] = {nullptr, nullptr};
 	int64_t first[2] = {0, 0}, n[2] = {0, 0};
 	int cur = -1;                                // the buffer whose window is in flight, -1: none (the end)
-	~ReadsState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+	~WindowedState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+	bool busy() const { return live || cur >= 0; }
+	void stop() { live = false; cur = -1; }
+	bool current(uint64_t file_gen) const { return live && gen == file_gen; }     // (a *_next call continues it)
+	void begin(const uint8_t *stream, uint64_t file_gen) { d_out = stream; gen = file_gen; next_w = 0; cur = -1; }
+	bool next_window(size_t &w)                  // the next non-empty window of the plan; false: none left
+	{
+		while (next_w + 1 < ws.size() && ws[next_w + 1] == ws[next_w]) next_w++;
+		if (next_w + 1 >= ws.size()) return false;
+		w = next_w++;
+		return true;
+	}
 };
 
-// sk_bam_file_rewrite / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot kKeepRwCols), the window
-// plan, one device area for the window being rewritten and compressed (raw bytes, deflate scratch, blocks) and two packed-member
-// buffers on each side (ctx slots kKeepRwWin / kKeepRwPin): one window in flight while the caller writes the other
-struct RewriteState {
-	bool live = false;
-	uint64_t gen = 0;                            // Ranges::gen of the file call that set it up
+// sk_bam_file_reads / sk_bam_file_reads_next: the kept records' columns (device, ctx slot kKeepFileCols), the window plan (text and name
+// bytes of window w from wt[w] / wn[w] on), and two window buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
+struct ReadsState : WindowedState {
+	int fmt = 0;
+	uint8_t min_baseq = 10;
+	uint64_t *krec = nullptr, *ktoff = nullptr, *knoff = nullptr, *kkey = nullptr;
+	uint8_t *kkind = nullptr;
+	std::vector<uint64_t> wt, wn;
+	uint8_t *d_win[2] = {nullptr, nullptr}, *h_win[2] = {nullptr, nullptr};
+	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
+};
+
+// sk_bam_file_rewrite / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot kKeepFileCols), the window
+// plan (output bytes of window w from wo[w] on), one device area for the window being rewritten and compressed (raw bytes, deflate
+// scratch, blocks) and two packed-member buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
+struct RewriteState : WindowedState {
 	int op = 0, level = 1;
-	const uint8_t *d_out = nullptr;
 	uint64_t *krec = nullptr, *kout = nullptr;
-	std::vector<uint64_t> ws, wo;                // window w: records ws[w] .., output bytes wo[w] .. (up to w + 1)
+	std::vector<uint64_t> wo;
 	std::vector<uint8_t> header;                 // the output header (the first window)
-	size_t next_w = 0;
 	bool header_done = false;
 	uint8_t *d_raw = nullptr, *d_slots = nullptr, *d_pack[2] = {nullptr, nullptr}, *h_pin[2] = {nullptr, nullptr};
 	uint32_t *d_tokens = nullptr, *d_result = nullptr, *d_crc = nullptr;
 	uint64_t *d_msz = nullptr, *h_size = nullptr;   // h_size[b]: window b's packed bytes (page-locked)
 	void *d_blocks = nullptr;
-	hipEvent_t ev[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
-	int64_t first[2] = {0, 0}, n[2] = {0, 0};
+	hipEvent_t ev_copy[2] = {nullptr, nullptr};     // the copy of packed buffer b on the second stream
 	uint64_t raw[2] = {0, 0};
-	int cur = -1;                                // the buffer whose window is in flight, -1: none (the end)
-	~RewriteState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
+	~RewriteState() { for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
 };
 
 // what stays with the ctx: the range of the compressed file and the range of the inflated stream
@@ -217,7 +235,7 @@ struct Ranges {
 	OutRange comp, out;
 	std::vector<uint8_t> header;                 // sk_bam_file_columns: the last file's header bytes (cols->header)
 	uint64_t gen = 0;                            // file calls so far: a reads state of an earlier call is stale
-	ReadsState reads;
+	ReadsState reads;                            // (only one of the two is live: the next file call ends either)
 	RewriteState rw;
 	static void destroy(void *p) { Ranges *r = (Ranges *)p; r->comp.release(); r->out.release(); delete r; }
 };
@@ -299,6 +317,7 @@ struct Readers {
 // 64 bytes beyond; block_end and entry of the walk) and, on the host, the per-block record counts and the header bytes.  ready = false
 // (info[5] = -check): the file is not one this path serves.  The device buffers of d_bend / d_entry belong to the caller's Cleanup.
 struct Front {
+	const char *who = nullptr;                   // the file call, in trace lines and messages
 	bool ready = false;
 	const uint8_t *d_out = nullptr;
 	uint64_t stream_len = 0, first = 0, n_records = 0, fsize = 0, n_host = 0;
@@ -312,24 +331,23 @@ struct Front {
 };
 
 // open and stat, the buffers, the readers, the BGZF headers and the batches of inflate launches, zlib for the blocks the device gave up,
-// the BAM header, the walk and its verification: everything both file calls do before they read the records.  `who` names the caller
+// the BAM header, the walk and its verification: everything the file calls do before they read the records.  fr.who names the caller
 // in trace lines.
-static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup &cl, Front &fr, double info[8])
+static int bam_file_front(sk_ctx *c, const char *path, Cleanup &cl, Front &fr, double info[8])
 {
+	const char *who = fr.who;
 	Ranges *both = (Ranges *)sk::ctx_ext(c);
 	if (!both) { both = new Ranges; sk::ctx_set_ext(c, both, Ranges::destroy); }
 	// an earlier sk_bam_file_reads may have left a window in flight on the ctx stream: its text kernel reads the inflated stream and its
 	// copies write the page-locked window buffers.  It ends before this call remaps the ranges or takes the kept buffers again.
 	// (the same for an sk_bam_file_rewrite, whose window copies run on the second stream)
-	if (both->reads.live || both->reads.cur >= 0 || both->rw.live || both->rw.cur >= 0) {
+	if (both->reads.busy() || both->rw.busy()) {
 		BF_HIP(hipStreamSynchronize(sk::ctx_stream(c)));
 		BF_HIP(hipStreamSynchronize(sk::ctx_stream2(c)));
 	}
-	both->gen++;                                                        // (what an earlier sk_bam_file_reads left is no longer read)
-	both->reads.live = false;
-	both->reads.cur = -1;
-	both->rw.live = false;
-	both->rw.cur = -1;
+	both->gen++;                                                        // (what an earlier windowed call left is no longer read)
+	both->reads.stop();
+	both->rw.stop();
 	cl.fd = open(path, O_RDONLY);
 	if (cl.fd < 0) BF_LEAVE(1);                                        // (the caller's reader says so in the reference's words)
 	struct stat sb;
@@ -344,7 +362,6 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 	// THE CTX from one call to the next (sk::ctx_keep; sk_destroy frees them): a process that gave 20 GB back and asked for them again
 	// found one call in three waiting 1.3-2.4 s in its reading loop — the copies queue behind what the driver does with memory
 	// that changes hands (with a third of the room: none in nine calls; the first call of a process: never).
-	enum { kKeepComp = 0, kKeepOut = 1, kKeepPin = 2, kKeepTable = 3, kKeepBlocks = 4, kKeepStatus = 5 };
 	int krc = SK_OK;
 	uint64_t out_cap = std::max<uint64_t>(fsize * 6, (uint64_t)256 << 20);
 	if (const char *ev = getenv("SK_BAMFILE_OUT_FACTOR")) { const int f = atoi(ev); if (f >= 1 && f <= 1100) out_cap = std::max<uint64_t>(fsize * (uint64_t)f, (uint64_t)1 << 20); }
@@ -373,23 +390,23 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 			cmapper.start(crange);
 			cmapper.ask((size_t)fsize + 64);                              // (all of the file's range, ahead of the readers)
 		} else {
-			d_comp = (uint8_t *)sk::ctx_keep(c, kKeepComp, fsize + 64, false, &krc);
+			d_comp = (uint8_t *)sk::ctx_keep(c, sk::kKeepComp, fsize + 64, false, &krc);
 			if (!d_comp) return krc;
 		}
 		mapper.start(range);
 		mapper.ask(std::min<size_t>((size_t)fsize * 2, range->reserved));   // (a BAM inflates at least that far: on its way before the first byte is read)
-	} else if (sk::ctx_kept_bytes(c, kKeepOut) >= out_cap + 64) {
-		out_cap = sk::ctx_kept_bytes(c, kKeepOut) - 64;                   // (what an earlier call took: all of it is room)
-		d_out = (uint8_t *)sk::ctx_keep(c, kKeepOut, out_cap + 64, false, &krc);
-		d_comp = (uint8_t *)sk::ctx_keep(c, kKeepComp, fsize + 64, false, &krc);
+	} else if (sk::ctx_kept_bytes(c, sk::kKeepOut) >= out_cap + 64) {
+		out_cap = sk::ctx_kept_bytes(c, sk::kKeepOut) - 64;                   // (what an earlier call took: all of it is room)
+		d_out = (uint8_t *)sk::ctx_keep(c, sk::kKeepOut, out_cap + 64, false, &krc);
+		d_comp = (uint8_t *)sk::ctx_keep(c, sk::kKeepComp, fsize + 64, false, &krc);
 		if (!d_comp) return krc;
 	} else {
-		d_comp = (uint8_t *)sk::ctx_keep(c, kKeepComp, fsize + 64, false, &krc);
+		d_comp = (uint8_t *)sk::ctx_keep(c, sk::kKeepComp, fsize + 64, false, &krc);
 		if (!d_comp) return krc;
 		size_t free_b = 0, total_b = 0;
 		BF_HIP(hipMemGetInfo(&free_b, &total_b));
-		out_cap = std::min<uint64_t>(out_cap, (uint64_t)((free_b + sk::ctx_kept_bytes(c, kKeepOut)) * 0.8));
-		d_out = (uint8_t *)sk::ctx_keep(c, kKeepOut, out_cap + 64, false, &krc);
+		out_cap = std::min<uint64_t>(out_cap, (uint64_t)((free_b + sk::ctx_kept_bytes(c, sk::kKeepOut)) * 0.8));
+		d_out = (uint8_t *)sk::ctx_keep(c, sk::kKeepOut, out_cap + 64, false, &krc);
 		if (!d_out) BF_LEAVE(3);
 	}
 
@@ -402,7 +419,7 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 	const int kBufs = threads + threads / 2 + 1;
 	Readers rd;
 	rd.fd = cl.fd; rd.chunk = chunk; rd.fsize = fsize; rd.R = kBufs;
-	rd.ring = (uint8_t *)sk::ctx_keep(c, kKeepPin, (size_t)kBufs * chunk, true, &krc);
+	rd.ring = (uint8_t *)sk::ctx_keep(c, sk::kKeepPin, (size_t)kBufs * chunk, true, &krc);
 	if (!rd.ring) return krc;
 	BF_HIP(hipGetDevice(&rd.device));
 	for (int i = 0; i < kBufs; i++) {
@@ -425,15 +442,15 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 		sk_bgzf_block *data() const { return p; }
 		sk_bgzf_block &operator[](size_t i) const { return p[i]; }
 	} blocks;
-	blocks.p = (sk_bgzf_block *)sk::ctx_keep(c, kKeepTable, tab_cap * sizeof(sk_bgzf_block), true, &krc);
+	blocks.p = (sk_bgzf_block *)sk::ctx_keep(c, sk::kKeepTable, tab_cap * sizeof(sk_bgzf_block), true, &krc);
 	if (!blocks.p) return krc;
 	std::vector<uint64_t> bend;
 	bend.reserve(tab_cap);
 	const double t_alloc_pre = now_ms();
 	(void)t_alloc_pre;
-	sk_bgzf_block *d_blocks = (sk_bgzf_block *)sk::ctx_keep(c, kKeepBlocks, tab_cap * sizeof(sk_bgzf_block), false, &krc);
+	sk_bgzf_block *d_blocks = (sk_bgzf_block *)sk::ctx_keep(c, sk::kKeepBlocks, tab_cap * sizeof(sk_bgzf_block), false, &krc);
 	if (!d_blocks) return krc;
-	uint32_t *d_status = (uint32_t *)sk::ctx_keep(c, kKeepStatus, tab_cap * sizeof(uint32_t), false, &krc);
+	uint32_t *d_status = (uint32_t *)sk::ctx_keep(c, sk::kKeepStatus, tab_cap * sizeof(uint32_t), false, &krc);
 	if (!d_status) return krc;
 
 	const double t_alloc = now_ms();
@@ -643,25 +660,89 @@ static int bam_file_front(sk_ctx *c, const char *path, const char *who, Cleanup 
 	return SK_OK;
 }
 
-static void front_info(const Front &fr, double info[8])
+// The opening every file call shares: with c, path and handled given, *handled = 0 and info cleared, then the call's own checks (`check`:
+// SK_OK or an error code), the device bound and the front half run.  SK_OK with fr.ready = false: not this path's file (info[5] says why).
+template <class Check>
+static int file_call_open(sk_ctx *c, const char *path, const char *who, int *handled, double info[8], Cleanup &cl, Front &fr, Check check)
 {
+	if (!c || !path || !handled) return SK_ERR_INVALID;
+	*handled = 0;
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (int r = check()) return r;
+	if (int r = sk::ctx_bind(c)) return r;
+	fr.who = who;
+	return bam_file_front(c, path, cl, fr, info);
+}
+
+// The closing every file call shares: the trace line (the front half's stages, the walk up to t_stage, the call's own `stage` from
+// there, and `tail`) and info[].
+static void file_call_close(const Front &fr, const char *stage, double t_stage, const char *tail, double info[8])
+{
+	if (getenv("SK_BAMFILE_TRACE"))
+		fprintf(stderr, "%s: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, %s %.1f ms; %lld blocks, %llu by zlib%s\n",
+		        fr.who, fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_stage - fr.t_header, stage,
+		        now_ms() - t_stage, (long long)fr.nb, (unsigned long long)fr.n_host, tail);
 	if (!info) return;
 	info[0] = (double)fr.fsize; info[1] = (double)fr.stream_len; info[2] = (double)fr.nb; info[3] = (double)fr.n_records;
 	info[4] = (double)fr.n_host; info[5] = (double)fr.rounds; info[6] = fr.t_read - fr.t0; info[7] = now_ms() - fr.t_read;
 }
 
+// where every block's first record goes: the exclusive prefix of the walk's per-block counts, rb[nb] = the records
+static int block_first_records(sk_ctx *c, const Front &fr, std::vector<uint64_t> &rb)
+{
+	rb.resize((size_t)fr.nb + 1);
+	uint64_t run = 0;
+	for (int64_t i = 0; i < fr.nb; i++) { rb[(size_t)i] = run; run += fr.nrec[(size_t)i]; }
+	rb[(size_t)fr.nb] = run;
+	if (run != fr.n_records)
+		return sk::ctx_fail(c, SK_ERR_HIP, "%s: %llu records by the blocks' counts, %llu by the walk", fr.who, (unsigned long long)run, (unsigned long long)fr.n_records);
+	return SK_OK;
+}
+
+// The window plan of a windowed call (sk_internal.h: launch_bam_windows): window w holds the records whose off0 + off1 bytes (off1 ==
+// nullptr: off0) lie in [w W, (w + 1) W), W = window_bytes (0: 64 MiB) kept within [256 B, 1 GiB]; one record may go beyond.  s.ws, w0
+// and w1 (only with off1) come back with an entry past the last window; max[0 .. 2] = the most records, off0 bytes and off1 bytes of any
+// window.  *room = false: no device memory for the plan.
+static int plan_windows(sk_ctx *c, Cleanup &cl, uint64_t window_bytes, const uint64_t *off0, const uint64_t *off1, uint64_t n, uint64_t total0,
+                        uint64_t total1, WindowedState &s, std::vector<uint64_t> &w0, std::vector<uint64_t> *w1, uint64_t max[3], bool *room)
+{
+	*room = true;
+	uint64_t W = window_bytes ? window_bytes : (uint64_t)64 << 20;
+	W = std::min<uint64_t>(std::max<uint64_t>(W, 256), (uint64_t)1 << 30);
+	const int64_t nw = n ? (int64_t)((total0 + total1) / W + 2) : 1;
+	s.ws.assign((size_t)nw, n); w0.assign((size_t)nw, total0);
+	if (w1) w1->assign((size_t)nw, total1);
+	if (n) {
+		hipStream_t st = sk::ctx_stream(c);
+		uint64_t *d_w = nullptr;
+		if (hipMalloc((void **)&d_w, (size_t)nw * (w1 ? 24 : 16)) != hipSuccess) { (void)hipGetLastError(); *room = false; return SK_OK; }
+		cl.dev.push_back(d_w);
+		BF_HIP(sk::launch_bam_windows(off0, off1, (int64_t)n, W, total0, total1, d_w, d_w + nw, w1 ? d_w + 2 * nw : nullptr, nw, st));
+		BF_HIP(hipMemcpyAsync(s.ws.data(), d_w, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipMemcpyAsync(w0.data(), d_w + nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		if (w1) BF_HIP(hipMemcpyAsync(w1->data(), d_w + 2 * nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	max[0] = max[1] = max[2] = 0;
+	for (size_t w = 0; w + 1 < (size_t)nw; w++) {
+		max[0] = std::max(max[0], s.ws[w + 1] - s.ws[w]);
+		max[1] = std::max(max[1], w0[w + 1] - w0[w]);
+		if (w1) max[2] = std::max(max[2], (*w1)[w + 1] - (*w1)[w]);
+	}
+	return SK_OK;
+}
+
 extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag, uint64_t counters[3], uint64_t *hist, uint64_t *hist_total,
                                   int *handled, double info[8])
 {
-	if (!c || !path || !handled) return SK_ERR_INVALID;
-	*handled = 0;
-	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
-	if (max_frag < 0) return sk::ctx_fail(c, SK_ERR_INVALID, "max_frag = %d", max_frag);
-	if (!counters && !hist) return sk::ctx_fail(c, SK_ERR_INVALID, "nothing to do");
-	if (int r = sk::ctx_bind(c)) return r;
 	Cleanup cl;
 	Front fr;
-	if (int r = bam_file_front(c, path, "sk_bam_file_reduce", cl, fr, info)) return r;
+	if (int r = file_call_open(c, path, "sk_bam_file_reduce", handled, info, cl, fr, [&] {
+		    if (max_frag < 0) return sk::ctx_fail(c, SK_ERR_INVALID, "max_frag = %d", max_frag);
+		    if (!counters && !hist) return sk::ctx_fail(c, SK_ERR_INVALID, "nothing to do");
+		    return (int)SK_OK;
+	    }))
+		return r;
 	if (!fr.ready) return SK_OK;
 	// ---- the records: reduce
 	hipStream_t st = sk::ctx_stream(c);
@@ -679,11 +760,7 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 		for (size_t i = 0; i <= (size_t)max_frag; i++) hist[i] += red[4 + i];
 	}
 	*handled = 1;
-	if (getenv("SK_BAMFILE_TRACE"))
-		fprintf(stderr, "sk_bam_file_reduce: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, reduce %.1f ms; %lld blocks, %llu by zlib\n",
-		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, fr.t_walk - fr.t_header, now_ms() - fr.t_walk,
-		        (long long)fr.nb, (unsigned long long)fr.n_host);
-	front_info(fr, info);
+	file_call_close(fr, "reduce", fr.t_walk, "", info);
 	return SK_OK;
 }
 
@@ -692,20 +769,19 @@ extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag,
 // columns — leaves *handled = 0 for the caller's reader.
 extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, sk_bam_columns *cols, int *handled, double info[8])
 {
-	if (!c || !path || !handled || !cols) return SK_ERR_INVALID;
-	*handled = 0;
-	memset(cols, 0, sizeof *cols);
-	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
-	if (want & ~(uint32_t)SK_COL_ALL) return sk::ctx_fail(c, SK_ERR_INVALID, "want = %#x", want);
-	if (int r = sk::ctx_bind(c)) return r;
+	if (!cols) return SK_ERR_INVALID;
 	Cleanup cl;
 	Front fr;
-	if (int r = bam_file_front(c, path, "sk_bam_file_columns", cl, fr, info)) return r;
+	if (int r = file_call_open(c, path, "sk_bam_file_columns", handled, info, cl, fr, [&] {
+		    memset(cols, 0, sizeof *cols);
+		    if (want & ~(uint32_t)SK_COL_ALL) return sk::ctx_fail(c, SK_ERR_INVALID, "want = %#x", want);
+		    return (int)SK_OK;
+	    }))
+		return r;
 	if (!fr.ready) return SK_OK;
 	hipStream_t st = sk::ctx_stream(c);
 	const double t_gather = now_ms();
 	// ---- the columns: one kept allocation
-	enum { kKeepCols = 6 };
 	const uint64_t n = fr.n_records;
 	static const size_t width[8] = {2, 1, 4, 4, 4, 4, 4, 4};               // SK_COL_FLAG .. SK_COL_END
 	size_t at[8], total = 0;
@@ -714,19 +790,12 @@ extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, s
 		if (want & (1u << k)) total += ((size_t)n * width[k] + 16 + 255) & ~(size_t)255;
 	}
 	int krc = SK_OK;
-	uint8_t *base = (uint8_t *)sk::ctx_keep(c, kKeepCols, total ? total : 256, false, &krc);
-	if (!base) {                                                         // (a busy device: the caller's reader serves the file)
-		if (info) info[5] = -21.0;
-		return SK_OK;
-	}
+	uint8_t *base = (uint8_t *)sk::ctx_keep(c, sk::kKeepCols, total ? total : 256, false, &krc);
+	if (!base) BF_LEAVE(21);                                             // (a busy device: the caller's reader serves the file)
 	void *col[8];
 	for (int k = 0; k < 8; k++) col[k] = (want & (1u << k)) ? (void *)(base + at[k]) : nullptr;
-	// ---- where every block's first record goes: the exclusive prefix of the walk's counts
-	std::vector<uint64_t> rb((size_t)fr.nb + 1);
-	uint64_t run = 0;
-	for (int64_t i = 0; i < fr.nb; i++) { rb[(size_t)i] = run; run += fr.nrec[(size_t)i]; }
-	rb[(size_t)fr.nb] = run;
-	if (run != n) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_columns: %llu records by the blocks' counts, %llu by the walk", (unsigned long long)run, (unsigned long long)n);
+	std::vector<uint64_t> rb;
+	if (int r = block_first_records(c, fr, rb)) return r;
 	if (want && fr.nb) {
 		uint64_t *d_rb = nullptr;
 		BF_HIP(hipMalloc((void **)&d_rb, rb.size() * 8)); cl.dev.push_back(d_rb);
@@ -736,7 +805,6 @@ extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, s
 	}
 	BF_HIP(hipStreamSynchronize(st));
 	Ranges *keep = (Ranges *)sk::ctx_ext(c);
-	if (!keep) { keep = new Ranges; sk::ctx_set_ext(c, keep, Ranges::destroy); }
 	keep->header.swap(fr.header);
 	cols->n = (int64_t)n;
 	cols->flag = (uint16_t *)col[0]; cols->mapq = (uint8_t *)col[1]; cols->tid = (int32_t *)col[2]; cols->mtid = (int32_t *)col[3];
@@ -745,11 +813,7 @@ extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, s
 	cols->header_len = keep->header.size();
 	cols->n_ref = fr.n_ref;
 	*handled = 1;
-	if (getenv("SK_BAMFILE_TRACE"))
-		fprintf(stderr, "sk_bam_file_columns: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, gather %.1f ms; %lld blocks, %llu by zlib\n",
-		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_gather - fr.t_header, now_ms() - t_gather,
-		        (long long)fr.nb, (unsigned long long)fr.n_host);
-	front_info(fr, info);
+	file_call_close(fr, "gather", t_gather, "", info);
 	return SK_OK;
 }
 
@@ -762,9 +826,8 @@ extern "C" int sk_bam_file_columns(sk_ctx *c, const char *path, uint32_t want, s
 static bool reads_issue(sk_ctx *c, ReadsState &s, int b, int *rc)
 {
 	*rc = SK_OK;
-	while (s.next_w + 1 < s.ws.size() && s.ws[s.next_w + 1] == s.ws[s.next_w]) s.next_w++;
-	if (s.next_w + 1 >= s.ws.size()) return false;
-	const size_t w = s.next_w++;
+	size_t w;
+	if (!s.next_window(w)) return false;
 	const int64_t first = (int64_t)s.ws[w], n = (int64_t)(s.ws[w + 1] - s.ws[w]);
 	const uint64_t t0 = s.wt[w], tb = s.wt[w + 1] - t0, n0 = s.wn[w], nbytes = s.wn[w + 1] - n0;
 	hipStream_t st = sk::ctx_stream(c);
@@ -786,16 +849,15 @@ static bool reads_issue(sk_ctx *c, ReadsState &s, int b, int *rc)
 extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_t min_baseq, int want_unpaired, uint64_t window_bytes, int64_t *n_kept,
                                  uint64_t *text_bytes, int *handled, double info[8])
 {
-	if (!c || !path || !handled) return SK_ERR_INVALID;
-	*handled = 0;
-	if (n_kept) *n_kept = 0;
-	if (text_bytes) *text_bytes = 0;
-	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
-	if (format < 0 || format > 2) return sk::ctx_fail(c, SK_ERR_INVALID, "format = %d", format);
-	if (int r = sk::ctx_bind(c)) return r;
 	Cleanup cl;
 	Front fr;
-	if (int r = bam_file_front(c, path, "sk_bam_file_reads", cl, fr, info)) return r;
+	if (int r = file_call_open(c, path, "sk_bam_file_reads", handled, info, cl, fr, [&] {
+		    if (n_kept) *n_kept = 0;
+		    if (text_bytes) *text_bytes = 0;
+		    if (format < 0 || format > 2) return sk::ctx_fail(c, SK_ERR_INVALID, "format = %d", format);
+		    return (int)SK_OK;
+	    }))
+		return r;
 	if (!fr.ready) return SK_OK;
 	hipStream_t st = sk::ctx_stream(c);
 	const double t_size = now_ms();
@@ -819,37 +881,21 @@ extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_
 	if (decline) BF_LEAVE(30 + decline);                                // (1 qname, 2 fastq quality, 4 l_seq, 8 invalid record: info[5] = -31 .. -45)
 	const int64_t K = (int64_t)tot[0];
 	const uint64_t T = tot[1], N = tot[2];
-	// ---- the kept records' columns (ctx slot 9): stream offset, text offset, name offset, key, kind
-	enum { kKeepReadCols = 9, kKeepReadWin = 10, kKeepReadPin = 11 };
+	// ---- the kept records' columns: stream offset, text offset, name offset, key, kind
 	int krc = SK_OK;
 	const size_t kcol = ((size_t)K * 8 + 255) & ~(size_t)255;
-	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, kKeepReadCols, kcol * 4 + (((size_t)K + 255) & ~(size_t)255) + 256, false, &krc);
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, kcol * 4 + (((size_t)K + 255) & ~(size_t)255) + 256, false, &krc);
 	if (!kb) BF_LEAVE(21);
 	Ranges *R = (Ranges *)sk::ctx_ext(c);
 	ReadsState &s = R->reads;
 	s.krec = (uint64_t *)kb; s.ktoff = (uint64_t *)(kb + kcol); s.knoff = (uint64_t *)(kb + 2 * kcol); s.kkey = (uint64_t *)(kb + 3 * kcol); s.kkind = kb + 4 * kcol;
 	BF_HIP(sk::launch_bam_reads_index(fr.d_out, fr.d_bend, fr.d_entry, nb, format, want_unpaired ? 1 : 0, bk, bt, bn, s.krec, s.ktoff, s.knoff, s.kkey, s.kkind, st));
-	// ---- the windows: at most W text + name bytes each (one record may go beyond)
-	uint64_t W = window_bytes ? window_bytes : (uint64_t)64 << 20;
-	W = std::min<uint64_t>(std::max<uint64_t>(W, 256), (uint64_t)1 << 30);
-	const int64_t nw = K ? (int64_t)((T + N) / W + 2) : 1;
-	s.ws.assign((size_t)nw, (uint64_t)K); s.wt.assign((size_t)nw, T); s.wn.assign((size_t)nw, N);
-	if (K) {
-		uint64_t *d_w = nullptr;
-		if (hipMalloc((void **)&d_w, (size_t)nw * 24) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
-		cl.dev.push_back(d_w);
-		BF_HIP(sk::launch_bam_reads_windows(s.ktoff, s.knoff, K, W, T, N, d_w, d_w + nw, d_w + 2 * nw, nw, st));
-		BF_HIP(hipMemcpyAsync(s.ws.data(), d_w, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
-		BF_HIP(hipMemcpyAsync(s.wt.data(), d_w + nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
-		BF_HIP(hipMemcpyAsync(s.wn.data(), d_w + 2 * nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
-		BF_HIP(hipStreamSynchronize(st));
-	}
-	uint64_t max_n = 0, max_t = 0, max_nm = 0;
-	for (int64_t w = 0; w + 1 < nw; w++) {
-		max_n = std::max(max_n, s.ws[(size_t)w + 1] - s.ws[(size_t)w]);
-		max_t = std::max(max_t, s.wt[(size_t)w + 1] - s.wt[(size_t)w]);
-		max_nm = std::max(max_nm, s.wn[(size_t)w + 1] - s.wn[(size_t)w]);
-	}
+	// ---- the windows: at most W text + name bytes each
+	uint64_t mx[3];                                                     // records, text bytes, name bytes
+	bool room = true;
+	if (int r = plan_windows(c, cl, window_bytes, s.ktoff, s.knoff, (uint64_t)K, T, N, s, s.wt, &s.wn, mx, &room)) return r;
+	if (!room) BF_LEAVE(21);
+	const uint64_t max_n = mx[0], max_t = mx[1], max_nm = mx[2];
 	// ---- two window buffers, on the device and page-locked, in one layout
 	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
 	s.at_toff = up(max_t + 16);
@@ -858,16 +904,16 @@ extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_
 	s.at_kind = s.at_names + up(max_nm + 16);
 	s.at_key = s.at_kind + up(max_n + 16);
 	const size_t wbytes = s.at_key + up(max_n * 8 + 16);
-	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, kKeepReadWin, 2 * wbytes, false, &krc);
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, 2 * wbytes, false, &krc);
 	if (!dw) BF_LEAVE(21);
-	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, kKeepReadPin, 2 * wbytes, true, &krc);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * wbytes, true, &krc);
 	if (!hw) BF_LEAVE(21);
 	for (int b = 0; b < 2; b++) {
 		s.d_win[b] = dw + (size_t)b * wbytes; s.h_win[b] = hw + (size_t)b * wbytes;
-		if (!s.ev[b] && hipEventCreateWithFlags(&s.ev[b], hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); s.ev[b] = nullptr; BF_LEAVE(21); }
+		if (!blocking_event(s.ev[b])) BF_LEAVE(21);
 	}
-	s.fmt = format; s.min_baseq = min_baseq; s.d_out = fr.d_out; s.next_w = 0; s.cur = -1;
-	s.gen = R->gen;
+	s.fmt = format; s.min_baseq = min_baseq;
+	s.begin(fr.d_out, R->gen);
 	int rc = SK_OK;
 	if (reads_issue(c, s, 0, &rc)) s.cur = 0;
 	if (rc) return rc;
@@ -875,11 +921,9 @@ extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_
 	if (n_kept) *n_kept = K;
 	if (text_bytes) *text_bytes = T;
 	*handled = 1;
-	if (getenv("SK_BAMFILE_TRACE"))
-		fprintf(stderr, "sk_bam_file_reads: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, size + index + plan %.1f ms; %lld blocks, %llu by zlib; %lld kept, %llu text bytes, %lld windows\n",
-		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_size - fr.t_header, now_ms() - t_size,
-		        (long long)fr.nb, (unsigned long long)fr.n_host, (long long)K, (unsigned long long)T, (long long)(nw - 1));
-	front_info(fr, info);
+	char tail[128];
+	snprintf(tail, sizeof tail, "; %lld kept, %llu text bytes, %lld windows", (long long)K, (unsigned long long)T, (long long)s.ws.size() - 1);
+	file_call_close(fr, "size + index + plan", t_size, tail, info);
 	return SK_OK;
 }
 
@@ -888,7 +932,7 @@ extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
 	if (!c || !w) return SK_ERR_INVALID;
 	memset(w, 0, sizeof *w);
 	Ranges *R = (Ranges *)sk::ctx_ext(c);
-	if (!R || !R->reads.live || R->reads.gen != R->gen) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_reads_next: no sk_bam_file_reads in progress");
+	if (!R || !R->reads.current(R->gen)) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_reads_next: no sk_bam_file_reads in progress");
 	if (int r = sk::ctx_bind(c)) return r;
 	ReadsState &s = R->reads;
 	const int b = s.cur;
@@ -911,26 +955,6 @@ extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
 // complete members; only the members' bytes are copied back.  Every allocation that fails leaves the file to the caller's reader
 // (info[5] = -21).
 
-static const uint8_t kBgzfEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-// Header::from_template + Writer (htslib sam_hdr_write): the text up to its first NUL, trailing '\n's stripped and one appended when
-// anything is left; the reference list as read.  h: "BAM\1" .. the end of the reference list (checked by the front half).
-static std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h)
-{
-	const uint64_t l_text = le32(h.data() + 4);
-	const uint8_t *text = h.data() + 8;
-	uint64_t n = 0;
-	while (n < l_text && text[n] != 0) n++;
-	while (n > 0 && text[n - 1] == '\n') n--;
-	const uint64_t l_new = n ? n + 1 : 0;
-	std::vector<uint8_t> o(h.begin(), h.begin() + 4);
-	for (int k = 0; k < 4; k++) o.push_back((uint8_t)(l_new >> (8 * k)));
-	o.insert(o.end(), text, text + n);
-	if (n) o.push_back('\n');
-	o.insert(o.end(), h.begin() + 8 + (ptrdiff_t)l_text, h.end());
-	return o;
-}
-
 // the header (first) or window w of the plan (the next non-empty one) into packed buffer b: rewrite, cut, deflate, pack, and the packed
 // size back; false: nothing left
 static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
@@ -945,9 +969,8 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		raw_len = s.header.size();
 		e = hipMemcpyAsync(s.d_raw, s.header.data(), (size_t)raw_len, hipMemcpyHostToDevice, st);
 	} else {
-		while (s.next_w + 1 < s.ws.size() && s.ws[s.next_w + 1] == s.ws[s.next_w]) s.next_w++;
-		if (s.next_w + 1 >= s.ws.size()) return false;
-		const size_t w = s.next_w++;
+		size_t w;
+		if (!s.next_window(w)) return false;
 		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
 		raw_len = s.wo[w + 1] - s.wo[w];
 		e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st);
@@ -970,17 +993,16 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int level, uint64_t window_bytes, int64_t *n_records, uint64_t *raw_bytes,
                                    int *handled, double info[8])
 {
-	if (!c || !path || !handled) return SK_ERR_INVALID;
-	*handled = 0;
-	if (n_records) *n_records = 0;
-	if (raw_bytes) *raw_bytes = 0;
-	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
-	if (op < SK_REWRITE_TRIM_QNAMES || op > SK_REWRITE_TAGS_FROM_QNAME) return sk::ctx_fail(c, SK_ERR_INVALID, "op = %d", op);
-	if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
-	if (int r = sk::ctx_bind(c)) return r;
 	Cleanup cl;
 	Front fr;
-	if (int r = bam_file_front(c, path, "sk_bam_file_rewrite", cl, fr, info)) return r;
+	if (int r = file_call_open(c, path, "sk_bam_file_rewrite", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (op < SK_REWRITE_TRIM_QNAMES || op > SK_REWRITE_TAGS_FROM_QNAME) return sk::ctx_fail(c, SK_ERR_INVALID, "op = %d", op);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
 	if (!fr.ready) return SK_OK;
 	hipStream_t st = sk::ctx_stream(c);
 	const double t_size = now_ms();
@@ -1001,50 +1023,37 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 	BF_HIP(hipStreamSynchronize(st));
 	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_rewrite: declined (bits %#x)\n", decline);
 	if (decline) BF_LEAVE(30 + decline);                                // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
-	// ---- every record's stream and output offsets (ctx slot 9)
-	enum { kKeepRwCols = 9, kKeepRwWin = 10, kKeepRwPin = 11 };
+	// ---- every record's stream and output offsets
 	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
 	int krc = SK_OK;
-	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, kKeepRwCols, 2 * up(N * 8 + 8), false, &krc);
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * up(N * 8 + 8), false, &krc);
 	if (!kb) BF_LEAVE(21);
 	Ranges *R = (Ranges *)sk::ctx_ext(c);
 	RewriteState &s = R->rw;
 	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
 	{
-		std::vector<uint64_t> rb((size_t)nb + 1);
-		uint64_t run = 0;
-		for (int64_t i = 0; i < nb; i++) { rb[(size_t)i] = run; run += fr.nrec[(size_t)i]; }
-		if (run != N) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_rewrite: %llu records by the blocks' counts, %llu by the walk", (unsigned long long)run, (unsigned long long)N);
+		std::vector<uint64_t> rb;
+		if (int r = block_first_records(c, fr, rb)) return r;
 		if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
 		BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, d_rb, s.krec, s.kout, st));
 		BF_HIP(hipStreamSynchronize(st));                              // (rb is this scope's)
 	}
-	// ---- the windows: at most W rewritten bytes each (one record may go beyond)
-	uint64_t W = window_bytes ? window_bytes : (uint64_t)64 << 20;
-	W = std::min<uint64_t>(std::max<uint64_t>(W, 256), (uint64_t)1 << 30);
-	const int64_t nw = N ? (int64_t)(total / W + 2) : 1;
-	s.ws.assign((size_t)nw, N); s.wo.assign((size_t)nw, total);
-	if (N) {
-		uint64_t *d_w = nullptr;
-		if (hipMalloc((void **)&d_w, (size_t)nw * 16) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
-		cl.dev.push_back(d_w);
-		BF_HIP(sk::launch_bam_rw_windows(s.kout, (int64_t)N, W, total, d_w, d_w + nw, nw, st));
-		BF_HIP(hipMemcpyAsync(s.ws.data(), d_w, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
-		BF_HIP(hipMemcpyAsync(s.wo.data(), d_w + nw, (size_t)nw * 8, hipMemcpyDeviceToHost, st));
-		BF_HIP(hipStreamSynchronize(st));
-	}
-	s.header = rewrite_header(fr.header);
-	uint64_t max_raw = s.header.size();
-	for (int64_t w = 0; w + 1 < nw; w++) max_raw = std::max(max_raw, s.wo[(size_t)w + 1] - s.wo[(size_t)w]);
+	// ---- the windows: at most W rewritten bytes each
+	uint64_t mx[3];                                                     // records, rewritten bytes
+	bool room = true;
+	if (int r = plan_windows(c, cl, window_bytes, s.kout, nullptr, N, total, 0, s, s.wo, nullptr, mx, &room)) return r;
+	if (!room) BF_LEAVE(21);
+	s.header = bamfmt::rewrite_header(fr.header);
+	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
 	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
 	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
 	const uint64_t pack = max_raw + nblk * 31 + 64;
 	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
 	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
-	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, kKeepRwWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
 	if (!dw) BF_LEAVE(21);
 	const size_t p_pack = up(pack + 28);
-	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, kKeepRwPin, 2 * p_pack + 64, true, &krc);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * p_pack + 64, true, &krc);
 	if (!hw) BF_LEAVE(21);
 	s.d_raw = dw; s.d_blocks = dw + a_raw; s.d_result = (uint32_t *)(dw + a_raw + a_blk); s.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
 	s.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
@@ -1053,13 +1062,11 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 	s.d_slots = level ? dp + 2 * a_pack : nullptr;
 	s.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
 	s.h_pin[0] = hw; s.h_pin[1] = hw + p_pack; s.h_size = (uint64_t *)(hw + 2 * p_pack);
-	for (int b = 0; b < 2; b++) {
-		if (!s.ev[b] && hipEventCreateWithFlags(&s.ev[b], hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); s.ev[b] = nullptr; BF_LEAVE(21); }
-		if (!s.ev_copy[b] && hipEventCreateWithFlags(&s.ev_copy[b], hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); s.ev_copy[b] = nullptr; BF_LEAVE(21); }
-	}
+	for (int b = 0; b < 2; b++)
+		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
 	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
-	s.op = op; s.level = level; s.d_out = fr.d_out; s.next_w = 0; s.header_done = false; s.cur = -1;
-	s.gen = R->gen;
+	s.op = op; s.level = level; s.header_done = false;
+	s.begin(fr.d_out, R->gen);
 	int rc = SK_OK;
 	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
 	if (rc) return rc;
@@ -1067,11 +1074,9 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 	if (n_records) *n_records = (int64_t)N;
 	if (raw_bytes) *raw_bytes = s.header.size() + total;
 	*handled = 1;
-	if (getenv("SK_BAMFILE_TRACE"))
-		fprintf(stderr, "sk_bam_file_rewrite: alloc %.1f ms, read + copy + launches %.1f ms, wait for the inflate %.1f ms, host blocks + header %.1f ms, walk %.1f ms, size + index + plan %.1f ms; %lld blocks, %llu by zlib; %llu records, %llu rewritten bytes, %lld windows\n",
-		        fr.t_alloc - fr.t0, fr.t_read - fr.t_alloc, fr.t_inflated - fr.t_read, fr.t_header - fr.t_inflated, t_size - fr.t_header, now_ms() - t_size,
-		        (long long)fr.nb, (unsigned long long)fr.n_host, (unsigned long long)N, (unsigned long long)total, (long long)(nw - 1));
-	front_info(fr, info);
+	char tail[128];
+	snprintf(tail, sizeof tail, "; %llu records, %llu rewritten bytes, %lld windows", (unsigned long long)N, (unsigned long long)total, (long long)s.ws.size() - 1);
+	file_call_close(fr, "size + index + plan", t_size, tail, info);
 	return SK_OK;
 }
 
@@ -1080,7 +1085,7 @@ extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
 	if (!c || !w) return SK_ERR_INVALID;
 	memset(w, 0, sizeof *w);
 	Ranges *R = (Ranges *)sk::ctx_ext(c);
-	if (!R || !R->rw.live || R->rw.gen != R->gen) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_rewrite_next: no sk_bam_file_rewrite in progress");
+	if (!R || !R->rw.current(R->gen)) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_rewrite_next: no sk_bam_file_rewrite in progress");
 	if (int r = sk::ctx_bind(c)) return r;
 	RewriteState &s = R->rw;
 	const int b = s.cur;
@@ -1094,7 +1099,7 @@ extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
 	if (bytes) BF_HIP(hipMemcpyAsync(s.h_pin[b], s.d_pack[b], (size_t)bytes, hipMemcpyDeviceToHost, st2));
 	BF_HIP(hipEventRecord(s.ev_copy[b], st2));
 	BF_HIP(hipEventSynchronize(s.ev_copy[b]));
-	if (s.cur < 0) { memcpy(s.h_pin[b] + bytes, kBgzfEofBlock, 28); bytes += 28; }   // the last window ends with the EOF block
+	if (s.cur < 0) { memcpy(s.h_pin[b] + bytes, bamfmt::kBgzfEof, 28); bytes += 28; }   // the last window ends with the EOF block
 	w->first = s.first[b]; w->n = s.n[b];
 	w->bgzf = s.h_pin[b]; w->bytes = bytes; w->raw_bytes = s.raw[b];
 	return SK_OK;

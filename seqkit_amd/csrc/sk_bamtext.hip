@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/seqkit_hip.h"
+#include "sk_bamblock.h"
 #include "sk_internal.h"
 
 namespace sk {
@@ -255,14 +256,13 @@ __global__ __launch_bounds__(kScanThreads) void count_order_join_kernel(const Or
 }
 
 // ---- sam to raw|fasta|fastq: the reads of a verified BAM stream (sk_bam_file_reads) ------------------------------------------
-// bam_reads_size_kernel / bam_reads_index_kernel — a wave per BGZF block follows the chain from entry[c] (bam_gather_kernel's shape:
-// lane 0 leaves the records' offsets in LDS, then the lanes take consecutive records).  The first pass sums, per block, the kept
-// records, their text bytes and their name bytes, and ORs every record's decline bits; after the scans, the second pass writes the
-// kept records' columns at their kept index: stream offset, text offset, name offset, kind and qname key.
-// bam_reads_window_kernel — where each window of at most W text + name bytes begins.
+// bam_reads_size_kernel / bam_reads_index_kernel — a wave per BGZF block follows the chain from entry[c] (sk_bamblock.h: lane 0
+// leaves the records' offsets in LDS, then the lanes take consecutive records).  The first pass sums, per block, the kept records,
+// their text bytes and their name bytes, and ORs every record's decline bits; after the scans, the second pass writes the kept
+// records' columns at their kept index: stream offset, text offset, name offset, kind and qname key.
+// bam_window_kernel — where each window of at most W bytes begins (the reads' text + name bytes; sk_bamwrite.hip's rewritten bytes).
 // bam_reads_text_kernel — the text of one window: a 16-lane group owns a record and covers its output in consecutive dwords, each
 // composed by output address (the dwords it shares with its neighbours are written bytewise).
-constexpr int kReadsWaves = 4, kReadsRecs = 1824;                      // (a record that begins in a block takes >= 36 bytes of its 64 KiB)
 
 struct ReadsArgs {
 	const uint8_t *stream;
@@ -275,8 +275,6 @@ struct ReadsArgs {
 	uint8_t *kkind;
 };
 
-__device__ __forceinline__ uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 struct ReadRec { uint32_t kept, kind, tlen, nlen; };
 
 // the record at r: kept or not, its kind and text length (src/sam_to_fastq.rs:102,114-130,138-149); with `decline`, the reasons the
@@ -284,7 +282,7 @@ struct ReadRec { uint32_t kept, kind, tlen, nlen; };
 __device__ __forceinline__ ReadRec reads_rec(const uint8_t *r, int fmt, int want_unpaired, uint32_t *decline)
 {
 	ReadRec o{0u, 0u, 0u, 0u};
-	const uint32_t bs = rd32(r), w12 = rd32(r + 12), w16 = rd32(r + 16), S = rd32(r + 20);
+	const uint32_t bs = bam_le32_bytes(r), w12 = bam_le32_bytes(r + 12), w16 = bam_le32_bytes(r + 16), S = bam_le32_bytes(r + 20);
 	const uint32_t l_name = w12 & 0xffu, n_cigar = w16 & 0xffffu, f = w16 >> 16;
 	if (bs < 32u || l_name < 1u || S > 0x7fffffffu || 4ull * n_cigar + l_name + (((u64)S + 1) >> 1) + S > (u64)(bs - 32u)) {
 		if (decline) *decline |= 8u;                                       // htslib: "Invalid BAM record."
@@ -313,28 +311,14 @@ __device__ __forceinline__ ReadRec reads_rec(const uint8_t *r, int fmt, int want
 	return o;
 }
 
-__device__ __forceinline__ uint32_t reads_offsets(const ReadsArgs &a, int64_t c, uint16_t *off, int lane)
+__global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_size_kernel(const ReadsArgs a)
 {
-	uint32_t k = 0u;
-	if (lane == 0) {
-		const u64 entry = a.entry[c], end = a.bend[c];
-		for (u64 o = entry; o < end && k < (uint32_t)kReadsRecs; k++) {
-			off[k] = (uint16_t)(o - entry);
-			o += 4 + (u64)rd32(a.stream + o);
-		}
-	}
-	__builtin_amdgcn_wave_barrier();
-	return (uint32_t)__shfl((int)k, 0);
-}
-
-__global__ __launch_bounds__(kReadsWaves * 64) void bam_reads_size_kernel(const ReadsArgs a)
-{
-	__shared__ uint16_t offs[kReadsWaves][kReadsRecs];
+	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kReadsWaves + w;
+	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
 	if (c >= a.nb) return;                                                 // (no workgroup barrier below: each wave uses its own LDS)
 	uint16_t *off = offs[w];
-	const uint32_t n = reads_offsets(a, c, off, lane);
+	const uint32_t n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
 	const u64 entry = a.entry[c];
 	u64 kept = 0, tb = 0, nb = 0;
 	uint32_t dec = 0u;
@@ -361,23 +345,14 @@ __device__ __forceinline__ u64 qname_key(const uint8_t *p, uint32_t n)
 	return h;
 }
 
-__device__ __forceinline__ u64 wave_incl_scan(u64 x, int lane)
+__global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_index_kernel(const ReadsArgs a)
 {
-	for (int s = 1; s < 64; s <<= 1) {
-		const u64 y = __shfl_up(x, s);
-		if (lane >= s) x += y;
-	}
-	return x;
-}
-
-__global__ __launch_bounds__(kReadsWaves * 64) void bam_reads_index_kernel(const ReadsArgs a)
-{
-	__shared__ uint16_t offs[kReadsWaves][kReadsRecs];
+	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kReadsWaves + w;
+	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
 	if (c >= a.nb) return;
 	uint16_t *off = offs[w];
-	const uint32_t n = reads_offsets(a, c, off, lane);
+	const uint32_t n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
 	const u64 entry = a.entry[c];
 	u64 kb = a.bk[c], tb = a.bt[c], nb = a.bn[c];                       // where the block's first kept record goes
 	for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
@@ -398,18 +373,18 @@ __global__ __launch_bounds__(kReadsWaves * 64) void bam_reads_index_kernel(const
 	}
 }
 
-// window w = the kept records whose text + name offset lies in [w W, (w + 1) W): ws[w] its first record, wt[w] / wn[w] its first text /
-// name byte; entries past the last record's window hold (n, total text, total names).  nw entries in all.
-__global__ __launch_bounds__(256) void bam_reads_window_kernel(const u64 *ktoff, const u64 *knoff, int64_t n, u64 W, u64 total_t, u64 total_n,
-                                                               u64 *ws, u64 *wt, u64 *wn, int64_t nw)
+// window w = the records whose key off0[j] + off1[j] (off1 == nullptr: off0[j]) lies in [w W, (w + 1) W): ws[w] its first record, w0[w]
+// / w1[w] its off0 / off1; entries past the last record's window hold (n, total0, total1).  nw entries in all.
+__global__ __launch_bounds__(256) void bam_window_kernel(const u64 *off0, const u64 *off1, int64_t n, u64 W, u64 total0, u64 total1, u64 *ws, u64 *w0,
+                                                         u64 *w1, int64_t nw)
 {
 	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= n) return;
-	const u64 cur = (ktoff[j] + knoff[j]) / W;
-	const u64 from = j ? (ktoff[j - 1] + knoff[j - 1]) / W + 1 : 0;
-	for (u64 v = from; v <= cur && (int64_t)v < nw; v++) { ws[v] = (u64)j; wt[v] = ktoff[j]; wn[v] = knoff[j]; }
+	const u64 cur = (off0[j] + (off1 ? off1[j] : 0)) / W;
+	const u64 from = j ? (off0[j - 1] + (off1 ? off1[j - 1] : 0)) / W + 1 : 0;
+	for (u64 v = from; v <= cur && (int64_t)v < nw; v++) { ws[v] = (u64)j; w0[v] = off0[j]; if (off1) w1[v] = off1[j]; }
 	if (j == n - 1)
-		for (int64_t v = (int64_t)cur + 1; v < nw; v++) { ws[v] = (u64)n; wt[v] = total_t; wn[v] = total_n; }
+		for (int64_t v = (int64_t)cur + 1; v < nw; v++) { ws[v] = (u64)n; w0[v] = total0; if (off1) w1[v] = total1; }
 }
 
 struct ReadsText {
@@ -459,7 +434,7 @@ __global__ __launch_bounds__(kTextThreads) void bam_reads_text_kernel(const Read
 	for (int64_t j = ((int64_t)blockIdx.x * kTextThreads + threadIdx.x) >> 4; j < a.n; j += gstride) {
 		const int64_t k = a.first + j;
 		const uint8_t *r = a.stream + a.krec[k];
-		const uint32_t w12 = rd32(r + 12), w16 = rd32(r + 16), S = rd32(r + 20);
+		const uint32_t w12 = bam_le32_bytes(r + 12), w16 = bam_le32_bytes(r + 16), S = bam_le32_bytes(r + 20);
 		const uint32_t l_name = w12 & 0xffu, n_cigar = w16 & 0xffffu, L = l_name - 1u;
 		const bool rev = (w16 >> 16) & 0x10u;
 		const uint8_t *name = r + 36, *seq4 = name + l_name + 4u * n_cigar, *qual = seq4 + ((S + 1u) >> 1);
@@ -523,7 +498,6 @@ extern "C" int sk_bam_fragments_bed_dev(sk_ctx *c, const uint8_t *keep_bits, con
 	if (n_ref > 0 && name_off[0] != 0) return sk::ctx_fail(c, SK_ERR_INVALID, "name_off[0] must be 0");
 	for (int32_t r = 0; r < n_ref; r++) if (name_off[r + 1] < name_off[r]) return sk::ctx_fail(c, SK_ERR_INVALID, "name_off must not decrease");
 	if (int r = sk::ctx_bind(c)) return r;
-	enum { kKeepTextPin = 7, kKeepText = 8 };
 	hipStream_t st = sk::ctx_stream(c);
 	DevTmp tmp;
 	tmp.st = st;
@@ -554,9 +528,9 @@ extern "C" int sk_bam_fragments_bed_dev(sk_ctx *c, const uint8_t *keep_bits, con
 	BT_HIP(c, hipStreamSynchronize(st));
 	const uint64_t total = hb[0];
 	int krc = SK_OK;
-	uint8_t *d_text = (uint8_t *)sk::ctx_keep(c, kKeepText, (size_t)total + 16, false, &krc);
+	uint8_t *d_text = (uint8_t *)sk::ctx_keep(c, sk::kKeepText, (size_t)total + 16, false, &krc);
 	if (!d_text) return krc;
-	uint8_t *h_text = (uint8_t *)sk::ctx_keep(c, kKeepTextPin, (size_t)total + 16, true, &krc);
+	uint8_t *h_text = (uint8_t *)sk::ctx_keep(c, sk::kKeepTextPin, (size_t)total + 16, true, &krc);
 	if (!h_text) return krc;
 	a.text = d_text;
 	if (tiles > 0) {
@@ -608,7 +582,7 @@ extern "C" int sk_count_order_check_dev(sk_ctx *c, const uint16_t *flag, const u
 	return SK_OK;
 }
 
-// ---- launchers of the reads passes (sk_bamfile.cpp: sk_bam_file_reads) ---------------------------------------------------------
+// ---- launchers of the reads passes and the window plan (sk_bamfile.cpp: sk_bam_file_reads, sk_bam_file_rewrite) ------------------
 namespace sk {
 hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
                                  uint64_t *bk, uint64_t *bt, uint64_t *bn, uint32_t *decline, hipStream_t st)
@@ -617,7 +591,7 @@ hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, co
 	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.fmt = fmt; a.want_unpaired = want_unpaired;
 	a.bk = (u64 *)bk; a.bt = (u64 *)bt; a.bn = (u64 *)bn; a.decline = decline;
 	if (nb > 0) {
-		bam_reads_size_kernel<<<(unsigned)((nb + kReadsWaves - 1) / kReadsWaves), kReadsWaves * 64, 0, st>>>(a);
+		bam_reads_size_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
 		if (hipError_t e = hipGetLastError()) return e;
 	}
 	for (u64 *v : {a.bk, a.bt, a.bn}) {
@@ -643,16 +617,16 @@ hipError_t launch_bam_reads_index(const uint8_t *stream, const uint64_t *bend, c
 	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.fmt = fmt; a.want_unpaired = want_unpaired;
 	a.bk = (u64 *)bk; a.bt = (u64 *)bt; a.bn = (u64 *)bn;
 	a.krec = (u64 *)krec; a.ktoff = (u64 *)ktoff; a.knoff = (u64 *)knoff; a.kkey = (u64 *)kkey; a.kkind = kkind;
-	bam_reads_index_kernel<<<(unsigned)((nb + kReadsWaves - 1) / kReadsWaves), kReadsWaves * 64, 0, st>>>(a);
+	bam_reads_index_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
 	return hipGetLastError();
 }
 
-hipError_t launch_bam_reads_windows(const uint64_t *ktoff, const uint64_t *knoff, int64_t n, uint64_t W, uint64_t total_t, uint64_t total_n,
-                                    uint64_t *ws, uint64_t *wt, uint64_t *wn, int64_t nw, hipStream_t st)
+hipError_t launch_bam_windows(const uint64_t *off0, const uint64_t *off1, int64_t n, uint64_t W, uint64_t total0, uint64_t total1, uint64_t *ws,
+                              uint64_t *w0, uint64_t *w1, int64_t nw, hipStream_t st)
 {
 	if (n <= 0) return hipSuccess;
-	bam_reads_window_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((const u64 *)ktoff, (const u64 *)knoff, n, W, total_t, total_n,
-	                                                                      (u64 *)ws, (u64 *)wt, (u64 *)wn, nw);
+	bam_window_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((const u64 *)off0, (const u64 *)off1, n, W, total0, total1, (u64 *)ws, (u64 *)w0,
+	                                                                (u64 *)w1, nw);
 	return hipGetLastError();
 }
 

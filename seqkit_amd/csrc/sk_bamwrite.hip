@@ -1,14 +1,14 @@
 // sk_bamwrite.hip — the BAM-out half of sk_bam_file_rewrite (include/seqkit_hip.h): the per-record rewrite of `sam trim qnames`,
 // `sam tags from qname` and `sam qname from tags` over a verified BAM stream, and the packing of deflated blocks into BGZF members.
 //
-// bam_rw_size_kernel / bam_rw_index_kernel — a wave per BGZF block follows the chain from entry[c] (bam_reads_size_kernel's shape:
-// lane 0 leaves the records' offsets in LDS, then the lanes take consecutive records).  rw_plan reads one record and says what the
+// bam_rw_size_kernel / bam_rw_index_kernel — a wave per BGZF block follows the chain from entry[c] (sk_bamblock.h: lane 0 leaves the
+// records' offsets in LDS, then the lanes take consecutive records).  rw_plan reads one record and says what the
 // command makes of it: unchanged, or a new name (a prefix of the old one, followed by " RX:" + the RX value for qname from tags) and
 // appended Z fields (tags from qname).  The first pass sums the rewritten bytes per block and ORs the decline bits: every record the
 // reference would end on (src/sam_trim_qnames.rs:23 qname[trim - 2]; src/sam_tags_from_qname.rs:46 error!; set_qname's 254-byte
 // limit), and, for qname from tags, aux data that do not parse to the record's end.  After the scan, the second pass writes every
 // record's stream offset and output offset.
-// bam_rw_window_kernel — where each window of at most W rewritten bytes begins.
+// (where each window of at most W rewritten bytes begins: sk_bamtext.hip's bam_window_kernel)
 // bam_rw_write_kernel — one window's records: a 16-lane group owns a record and covers its output in consecutive dwords.  A dword
 // that lies inside one of the record's copied spans (the core and the kept name; CIGAR, bases, qualities and aux) is built from two
 // aligned loads with a funnel shift (v_alignbyte) and stored whole; the rest — the block_size and l_read_name bytes, the spans' edges,
@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "../../include/seqkit_hip.h"
+#include "sk_bamblock.h"
 #include "sk_internal.h"
 
 namespace sk {
@@ -31,21 +32,8 @@ namespace {
 typedef uint32_t u32;
 typedef unsigned long long u64;
 
-constexpr int kRwWaves = 4, kRwRecs = 1824;       // (a record that begins in a block takes >= 36 bytes of its 64 KiB)
 constexpr int kRwThreads = 256;                   // write kernel: 16 groups of 16 lanes
 constexpr u32 kMaxIn = 0xff00u;
-
-__device__ __forceinline__ u32 rd32(const uint8_t *p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); }
-
-// four bytes at any alignment from two aligned loads (the buffer is readable to the next dword behind its last byte)
-__device__ __forceinline__ u32 load4(const uint8_t *p)
-{
-	const uintptr_t a = (uintptr_t)p;
-	const u32 *q = reinterpret_cast<const u32 *>(a & ~(uintptr_t)3);
-	const u32 sh = (u32)(a & 3u);
-	const u32 lo = q[0];
-	return sh == 0u ? lo : __builtin_amdgcn_alignbyte(q[1], lo, sh);
-}
 
 // What a command makes of one record.  Output layout of a changed record: block_size, the core (l_read_name new), the first P bytes of
 // the old name, X bytes (NUL, or " RX:" value NUL), the old record from the end of the name on (tail_len bytes: CIGAR .. aux), then
@@ -58,7 +46,7 @@ struct RwPlan {
 
 __device__ __forceinline__ u32 rw_plan(const uint8_t *r, int op, RwPlan &pl)
 {
-	const u32 bs = rd32(r), w12 = rd32(r + 12), w16 = rd32(r + 16), S = rd32(r + 20);
+	const u32 bs = bam_le32_bytes(r), w12 = bam_le32_bytes(r + 12), w16 = bam_le32_bytes(r + 16), S = bam_le32_bytes(r + 20);
 	const u32 lo = w12 & 0xffu, nc = w16 & 0xffffu;
 	pl.same = 1u; pl.P = 0u; pl.X = 0u; pl.voff = 0u; pl.vl = 0u; pl.sp = 0u; pl.tail_s = 0u; pl.tail_len = 0u; pl.alen = 0u;
 	pl.out_len = 4u + bs;
@@ -107,7 +95,7 @@ __device__ __forceinline__ u32 rw_plan(const uint8_t *r, int op, RwPlan &pl)
 				a++;
 			} else if (ty == 'B') {
 				if (a + 5u > end) return 16u;
-				const u32 sub = r[a], cnt = rd32(r + a + 1);
+				const u32 sub = r[a], cnt = bam_le32_bytes(r + a + 1);
 				const u32 es = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : (sub == 'i' || sub == 'I' || sub == 'f') ? 4u : 0u;
 				if (!es) return 16u;
 				a += 5ull + (u64)cnt * es;
@@ -174,8 +162,8 @@ __device__ __forceinline__ void emit(uint8_t *out, u64 o0, u64 len, u32 ro0, u32
 		if (a >= o0 && a + 4 <= e) {
 			const u32 p = (u32)(a - o0);
 			u32 v;
-			if (p >= ro0 && p + 4u <= ro0 + rl0) v = load4(src0 + (p - ro0));
-			else if (p >= ro1 && p + 4u <= ro1 + rl1) v = load4(src1 + (p - ro1));
+			if (p >= ro0 && p + 4u <= ro0 + rl0) v = bam_le32(src0 + (p - ro0));
+			else if (p >= ro1 && p + 4u <= ro1 + rl1) v = bam_le32(src1 + (p - ro1));
 			else v = byte(p) | (byte(p + 1u) << 8) | (byte(p + 2u) << 16) | (byte(p + 3u) << 24);
 			*reinterpret_cast<u32 *>(out + a) = v;
 		} else {
@@ -198,28 +186,14 @@ struct RwArgs {
 	u64 *krec, *kout;
 };
 
-__device__ __forceinline__ u32 rw_offsets(const RwArgs &a, int64_t c, uint16_t *off, int lane)
+__global__ __launch_bounds__(kBlockWaves * 64) void bam_rw_size_kernel(const RwArgs a)
 {
-	u32 k = 0u;
-	if (lane == 0) {
-		const u64 entry = a.entry[c], end = a.bend[c];
-		for (u64 o = entry; o < end && k < (u32)kRwRecs; k++) {
-			off[k] = (uint16_t)(o - entry);
-			o += 4 + (u64)rd32(a.stream + o);
-		}
-	}
-	__builtin_amdgcn_wave_barrier();
-	return (u32)__shfl((int)k, 0);
-}
-
-__global__ __launch_bounds__(kRwWaves * 64) void bam_rw_size_kernel(const RwArgs a)
-{
-	__shared__ uint16_t offs[kRwWaves][kRwRecs];
+	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kRwWaves + w;
+	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
 	if (c >= a.nb) return;                                                 // (no workgroup barrier below: each wave uses its own LDS)
 	uint16_t *off = offs[w];
-	const u32 n = rw_offsets(a, c, off, lane);
+	const u32 n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
 	const u64 entry = a.entry[c];
 	u64 bytes = 0;
 	u32 dec = 0u;
@@ -238,23 +212,14 @@ __global__ __launch_bounds__(kRwWaves * 64) void bam_rw_size_kernel(const RwArgs
 	}
 }
 
-__device__ __forceinline__ u64 wave_incl_scan(u64 x, int lane)
+__global__ __launch_bounds__(kBlockWaves * 64) void bam_rw_index_kernel(const RwArgs a)
 {
-	for (int s = 1; s < 64; s <<= 1) {
-		const u64 y = __shfl_up(x, s);
-		if (lane >= s) x += y;
-	}
-	return x;
-}
-
-__global__ __launch_bounds__(kRwWaves * 64) void bam_rw_index_kernel(const RwArgs a)
-{
-	__shared__ uint16_t offs[kRwWaves][kRwRecs];
+	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kRwWaves + w;
+	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
 	if (c >= a.nb) return;
 	uint16_t *off = offs[w];
-	const u32 n = rw_offsets(a, c, off, lane);
+	const u32 n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
 	const u64 entry = a.entry[c];
 	u64 k0 = a.rb[c], ob = a.bo[c];                                        // the block's first record and where its output begins
 	for (u32 j0 = 0; j0 < n; j0 += 64u) {
@@ -265,19 +230,6 @@ __global__ __launch_bounds__(kRwWaves * 64) void bam_rw_index_kernel(const RwArg
 		if (j < n) { a.krec[k0 + j] = entry + off[j]; a.kout[k0 + j] = ob + il - len; }
 		ob += __shfl(il, 63);
 	}
-}
-
-// window w = the records whose output offset lies in [w W, (w + 1) W): ws[w] its first record, wo[w] its first output byte; entries
-// past the last record's window hold (n, total).  nw entries in all.
-__global__ __launch_bounds__(256) void bam_rw_window_kernel(const u64 *kout, int64_t n, u64 W, u64 total, u64 *ws, u64 *wo, int64_t nw)
-{
-	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= n) return;
-	const u64 cur = kout[j] / W;
-	const u64 from = j ? kout[j - 1] / W + 1 : 0;
-	for (u64 v = from; v <= cur && (int64_t)v < nw; v++) { ws[v] = (u64)j; wo[v] = kout[j]; }
-	if (j == n - 1)
-		for (int64_t v = (int64_t)cur + 1; v < nw; v++) { ws[v] = (u64)n; wo[v] = total; }
 }
 
 __global__ __launch_bounds__(kRwThreads) void bam_rw_write_kernel(const uint8_t *stream, const u64 *krec, const u64 *kout, int64_t first, int64_t n,
@@ -362,7 +314,7 @@ hipError_t launch_bam_rw_size(const uint8_t *stream, const uint64_t *bend, const
 	RwArgs a{};
 	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.op = op; a.bo = (u64 *)bo; a.decline = decline;
 	if (nb > 0) {
-		bam_rw_size_kernel<<<(unsigned)((nb + kRwWaves - 1) / kRwWaves), kRwWaves * 64, 0, st>>>(a);
+		bam_rw_size_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
 		if (hipError_t e = hipGetLastError()) return e;
 	}
 	return launch_scan_u64(bo, nb, st);
@@ -375,14 +327,7 @@ hipError_t launch_bam_rw_index(const uint8_t *stream, const uint64_t *bend, cons
 	RwArgs a{};
 	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.op = op; a.bo = (u64 *)bo; a.rb = (const u64 *)rb;
 	a.krec = (u64 *)krec; a.kout = (u64 *)kout;
-	bam_rw_index_kernel<<<(unsigned)((nb + kRwWaves - 1) / kRwWaves), kRwWaves * 64, 0, st>>>(a);
-	return hipGetLastError();
-}
-
-hipError_t launch_bam_rw_windows(const uint64_t *kout, int64_t n, uint64_t W, uint64_t total, uint64_t *ws, uint64_t *wo, int64_t nw, hipStream_t st)
-{
-	if (n <= 0) return hipSuccess;
-	bam_rw_window_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((const u64 *)kout, n, W, total, (u64 *)ws, (u64 *)wo, nw);
+	bam_rw_index_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
 	return hipGetLastError();
 }
 

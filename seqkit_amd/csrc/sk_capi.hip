@@ -58,9 +58,8 @@ struct sk_ctx {
 	int many_no_stride = 0, many_no_detail = -1;
 	uint8_t *pin = nullptr;            // a pinned landing area (sk_bgzf_deflate: the compressed slots come back here)
 	size_t pin_bytes = 0;
-	// buffers that stay with the ctx from one call to the next (sk::ctx_keep: 0-5 the file calls' device and pinned buffers, 6 the columns
-	// of sk_bam_file_columns, 7-8 the text of sk_bam_fragments_bed_dev)
-	struct Kept { void *p = nullptr; size_t cap = 0; bool pinned = false; } kept[12];
+	// buffers that stay with the ctx from one call to the next (sk::ctx_keep; sk_internal.h: sk::KeepSlot)
+	struct Kept { void *p = nullptr; size_t cap = 0; bool pinned = false; } kept[sk::kKeepSlots];
 	void *ext = nullptr;               // an object another translation unit keeps with the ctx (sk_bamfile.cpp: its mapped output range), and how to free it
 	void (*ext_free)(void *) = nullptr;
 	sk::Census *census = nullptr;
@@ -122,9 +121,9 @@ namespace sk {
 hipStream_t ctx_stream(sk_ctx *c) { return c->stream; }
 hipStream_t ctx_stream2(sk_ctx *c) { return c->stream2; }
 int ctx_n_cu(sk_ctx *c) { return c->n_cu; }
-// a buffer of at least `bytes` that stays with the ctx (slot 0..11; device memory or page-locked host memory); its contents are not kept
-// when it has to grow.  nullptr + an error code in *rc when the allocation fails (the slot is then empty).
-void *ctx_keep(sk_ctx *c, int slot, size_t bytes, bool pinned, int *rc)
+// a buffer of at least `bytes` that stays with the ctx (device memory or page-locked host memory); its contents are not kept when it
+// has to grow.  nullptr + an error code in *rc when the allocation fails (the slot is then empty).
+void *ctx_keep(sk_ctx *c, KeepSlot slot, size_t bytes, bool pinned, int *rc)
 {
 	*rc = SK_OK;
 	auto &k = c->kept[slot];
@@ -136,7 +135,7 @@ void *ctx_keep(sk_ctx *c, int slot, size_t bytes, bool pinned, int *rc)
 	k.p = p; k.cap = bytes; k.pinned = pinned;
 	return p;
 }
-size_t ctx_kept_bytes(sk_ctx *c, int slot) { return c->kept[slot].p ? c->kept[slot].cap : 0; }
+size_t ctx_kept_bytes(sk_ctx *c, KeepSlot slot) { return c->kept[slot].p ? c->kept[slot].cap : 0; }
 void *ctx_ext(sk_ctx *c) { return c->ext; }
 void ctx_set_ext(sk_ctx *c, void *p, void (*free_fn)(void *)) { c->ext = p; c->ext_free = free_fn; }
 int ctx_bind(sk_ctx *c) { return bind(c); }

@@ -55,6 +55,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "sk_bamblock.h"
 #include "sk_internal.h"
 
 namespace sk {
@@ -1177,17 +1178,6 @@ __global__ __launch_bounds__(256) void bgzf_crc_kernel(const uint8_t *out, const
 }
 
 // ---- the records of the inflated stream ----------------------------------------------------------------------------
-__device__ __forceinline__ u32 bam_le32(const uint8_t *p)
-{
-	// (any alignment: two aligned dwords and a byte shift)
-	const uintptr_t a = (uintptr_t)p;
-	const u32 *q = reinterpret_cast<const u32 *>(a & ~(uintptr_t)3);
-	const u32 sh = (u32)(a & 3u);
-	const u32 lo = q[0];
-	if (sh == 0u) return lo;
-	return __builtin_amdgcn_alignbyte(q[1], lo, sh);
-}
-
 // Walk block c from entry[c] (a position of the stream) to the first record that begins at or behind the block's end
 // (bend[c] = where block c + 1 begins): exitp[c] = that position, nrec[c] = records begun inside.  A record whose block_size
 // no record can have (< 32) or that reaches beyond the stream ends the walk with exitp = ~0 - (1 or 2): the caller's CPU path
@@ -1348,37 +1338,29 @@ __global__ __launch_bounds__(256) void bam_walk_reduce_kernel(const WalkArgs a, 
 }
 
 // The fixed-core fields of every record of a verified chain, in file order, into SoA columns (sk_bam_file_columns).  A wave per
-// BGZF block: lane 0 follows the chain from entry[c] to the block's end and leaves every record's offset in LDS (a record begins
-// inside the block and takes at least 36 bytes: at most 65536 / 36 + 1 of them), then the 64 lanes take consecutive records and
-// store each column coalesced.  rec_base[c] = index of block c's first record (exclusive prefix of the walk's counts).
+// BGZF block: lane 0 follows the chain from entry[c] to the block's end and leaves every record's offset in LDS (sk_bamblock.h:
+// block_record_offsets), then the 64 lanes take consecutive records and store each column coalesced.  rec_base[c] = index of block c's first record (exclusive prefix of the walk's counts).
 // end_pos is BamStream::next(..., want_end)'s (sam_main.cpp): pos plus the lengths of the ops M D N = X (0 2 3 7 8), summed in
 // 64 bits and truncated; pos itself when the variable part is shorter than the read name and the CIGAR.
-constexpr int kGatherWaves = 4, kGatherRecs = 1824;
 struct GatherCols {
 	uint16_t *flag;
 	uint8_t *mapq;
 	int32_t *tid, *mtid, *pos, *mpos, *tlen, *end_pos;
 };
-__global__ __launch_bounds__(kGatherWaves * 64) void bam_gather_kernel(const WalkArgs a, const u64 *rec_base, GatherCols g)
+__global__ __launch_bounds__(kBlockWaves * 64) void bam_gather_kernel(const WalkArgs a, const u64 *rec_base, GatherCols g)
 {
-	__shared__ uint16_t offs[kGatherWaves][kGatherRecs];                // (a record that begins in the block begins < 65536 bytes behind its entry)
+	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kGatherWaves + w;
+	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
 	const bool live = c < a.n;
 	const u64 entry = live ? a.entry[c] : 0ull, end = live ? a.bend[c] : 0ull;
 	uint16_t *off = offs[w];
-	if (live && lane == 0) {
-		u32 k = 0u;
-		for (u64 o = entry; o < end && k < (u32)kGatherRecs; k++) {
-			off[k] = (uint16_t)(o - entry);
-			o += 4 + (u64)bam_le32(a.stream + o);
-		}
-	}
-	__syncthreads();
+	if (live && lane == 0) (void)block_record_offsets(a.stream, entry, end, off);
+	__syncthreads();                                                       // (every wave of the workgroup, the ones past the last block too)
 	if (!live) return;
 	const u64 base = rec_base[c];
 	const u32 n = (u32)(rec_base[c + 1] - base);
-	for (u32 j = (u32)lane; j < n && j < (u32)kGatherRecs; j += 64u) {
+	for (u32 j = (u32)lane; j < n && j < (u32)kBlockRecs; j += 64u) {
 		const uint8_t *r = a.stream + entry + off[j];
 		const int64_t i = (int64_t)(base + j);
 		const int32_t p = (int32_t)bam_le32(r + 8);
@@ -1463,7 +1445,7 @@ hipError_t launch_bam_gather(const uint8_t *stream, uint64_t stream_len, const u
 	a.stream = stream; a.stream_len = stream_len; a.bend = reinterpret_cast<const u64 *>(bend); a.entry = const_cast<u64 *>(reinterpret_cast<const u64 *>(entry));
 	a.exitp = nullptr; a.nrec = nullptr; a.n = n; a.first = 0; a.changed = nullptr;
 	GatherCols g{flag, mapq, tid, mtid, pos, mpos, tlen, end_pos};
-	bam_gather_kernel<<<(unsigned)((n + kGatherWaves - 1) / kGatherWaves), kGatherWaves * 64, 0, st>>>(a, reinterpret_cast<const u64 *>(rec_base), g);
+	bam_gather_kernel<<<(unsigned)((n + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a, reinterpret_cast<const u64 *>(rec_base), g);
 	return hipGetLastError();
 }
 

@@ -167,14 +167,12 @@ hipError_t launch_bam_gather(const uint8_t *stream, uint64_t stream_len, const u
                              uint16_t *flag, uint8_t *mapq, int32_t *tid, int32_t *mtid, int32_t *pos, int32_t *mpos, int32_t *tlen, int32_t *end_pos,
                              hipStream_t st);
 // sam to raw|fasta|fastq over a verified stream (sk_bamtext.hip): the sizing pass + the scans of its per-block sums, the kept records'
-// columns, the windows, and one window's text
+// columns, and one window's text
 hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
                                  uint64_t *bk, uint64_t *bt, uint64_t *bn, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_reads_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
                                   const uint64_t *bk, const uint64_t *bt, const uint64_t *bn, uint64_t *krec, uint64_t *ktoff, uint64_t *knoff,
                                   uint64_t *kkey, uint8_t *kkind, hipStream_t st);
-hipError_t launch_bam_reads_windows(const uint64_t *ktoff, const uint64_t *knoff, int64_t n, uint64_t W, uint64_t total_t, uint64_t total_n,
-                                    uint64_t *ws, uint64_t *wt, uint64_t *wn, int64_t nw, hipStream_t st);
 hipError_t launch_bam_reads_text(const uint8_t *stream, const uint64_t *krec, const uint64_t *ktoff, const uint64_t *knoff, int64_t first, int64_t n,
                                  uint64_t t0, uint64_t n0, int fmt, uint8_t min_baseq, uint8_t *text, uint64_t *toff, uint8_t *names, uint32_t *noff,
                                  int n_cu, hipStream_t st);
@@ -188,15 +186,19 @@ size_t deflate_tokens_per_block();
 hipError_t launch_bgzf_crc(const uint8_t *in, const void *blocks, int64_t n_blocks, uint32_t *crc, int n_cu, hipStream_t st);
 
 hipError_t launch_scan_u64(uint64_t *v, int64_t n, hipStream_t st);     // sk_bamtext.hip: v[0 .. n) -> exclusive offsets, v[n] the sum
+// the window plan of sk_bam_file_reads and sk_bam_file_rewrite (sk_bamtext.hip): window w holds the records whose key off0[j] + off1[j]
+// (off1 == nullptr: off0[j]) lies in [w W, (w + 1) W); ws[w] = its first record, w0[w] / w1[w] = that record's off0 / off1 (w1 only with
+// off1).  The entries past the last record's window hold (n, total0, total1).  nw entries in all.
+hipError_t launch_bam_windows(const uint64_t *off0, const uint64_t *off1, int64_t n, uint64_t W, uint64_t total0, uint64_t total1, uint64_t *ws,
+                              uint64_t *w0, uint64_t *w1, int64_t nw, hipStream_t st);
 // ---- BAM out: the per-record rewrite of sk_bam_file_rewrite and the BGZF member packing (sk_bamwrite.hip) ----
 // size: per block the rewritten bytes of the records that begin in it (then exclusive offsets, bo[nb] the total) and the OR of the
-// records' decline bits; index: every record's stream offset and output offset (rb: the blocks' first record indices);
-// windows: where each window of at most W rewritten bytes begins; write: records first .. first + n - 1 into out (out offset o0 at 0)
+// records' decline bits; index: every record's stream offset and output offset (rb: the blocks' first record indices); write: records
+// first .. first + n - 1 into out (out offset o0 at 0)
 hipError_t launch_bam_rw_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int op, uint64_t *bo, uint32_t *decline,
                               hipStream_t st);
 hipError_t launch_bam_rw_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int op, const uint64_t *bo,
                                const uint64_t *rb, uint64_t *krec, uint64_t *kout, hipStream_t st);
-hipError_t launch_bam_rw_windows(const uint64_t *kout, int64_t n, uint64_t W, uint64_t total, uint64_t *ws, uint64_t *wo, int64_t nw, hipStream_t st);
 hipError_t launch_bam_rw_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, int op,
                                uint8_t *out, int n_cu, hipStream_t st);
 // BGZF members of raw[0 .. raw_len): the cut into blocks of at most 0xff00 bytes (blocks: device sk_deflate_block[n]), and, after the
@@ -228,11 +230,21 @@ constexpr int kMaxCensusLen = 31;
 // ---- what sk_bamfile.cpp needs of a ctx (sk_capi.hip owns the struct) ----
 struct sk_ctx;
 namespace sk {
+// The buffers that stay with a ctx from call to call (ctx_keep).  The file calls' front half (sk_bamfile.cpp: bam_file_front) keeps the
+// compressed file, the inflated stream, the reader ring, the block table and its device copy and the blocks' status.  The reads and
+// rewrite calls share their three slots: only one file call's state is live on a ctx (the next file call ends the one before).
+enum KeepSlot {
+	kKeepComp = 0, kKeepOut = 1, kKeepPin = 2, kKeepTable = 3, kKeepBlocks = 4, kKeepStatus = 5,   // the front half
+	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
+	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
+	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / sk_bam_file_rewrite: per-record columns, windows
+	kKeepSlots = 12
+};
 hipStream_t ctx_stream(sk_ctx *c);
 hipStream_t ctx_stream2(sk_ctx *c);
 int ctx_n_cu(sk_ctx *c);
-void *ctx_keep(sk_ctx *c, int slot, size_t bytes, bool pinned, int *rc);      // a buffer that stays with the ctx from call to call, slot 0..11 (freed by sk_destroy)
-size_t ctx_kept_bytes(sk_ctx *c, int slot);
+void *ctx_keep(sk_ctx *c, KeepSlot slot, size_t bytes, bool pinned, int *rc);      // a buffer that stays with the ctx from call to call (freed by sk_destroy)
+size_t ctx_kept_bytes(sk_ctx *c, KeepSlot slot);
 void *ctx_ext(sk_ctx *c);                                       // an object kept with the ctx (freed by sk_destroy through free_fn)
 void ctx_set_ext(sk_ctx *c, void *p, void (*free_fn)(void *));
 int ctx_bind(sk_ctx *c);                                        // hipSetDevice; SK_OK or an error code with the message set
