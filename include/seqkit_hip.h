@@ -420,7 +420,7 @@ int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
  * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
  * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
  * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
- * sk_bam_file_rewrite: SK_ERR_INVALID.                                                                                          */
+ * sk_bam_file_rewrite (or sk_bam_file_minimize, below, whose windows it hands out too): SK_ERR_INVALID.                         */
 #define SK_REWRITE_TRIM_QNAMES     1
 #define SK_REWRITE_QNAME_FROM_TAGS 2
 #define SK_REWRITE_TAGS_FROM_QNAME 3
@@ -432,6 +432,27 @@ typedef struct sk_bam_out_window {
 int sk_bam_file_rewrite(sk_ctx *ctx, const char *path, int op, int level /* 0 stored, 1 deflate */, uint64_t window_bytes /* 0 = default */,
                         int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
 int sk_bam_file_rewrite_next(sk_ctx *ctx, sk_bam_out_window *w);
+
+/* ---- BAM out for `sam minimize` (src/sam_minimize.rs:46-82) -----------------------------------------------------------------
+ * sk_bam_file_minimize: sk_bam_file_rewrite's front half, window pipeline and header, with the record rewrite of `sam minimize`.
+ * flags: SK_MINIMIZE_READ_IDS | SK_MINIMIZE_BASE_QUALITIES | SK_MINIMIZE_TAGS.  READ_IDS: a read's key is its qname up to the first
+ * '/' (a '/' at index 0: the empty key); in file order the 1st, 3rd, 5th .. record of a key takes the next unused number, starting
+ * at 1, and the 2nd, 4th .. takes the number of the record of that key just before it (the reference's map, whose entry is removed
+ * when the mate arrives); the new name is that number in decimal.  READ_IDS alone: the name, l_read_name and block_size change and
+ * every other byte stays, aux data included (set_qname).  With TAGS (Record::set): the record ends behind its qualities — no aux data
+ * — and for an odd l_seq the unused low nibble of the last base byte is 0; bin, mapq, flag and the mate fields stay, and without
+ * READ_IDS so does the name.  With BASE_QUALITIES the qualities are l_seq copies of baseq_fill.  *handled = 0 (info[5] = -(30 +
+ * bits)) leaves the file to the caller's reader: bit 8 an invalid record, 32 a CIGAR operation code above 8 (the reference panics
+ * there), 64 two different keys with one 64-bit hash (verified byte for byte, never guessed); info[5] = -21: 2^32 records or more, or
+ * the working memory (about 24 B per record for the ids, 16 for the offsets) cannot be had.  flags == 0, unknown bits, BASE_QUALITIES
+ * without TAGS, or a bad level: SK_ERR_INVALID.  level, window_bytes, *n_records, *raw_bytes: as sk_bam_file_rewrite.  The windows come
+ * from sk_bam_file_rewrite_next under its rules.  SK_MINIMIZE_KEY_BITS=k (1 .. 64, read per call) keeps only the low k bits of the
+ * hash: a knob for tests of the collision check, of no other use.                                                               */
+#define SK_MINIMIZE_READ_IDS       1
+#define SK_MINIMIZE_BASE_QUALITIES 2
+#define SK_MINIMIZE_TAGS           4
+int sk_bam_file_minimize(sk_ctx *ctx, const char *path, int flags, uint8_t baseq_fill, int level /* 0 stored, 1 deflate */,
+                         uint64_t window_bytes /* 0 = default */, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
 
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is

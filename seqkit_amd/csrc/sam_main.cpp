@@ -1287,6 +1287,113 @@ static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usa
 	return 0;
 }
 
+// ---- sam minimize ------------------------------------------------------------------------------------------------------
+// src/sam_minimize.rs: read ids become numbers (--read-ids), the qualities a fill byte (--base-qualities), the aux data go (--tags).
+// A regular file goes to the device whole (sk_bam_file_minimize: the ids by a sort of the names' hashes, then the rewrite windows);
+// stdin, SEQKIT_HOST_INFLATE=1 and every file the device declines — an invalid record, a CIGAR operation code above 8, where
+// rust-htslib's cigar() panics, or two names with one hash — are read record by record below.
+static const char *USAGE_MINIMIZE =
+	"\nUsage:\n  sam minimize [options] <bam_file>\n\nOptions:\n"
+	"  --uncompressed    Output in uncompressed BAM format\n"
+	"  --read-ids        Minimize read identifiers (i.e. QNAME fields)\n"
+	"  --base-qualities  Remove per-base qualities\n"
+	"  --tags            Remove all aux fields (tags)\n"
+	"  --baseq-fill=N    Base quality value to fill in as placeholder [default: 255]\n\n"
+	"Changes read IDs into simple numeric identifiers, removes per-base qualities,\nand removes all auxiliary fields (tags).\n";
+
+// the device path of `sam minimize`, as rewrite_from_file
+static int64_t minimize_from_file(const std::string &path, int flags, uint8_t fill, int level)
+{
+	sk_ctx *c = host::gpu();
+	int64_t n_rec = 0;
+	uint64_t raw = 0;
+	int handled = 0;
+	if (sk_bam_file_minimize(c, path.c_str(), flags, fill, level, file_window_bytes(), &n_rec, &raw, &handled, nullptr) != SK_OK || !handled) return -1;
+	sk_bam_out_window w;
+	for (;;) {
+		check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
+		if (w.n == 0 && w.bytes == 0) break;
+		BamOut::write_all(w.bgzf, (size_t)w.bytes);
+	}
+	return n_rec;
+}
+
+static int minimize_cmd(int argc, char **argv)
+{
+	std::vector<host::Opt> opts = {{"--uncompressed", false, false, ""}, {"--read-ids", false, false, ""}, {"--base-qualities", false, false, ""},
+	                               {"--tags", false, false, ""}, {"--baseq-fill", true, false, "255"}};
+	std::vector<std::string> pos;
+	if (!host::parse_args(argc, argv, 2, opts, pos, 1) || pos.size() != 1) error("Invalid arguments.\n%s", USAGE_MINIMIZE);
+	const std::string path = expand_home(pos[0]);
+	const bool read_ids = opts[1].present, baseq = opts[2].present, tags = opts[3].present;
+	uint64_t fill64 = 0;
+	if (!host::parse_uint(opts[4].value.c_str(), 255, fill64)) error("--baseq-fill must be an integer between 0 and 255.");       // :27-28
+	if (!read_ids && !baseq && !tags) error("One of --read-ids, --base-qualities, or --tags must be given.");                    // :30-32
+	if (baseq && !tags) error("Running 'sam minimize' with --base-qualities but without the --tags flag is not yet supported.");   // :34-36
+	const uint8_t fill = (uint8_t)fill64;
+	const int level = opts[0].present ? 0 : 1;
+	const int flags = (read_ids ? SK_MINIMIZE_READ_IDS : 0) | (baseq ? SK_MINIMIZE_BASE_QUALITIES : 0) | (tags ? SK_MINIMIZE_TAGS : 0);
+	host::gpu_warmup();
+	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
+	if (file_path_wanted(path)) {
+		const int64_t n = minimize_from_file(path, flags, fill, level);
+		if (n >= 0) {
+			if (trace) fprintf(stderr, "sam minimize: device path, %lld records\n", (long long)n);
+			return 0;
+		}
+	}
+	if (trace) fprintf(stderr, "sam minimize: host reader\n");
+	BamStream bam(path, true);
+	BamOut out(level);
+	g_bam_out = &out;
+	host::at_exit_flush(finish_bam_out);
+	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
+	out.put(hdr.data(), hdr.size());
+	out.flush();                                                                // (the header in members of its own)
+	BamCore c;
+	BamStream::Var v;
+	std::vector<uint8_t> body, rec;
+	std::string name;
+	std::unordered_map<std::string, uint32_t> qname_to_id;                        // :39-40
+	uint32_t highest_id = 0;
+	while (bam.next_full(c, v, body)) {
+		const size_t L = v.l_read_name - 1;
+		const uint8_t *nm = body.data();
+		name.assign(reinterpret_cast<const char *>(nm), L);
+		if (read_ids) {                                                         // :48-59
+			const void *slash = memchr(nm, '/', L);
+			if (slash) name.resize((size_t)((const uint8_t *)slash - nm));
+			uint32_t id;
+			auto it = qname_to_id.find(name);
+			if (it != qname_to_id.end()) { id = it->second; qname_to_id.erase(it); }
+			else { id = ++highest_id; qname_to_id.emplace(name, id); }
+			name = std::to_string(id);
+		}
+		const uint8_t *cigar = nm + v.l_read_name;                                // :61 read.cigar()
+		for (uint32_t k = 0; k < v.n_cigar; k++)
+			if ((cigar[4 * k] & 15) > 8) panic("Unexpected cigar operation");
+		const size_t cs = 4 * (size_t)v.n_cigar + (((size_t)v.l_seq + 1) >> 1);
+		const size_t tail = tags ? cs + v.l_seq : body.size() - v.l_read_name;    // set(): core, name, CIGAR, bases, qualities; set_qname(): all
+		const uint32_t bs = (uint32_t)(32 + name.size() + 1 + tail);
+		rec.assign(bam.head, bam.head + 36);
+		for (int k = 0; k < 4; k++) rec[k] = (uint8_t)(bs >> (8 * k));
+		rec[12] = (uint8_t)(name.size() + 1);
+		rec.insert(rec.end(), name.begin(), name.end());
+		rec.push_back(0);
+		const size_t t0 = rec.size();
+		rec.insert(rec.end(), cigar, cigar + tail);
+		if (tags) {
+			if (v.l_seq & 1) rec[t0 + cs - 1] &= 0xf0;                            // (the bases go through as_bytes() and the encoder: the pad nibble is 0)
+			if (baseq) memset(rec.data() + t0 + cs, fill, v.l_seq);
+		}
+		out.put(rec.data(), rec.size());
+	}
+	bam.raise_deferred();
+	out.finish();
+	g_bam_out = nullptr;
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	// blocks, per-sample strings and gzip jobs are hundreds of KiB each: above glibc's default mmap threshold every one of them was a
@@ -1308,6 +1415,7 @@ int main(int argc, char **argv)
 	else if (argc >= 4 && is(1, "tags") && is(2, "from") && is(3, "qname")) rc = rewrite_cmd(argc, argv, SK_REWRITE_TAGS_FROM_QNAME, 4, USAGE_TAGS_FROM_QNAME, true);
 	else if (argc >= 4 && is(1, "qname") && is(2, "from") && is(3, "tags")) rc = rewrite_cmd(argc, argv, SK_REWRITE_QNAME_FROM_TAGS, 4, USAGE_QNAME_FROM_TAGS, true);
 	else if (argc >= 3 && is(1, "trim") && is(2, "qnames")) rc = rewrite_cmd(argc, argv, SK_REWRITE_TRIM_QNAMES, 3, USAGE_TRIM, false);
+	else if (argc >= 2 && is(1, "minimize")) rc = minimize_cmd(argc, argv);
 	else fprintf(stderr, "%s\n", USAGE_TOP);
 	host::out().flush();
 	// everything is written and closed: what is left is taking the process apart (static destructors, the HIP runtime's exit handlers,

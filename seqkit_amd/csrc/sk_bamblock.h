@@ -1,6 +1,7 @@
 // sk_bamblock.h — what the per-block passes over a verified BAM stream share (sk_inflate.hip: bam_gather_kernel; sk_bamtext.hip: the
-// reads passes; sk_bamwrite.hip: the rewrite passes).  Such a pass is a wave per BGZF block: lane 0 follows the chain of records from
-// the block's entry to its end and leaves every record's offset in LDS, then the 64 lanes take consecutive records.
+// reads passes; sk_bamwrite.hip: the rewrite passes; sk_bamminimize.hip: the minimize passes).  Such a pass is a wave per BGZF block:
+// lane 0 follows the chain of records from the block's entry to its end and leaves every record's offset in LDS, then the 64 lanes
+// take consecutive records.  Also the name hash (reads, minimize) and the span copy of the window writers (rewrite, pack, minimize).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,6 +59,44 @@ __device__ __forceinline__ unsigned long long wave_incl_scan(unsigned long long 
 		if (lane >= s) x += y;
 	}
 	return x;
+}
+
+// FNV-1a over a name's bytes, then a finalizer (murmur3's fmix64): the pairing key of the reads passes and of sk_bam_file_minimize
+__device__ __forceinline__ unsigned long long qname_key(const uint8_t *p, uint32_t n)
+{
+	unsigned long long h = 0xcbf29ce484222325ull;
+	for (uint32_t k = 0; k < n; k++) h = (h ^ p[k]) * 0x100000001b3ull;
+	h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+	return h;
+}
+
+// out[o0 .. o0 + len) by `nl` lanes from lane `lane` on: the bytes in [ro0, ro0 + rl0), [ro1, ro1 + rl1) and [ro2, ro2 + rl2) (relative
+// to o0) are src0[p - ro0], src1[p - ro1] and src2[p - ro2], the others byte(p); a span of length 0 takes nothing.  Whole dwords inside
+// one span: two aligned loads and one dword store; the others byte by byte (the first and last dwords are shared with what lies around).
+template <class ByteFn>
+__device__ __forceinline__ void emit(uint8_t *out, unsigned long long o0, unsigned long long len, uint32_t ro0, uint32_t rl0, const uint8_t *src0,
+                                     uint32_t ro1, uint32_t rl1, const uint8_t *src1, uint32_t ro2, uint32_t rl2, const uint8_t *src2, const ByteFn &byte,
+                                     uint32_t lane, uint32_t nl)
+{
+	if (len == 0) return;
+	const unsigned long long e = o0 + len, d0 = o0 >> 2, d1 = (e - 1) >> 2;
+	for (unsigned long long d = d0 + lane; d <= d1; d += nl) {
+		const unsigned long long a = d << 2;
+		if (a >= o0 && a + 4 <= e) {
+			const uint32_t p = (uint32_t)(a - o0);
+			uint32_t v;
+			if (p >= ro0 && p + 4u <= ro0 + rl0) v = bam_le32(src0 + (p - ro0));
+			else if (p >= ro1 && p + 4u <= ro1 + rl1) v = bam_le32(src1 + (p - ro1));
+			else if (p >= ro2 && p + 4u <= ro2 + rl2) v = bam_le32(src2 + (p - ro2));
+			else v = byte(p) | (byte(p + 1u) << 8) | (byte(p + 2u) << 16) | (byte(p + 3u) << 24);
+			*reinterpret_cast<uint32_t *>(out + a) = v;
+		} else {
+			for (uint32_t b = 0; b < 4u; b++) {
+				const unsigned long long pp = a + b;
+				if (pp >= o0 && pp < e) out[pp] = (uint8_t)byte((uint32_t)(pp - o0));
+			}
+		}
+	}
 }
 
 }  // namespace sk

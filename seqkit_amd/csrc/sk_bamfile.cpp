@@ -212,11 +212,14 @@ struct ReadsState : WindowedState {
 	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
 };
 
-// sk_bam_file_rewrite / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot kKeepFileCols), the window
-// plan (output bytes of window w from wo[w] on), one device area for the window being rewritten and compressed (raw bytes, deflate
-// scratch, blocks) and two packed-member buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
+// sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot
+// kKeepFileCols), the window plan (output bytes of window w from wo[w] on), one device area for the window being rewritten and
+// compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
 struct RewriteState : WindowedState {
-	int op = 0, level = 1;
+	int op = 0, level = 1;                       // op 0: sk_bam_file_minimize, with its flags, fill byte and ids (ctx slot kKeepMinimize)
+	int min_flags = 0;
+	uint8_t min_fill = 255;
+	const uint32_t *ids = nullptr;
 	uint64_t *krec = nullptr, *kout = nullptr;
 	std::vector<uint64_t> wo;
 	std::vector<uint8_t> header;                 // the output header (the first window)
@@ -973,7 +976,8 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		if (!s.next_window(w)) return false;
 		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
 		raw_len = s.wo[w + 1] - s.wo[w];
-		e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st);
+		e = s.op ? sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st)
+		         : sk::launch_bam_min_write(s.d_out, s.krec, s.kout, s.ids, first, n, s.wo[w], s.min_flags, s.min_fill, s.d_raw, sk::ctx_n_cu(c), st);
 	}
 	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
 	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
@@ -988,6 +992,56 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 	if (e != hipSuccess) { *rc = sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_rewrite: window at record %lld: %s", (long long)first, hipGetErrorString(e)); return false; }
 	s.first[b] = first; s.n[b] = n; s.raw[b] = raw_len;
 	return true;
+}
+
+// What sk_bam_file_rewrite and sk_bam_file_minimize share once every record's stream and output offsets (s.krec, s.kout) are there: the
+// window plan, the window area, and the header's members on their way.  `total`: the records' output bytes.
+static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, RewriteState &s, uint64_t gen, int level, uint64_t window_bytes, uint64_t total,
+                    double t_size, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	const uint64_t N = fr.n_records;
+	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
+	int krc = SK_OK;
+	// ---- the windows: at most W rewritten bytes each
+	uint64_t mx[3];                                                     // records, rewritten bytes
+	bool room = true;
+	if (int r = plan_windows(c, cl, window_bytes, s.kout, nullptr, N, total, 0, s, s.wo, nullptr, mx, &room)) return r;
+	if (!room) BF_LEAVE(21);
+	s.header = bamfmt::rewrite_header(fr.header);
+	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
+	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
+	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	const uint64_t pack = max_raw + nblk * 31 + 64;
+	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
+	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
+	if (!dw) BF_LEAVE(21);
+	const size_t p_pack = up(pack + 28);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * p_pack + 64, true, &krc);
+	if (!hw) BF_LEAVE(21);
+	s.d_raw = dw; s.d_blocks = dw + a_raw; s.d_result = (uint32_t *)(dw + a_raw + a_blk); s.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
+	s.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
+	uint8_t *dp = dw + a_raw + a_blk + a_res + a_crc + a_msz;
+	s.d_pack[0] = dp; s.d_pack[1] = dp + a_pack;
+	s.d_slots = level ? dp + 2 * a_pack : nullptr;
+	s.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
+	s.h_pin[0] = hw; s.h_pin[1] = hw + p_pack; s.h_size = (uint64_t *)(hw + 2 * p_pack);
+	for (int b = 0; b < 2; b++)
+		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
+	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
+	s.level = level; s.header_done = false;
+	s.begin(fr.d_out, gen);
+	int rc = SK_OK;
+	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
+	if (rc) return rc;
+	s.live = true;
+	if (n_records) *n_records = (int64_t)N;
+	if (raw_bytes) *raw_bytes = s.header.size() + total;
+	*handled = 1;
+	char tail[128];
+	snprintf(tail, sizeof tail, "; %llu records, %llu rewritten bytes, %lld windows", (unsigned long long)N, (unsigned long long)total, (long long)s.ws.size() - 1);
+	file_call_close(fr, "size + index + plan", t_size, tail, info);
+	return SK_OK;
 }
 
 extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int level, uint64_t window_bytes, int64_t *n_records, uint64_t *raw_bytes,
@@ -1038,46 +1092,96 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 		BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, d_rb, s.krec, s.kout, st));
 		BF_HIP(hipStreamSynchronize(st));                              // (rb is this scope's)
 	}
-	// ---- the windows: at most W rewritten bytes each
-	uint64_t mx[3];                                                     // records, rewritten bytes
-	bool room = true;
-	if (int r = plan_windows(c, cl, window_bytes, s.kout, nullptr, N, total, 0, s, s.wo, nullptr, mx, &room)) return r;
-	if (!room) BF_LEAVE(21);
-	s.header = bamfmt::rewrite_header(fr.header);
-	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
-	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
-	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
-	const uint64_t pack = max_raw + nblk * 31 + 64;
-	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
-	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
-	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
-	if (!dw) BF_LEAVE(21);
-	const size_t p_pack = up(pack + 28);
-	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * p_pack + 64, true, &krc);
-	if (!hw) BF_LEAVE(21);
-	s.d_raw = dw; s.d_blocks = dw + a_raw; s.d_result = (uint32_t *)(dw + a_raw + a_blk); s.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
-	s.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
-	uint8_t *dp = dw + a_raw + a_blk + a_res + a_crc + a_msz;
-	s.d_pack[0] = dp; s.d_pack[1] = dp + a_pack;
-	s.d_slots = level ? dp + 2 * a_pack : nullptr;
-	s.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
-	s.h_pin[0] = hw; s.h_pin[1] = hw + p_pack; s.h_size = (uint64_t *)(hw + 2 * p_pack);
-	for (int b = 0; b < 2; b++)
-		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
-	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
-	s.op = op; s.level = level; s.header_done = false;
-	s.begin(fr.d_out, R->gen);
-	int rc = SK_OK;
-	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
-	if (rc) return rc;
-	s.live = true;
-	if (n_records) *n_records = (int64_t)N;
-	if (raw_bytes) *raw_bytes = s.header.size() + total;
-	*handled = 1;
-	char tail[128];
-	snprintf(tail, sizeof tail, "; %llu records, %llu rewritten bytes, %lld windows", (unsigned long long)N, (unsigned long long)total, (long long)s.ws.size() - 1);
-	file_call_close(fr, "size + index + plan", t_size, tail, info);
-	return SK_OK;
+	s.op = op;
+	return rw_begin(c, cl, fr, s, R->gen, level, window_bytes, total, t_size, n_records, raw_bytes, handled, info);
+}
+
+// ---- sam minimize (include/seqkit_hip.h: sk_bam_file_minimize; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then with SK_MINIMIZE_READ_IDS the id passes (sk_bamminimize.hip: keys, sort, runs, ids) in the working memory of ctx
+// slot kKeepMinimize — two key and two index buffers for the sort (24 B per record and the sort's own scratch); behind the sort the idle
+// key buffer holds src and the opener counts and the idle index buffer the ids — then the sizing pass with the ids' digits, and from
+// there on what sk_bam_file_rewrite does.  The file is left to the caller's reader (info[5] = -21) when that memory cannot be had or
+// the file has 2^32 records or more (the ids are u32), and with info[5] = -(30 + bits) on an invalid record (8), a CIGAR operation
+// code above 8 (32) or two keys with one hash (64).
+extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint8_t baseq_fill, int level, uint64_t window_bytes, int64_t *n_records,
+                                    uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_minimize", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    const int all = SK_MINIMIZE_READ_IDS | SK_MINIMIZE_BASE_QUALITIES | SK_MINIMIZE_TAGS;
+		    if (!flags || (flags & ~all) || ((flags & SK_MINIMIZE_BASE_QUALITIES) && !(flags & SK_MINIMIZE_TAGS)))
+			    return sk::ctx_fail(c, SK_ERR_INVALID, "flags = %d", flags);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const double t_size = now_ms();
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	uint64_t *d_blk = nullptr;
+	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 16 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+	cl.dev.push_back(d_blk);
+	uint64_t *bo = d_blk, *d_rb = bo + nb + 1;
+	uint32_t *d_decline = (uint32_t *)(d_rb + nb);
+	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
+	std::vector<uint64_t> rb;
+	if (int r = block_first_records(c, fr, rb)) return r;
+	if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
+	int krc = SK_OK;
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * up(N * 8 + 8), false, &krc);
+	if (!kb) BF_LEAVE(21);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	RewriteState &s = R->rw;
+	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
+	uint32_t decline = 0;
+	auto declined = [&](void) -> int {                                   // the bits so far; < 0: the copy failed
+		if (hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
+		if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_minimize: declined (bits %#x)\n", decline);
+		return (int)decline;
+	};
+	// ---- the read ids
+	s.ids = nullptr;
+	if ((flags & SK_MINIMIZE_READ_IDS) && N) {
+		int bits = 64;                                                  // (a test knob: fewer bits make hash collisions reachable)
+		if (const char *ev = getenv("SK_MINIMIZE_KEY_BITS")) { const int v = atoi(ev); if (v >= 1 && v <= 64) bits = v; }
+		uint64_t *key[2] = {nullptr, nullptr};
+		uint32_t *idx[2] = {nullptr, nullptr};
+		size_t temp_bytes = 0;
+		BF_HIP(sk::bam_min_sort(nullptr, &temp_bytes, key, idx, N, bits, nullptr, st));
+		const size_t a_key = up(N * 8), a_idx = up(N * 4), a_agg = up((N / 1024 + 2) * 4);
+		uint8_t *mb = (uint8_t *)sk::ctx_keep(c, sk::kKeepMinimize, 2 * a_key + 2 * a_idx + a_agg + up(temp_bytes), false, &krc);
+		if (!mb) BF_LEAVE(21);
+		key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
+		idx[0] = (uint32_t *)(mb + 2 * a_key); idx[1] = (uint32_t *)(mb + 2 * a_key + a_idx);
+		uint32_t *agg = (uint32_t *)(mb + 2 * a_key + 2 * a_idx);
+		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, bits, s.krec, key[0], idx[0], d_decline, st));
+		const int d0 = declined();                                      // (the passes below read the names of valid records only)
+		if (d0 < 0) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_minimize: the key pass failed");
+		if (d0) BF_LEAVE(30 + d0);
+		int cur = 0;
+		BF_HIP(sk::bam_min_sort(mb + 2 * a_key + 2 * a_idx + a_agg, &temp_bytes, key, idx, N, bits, &cur, st));
+		uint32_t *src = (uint32_t *)key[cur ^ 1], *cnt = src + N, *ids = idx[cur ^ 1];
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, s.krec, key[cur], idx[cur], N, agg, src, cnt, ids, d_decline, st));
+		s.ids = ids;
+	}
+	// ---- the sizing pass: per block the output bytes (then their exclusive offsets), the decline bits
+	BF_HIP(sk::launch_bam_min_size(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, flags, s.ids, bo, d_decline, st));
+	uint64_t total = 0;
+	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
+	const int d1 = declined();
+	if (d1 < 0) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_minimize: the sizing pass failed");
+	if (d1) BF_LEAVE(30 + d1);
+	BF_HIP(sk::launch_bam_min_index(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, flags, s.ids, bo, s.krec, s.kout, st));
+	BF_HIP(hipStreamSynchronize(st));
+	s.op = 0; s.min_flags = flags; s.min_fill = baseq_fill;
+	return rw_begin(c, cl, fr, s, R->gen, level, window_bytes, total, t_size, n_records, raw_bytes, handled, info);
 }
 
 extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)

@@ -336,15 +336,6 @@ __global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_size_kernel(const 
 	}
 }
 
-// FNV-1a over the qname, then a finalizer (murmur3's fmix64)
-__device__ __forceinline__ u64 qname_key(const uint8_t *p, uint32_t n)
-{
-	u64 h = 0xcbf29ce484222325ull;
-	for (uint32_t k = 0; k < n; k++) h = (h ^ p[k]) * 0x100000001b3ull;
-	h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-	return h;
-}
-
 __global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_index_kernel(const ReadsArgs a)
 {
 	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];

@@ -12,7 +12,7 @@
 // bam_rw_write_kernel — one window's records: a 16-lane group owns a record and covers its output in consecutive dwords.  A dword
 // that lies inside one of the record's copied spans (the core and the kept name; CIGAR, bases, qualities and aux) is built from two
 // aligned loads with a funnel shift (v_alignbyte) and stored whole; the rest — the block_size and l_read_name bytes, the spans' edges,
-// the appended bytes and the dwords shared with the neighbouring records — is composed byte by byte.
+// the appended bytes and the dwords shared with the neighbouring records — is composed byte by byte (sk_bamblock.h: emit).
 // bgzf_cut_kernel / bgzf_member_size_kernel / bgzf_pack_kernel — a window as blocks of at most 0xff00 bytes for bgzf_deflate_kernel
 // (sk_deflate.hip), then the members (SAMv1 §4.1: 18-byte header with BC = BSIZE - 1, payload, CRC32, ISIZE) back to back: a wave
 // per member, the payload copied as the records are.  A block that does not shrink, and every block at level 0, is framed as a
@@ -148,33 +148,6 @@ __device__ __forceinline__ u32 rw_byte(const uint8_t *r, int op, const RwPlan &p
 	return 0u;
 }
 
-// out[o0 .. o0 + len) by `nl` lanes from lane `lane` on: the bytes in [ro0, ro0 + rl0) and [ro1, ro1 + rl1) (relative to o0) are
-// src0[p - ro0] and src1[p - ro1], the others byte(p).  Whole dwords inside one span: two aligned loads and one dword store; the others
-// byte by byte (the first and last dwords are shared with what lies around).
-template <class ByteFn>
-__device__ __forceinline__ void emit(uint8_t *out, u64 o0, u64 len, u32 ro0, u32 rl0, const uint8_t *src0, u32 ro1, u32 rl1, const uint8_t *src1,
-                                     const ByteFn &byte, u32 lane, u32 nl)
-{
-	if (len == 0) return;
-	const u64 e = o0 + len, d0 = o0 >> 2, d1 = (e - 1) >> 2;
-	for (u64 d = d0 + lane; d <= d1; d += nl) {
-		const u64 a = d << 2;
-		if (a >= o0 && a + 4 <= e) {
-			const u32 p = (u32)(a - o0);
-			u32 v;
-			if (p >= ro0 && p + 4u <= ro0 + rl0) v = bam_le32(src0 + (p - ro0));
-			else if (p >= ro1 && p + 4u <= ro1 + rl1) v = bam_le32(src1 + (p - ro1));
-			else v = byte(p) | (byte(p + 1u) << 8) | (byte(p + 2u) << 16) | (byte(p + 3u) << 24);
-			*reinterpret_cast<u32 *>(out + a) = v;
-		} else {
-			for (u32 b = 0; b < 4u; b++) {
-				const u64 pp = a + b;
-				if (pp >= o0 && pp < e) out[pp] = (uint8_t)byte((u32)(pp - o0));
-			}
-		}
-	}
-}
-
 struct RwArgs {
 	const uint8_t *stream;
 	const u64 *bend, *entry;
@@ -244,8 +217,8 @@ __global__ __launch_bounds__(kRwThreads) void bam_rw_write_kernel(const uint8_t 
 		(void)rw_plan(r, op, pl);
 		const u64 ob = kout[k] - o0;
 		auto byte = [&](u32 p) -> u32 { return rw_byte(r, op, pl, p); };
-		if (pl.same) emit(out, ob, pl.out_len, 0u, pl.out_len, r, 0u, 0u, r, byte, gl, 16u);
-		else emit(out, ob, pl.out_len, 13u, 23u + pl.P, r + 13, 36u + pl.P + pl.X, pl.tail_len, r + pl.tail_s, byte, gl, 16u);
+		if (pl.same) emit(out, ob, pl.out_len, 0u, pl.out_len, r, 0u, 0u, r, 0u, 0u, r, byte, gl, 16u);
+		else emit(out, ob, pl.out_len, 13u, 23u + pl.P, r + 13, 36u + pl.P + pl.X, pl.tail_len, r + pl.tail_s, 0u, 0u, r, byte, gl, 16u);
 	}
 }
 
@@ -303,7 +276,7 @@ __global__ __launch_bounds__(256) void bgzf_pack_kernel(const uint8_t *raw, cons
 		return q < 4u ? (c >> (8u * q)) & 0xffu : (len >> (8u * (q - 4u))) & 0xffu;
 	};
 	const u32 plen = stored ? len : clen;
-	emit(out, moff[i], bsize, p0, plen, src, 0u, 0u, src, byte, lane, 64u);
+	emit(out, moff[i], bsize, p0, plen, src, 0u, 0u, src, 0u, 0u, src, byte, lane, 64u);
 }
 
 }  // namespace

@@ -201,6 +201,23 @@ hipError_t launch_bam_rw_index(const uint8_t *stream, const uint64_t *bend, cons
                                const uint64_t *rb, uint64_t *krec, uint64_t *kout, hipStream_t st);
 hipError_t launch_bam_rw_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, int op,
                                uint8_t *out, int n_cu, hipStream_t st);
+// ---- sam minimize: the read ids and the per-record rewrite of sk_bam_file_minimize (sk_bamminimize.hip) ----
+// keys: every record's stream offset, the hash of its name up to the first '/' (its low key_bits bits) and its index; decline bit 8: an
+// invalid record.  sort: (hash, index) by hash, stable, between the two buffers of each kind (*sorted: the one that holds the result);
+// temp == nullptr: only *temp_bytes.  ids: from the sorted pairs the records' ids (agg: u32[n / 1024 + 1] scratch; src, cnt: u32[n]
+// scratch); decline bit 64: two different keys with one hash.  size / index / write: as launch_bam_rw_*; flags SK_MINIMIZE_*; ids ==
+// nullptr without SK_MINIMIZE_READ_IDS; decline bit 32: a CIGAR operation code above 8.
+hipError_t launch_bam_min_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int key_bits,
+                               uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st);
+hipError_t bam_min_sort(void *temp, size_t *temp_bytes, uint64_t *key[2], uint32_t *idx[2], uint64_t n, int key_bits, int *sorted, hipStream_t st);
+hipError_t launch_bam_min_ids(const uint8_t *stream, const uint64_t *krec, const uint64_t *key, const uint32_t *idx, uint64_t n, uint32_t *agg,
+                              uint32_t *src, uint32_t *cnt, uint32_t *ids, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_min_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int flags,
+                               const uint32_t *ids, uint64_t *bo, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_min_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int flags,
+                                const uint32_t *ids, const uint64_t *bo, uint64_t *krec, uint64_t *kout, hipStream_t st);
+hipError_t launch_bam_min_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint32_t *ids, int64_t first, int64_t n,
+                                uint64_t o0, int flags, uint8_t fill, uint8_t *out, int n_cu, hipStream_t st);
 // BGZF members of raw[0 .. raw_len): the cut into blocks of at most 0xff00 bytes (blocks: device sk_deflate_block[n]), and, after the
 // deflate (or at level 0 the CRC alone), the members back to back into out: msz[n + 1] scratch, msz[n] = their total bytes afterwards
 hipError_t launch_bgzf_cut(uint64_t raw_len, void *blocks, int64_t n, hipStream_t st);
@@ -237,8 +254,9 @@ enum KeepSlot {
 	kKeepComp = 0, kKeepOut = 1, kKeepPin = 2, kKeepTable = 3, kKeepBlocks = 4, kKeepStatus = 5,   // the front half
 	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
 	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
-	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / sk_bam_file_rewrite: per-record columns, windows
-	kKeepSlots = 12
+	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize: per-record columns, windows
+	kKeepMinimize = 12,                                 // sk_bam_file_minimize: the sort's keys and indices, then the read ids
+	kKeepSlots = 13
 };
 hipStream_t ctx_stream(sk_ctx *c);
 hipStream_t ctx_stream2(sk_ctx *c);

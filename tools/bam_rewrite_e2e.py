@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""`sam tags from qname`, `sam qname from tags` and `sam trim qnames` from a BAM FILE: the device path (sk_bam_file_rewrite) against the
-host reader (SEQKIT_HOST_INFLATE=1), alternating: wall time and CPU-seconds of every run, stdout to a file on local disk and to
-/dev/null; the inflated outputs of both paths are checked identical.
+"""`sam tags from qname`, `sam qname from tags`, `sam trim qnames` and `sam minimize` (--read-ids; --read-ids --tags; --read-ids --tags
+--base-qualities) from a BAM FILE: the device path (sk_bam_file_rewrite, sk_bam_file_minimize) against the host reader
+(SEQKIT_HOST_INFLATE=1), alternating: wall time and CPU-seconds of every run, stdout to a file on local disk and to /dev/null; the
+inflated outputs of both paths are checked identical.
 
 The file: paired records of 150 drawn bases and qualities whose names carry a "/1" or "/2" suffix and a " UMI:" field
 ("readN/1 UMI:ACGTACGT"); for `qname from tags` the output of `tags from qname` (names without the field, an RX tag).
-usage: bam_rewrite_e2e.py [million records (20)] [runs per path (2)] [--lib-only: the library call alone, e.g. under rocprofv3
---kernel-trace --stats]"""
+usage: bam_rewrite_e2e.py [million records (20)] [runs per path (2)] [--lib-only: the library calls alone, e.g. under rocprofv3
+--kernel-trace --stats] [--only=minimize: `trim qnames`, the minimize rows' yardstick, and the minimize rows] [--trim-sam=PATH: the
+`trim qnames` row from another build's sam binary, e.g. the parent commit's]"""
 import os
 import resource
 import struct
@@ -25,7 +27,9 @@ from seqkit_amd import build  # noqa: E402
 build.build_all()
 SAM = os.path.join(build.BINDIR, "sam")
 lib_only = "--lib-only" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--lib-only"]
+only_minimize = "--only=minimize" in sys.argv
+TRIM_SAM = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--trim-sam=")), SAM)
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 millions = int(argv[0]) if len(argv) > 0 else 20
 runs = int(argv[1]) if len(argv) > 1 else 2
 PAIRS = 50_000
@@ -72,6 +76,12 @@ if lib_only:
             handled, n, raw, info = ctx.bam_file_rewrite(bam, "tags from qname", 1, 0)
             tot = sum(len(w["bgzf"]) for w in ctx.bam_file_rewrite_windows())
             print(f"sk_bam_file_rewrite + windows: {time.perf_counter() - t:.3f} s, handled {handled}, {n} records, {raw / 1e9:.2f} GB -> {tot / 1e9:.2f} GB")
+        for flags in ((True, False, False), (True, False, True), (True, True, True)):
+            for _ in range(2):
+                t = time.perf_counter()
+                handled, n, raw, info = ctx.bam_file_minimize(bam, *flags)
+                tot = sum(len(w["bgzf"]) for w in ctx.bam_file_rewrite_windows())
+                print(f"sk_bam_file_minimize {flags} + windows: {time.perf_counter() - t:.3f} s, handled {handled}, {n} records, {raw / 1e9:.2f} GB -> {tot / 1e9:.2f} GB")
     sys.exit(0)
 
 
@@ -89,15 +99,25 @@ def run(words, path, env, dest):
     r0 = resource.getrusage(resource.RUSAGE_CHILDREN)
     t = time.perf_counter()
     with open(dest, "wb") as o:
-        p = subprocess.run([SAM] + words + [path], stdout=o, stderr=subprocess.PIPE, env=dict(os.environ, **env))
+        p = subprocess.run([TRIM_SAM if words[0] == "trim" else SAM] + words + [path], stdout=o, stderr=subprocess.PIPE,
+                           env=dict(os.environ, SK_BAMFILE_TRACE="1", **env))
     wall = time.perf_counter() - t
     r1 = resource.getrusage(resource.RUSAGE_CHILDREN)
     assert p.returncode == 0, p.stderr[-500:]
+    who = ("sam " + " ".join(w for w in words if not w.startswith("--")) + ": ").encode()
+    assert (who + (b"host reader" if env else b"device path")) in p.stderr, p.stderr[-500:]       # (a collision would say "host reader")
     return wall, (r1.ru_utime - r0.ru_utime) + (r1.ru_stime - r0.ru_stime)
 
 
-subprocess.run([SAM, "tags", "from", "qname", bam], stdout=open(tagged, "wb"), check=True)
-for words, path in ((["tags", "from", "qname"], bam), (["qname", "from", "tags"], tagged), (["trim", "qnames"], bam)):
+ROWS = [(["tags", "from", "qname"], bam), (["qname", "from", "tags"], tagged), (["trim", "qnames"], bam),
+        (["minimize", "--read-ids"], bam), (["minimize", "--read-ids", "--tags"], bam), (["minimize", "--read-ids", "--tags", "--base-qualities"], bam)]
+if only_minimize:
+    ROWS = ROWS[2:]
+else:
+    subprocess.run([SAM, "tags", "from", "qname", bam], stdout=open(tagged, "wb"), check=True)
+if TRIM_SAM != SAM:
+    print(f"# the trim qnames row: {TRIM_SAM}")
+for words, path in ROWS:
     res = {}
     for dest in (out, "/dev/null"):
         for k in range(runs):
