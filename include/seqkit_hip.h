@@ -299,7 +299,8 @@ int sk_bam_flag_tlen_dev(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, 
  * payload; out 16-byte aligned.  status[i] (device u32): 0 = block i was inflated (and, with check_crc, its CRC
  * matched); 1..8 = the decoder gave the block up (an irregular code, a distance before the block, sizes that do not
  * match: what zlib would call a data error, and a few legal rarities) — nothing is decided here: the caller inflates
- * such a block with zlib, whose verdict stands; bit 8 (0x100) = CRC mismatch.  All pointers are device pointers.
+ * such a block with zlib, whose verdict stands; bit 8 (0x100) = CRC mismatch.  A block with in_len == 0 is given up
+ * too (8), whatever its out_len: no input is no DEFLATE stream.  All pointers are device pointers.
  *
  * sk_bam_walk_dev: stream = the inflated blocks back to back (out above, stream_len bytes, readable 8 bytes beyond),
  * block_end[c] = where block c ends in it (device u64[n], ascending), first_record = where the first record begins

@@ -1085,11 +1085,13 @@ __global__ __launch_bounds__(kInfWaves * 64) void bgzf_inflate_kernel(const uint
 			blk.out_off = (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)w2) | ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w2 >> 32)) << 32);
 			blk.crc = 0u; blk.pad = 0u;
 		}
-		u32 st = 0u;
+		// (no input at all is no DEFLATE stream, whatever out_len says — the shortest one, a lone end-of-block code, is 10 bits: status 8,
+		// "the input ends early", without a look at the bytes around it that belong to other blocks)
+		u32 st = 8u;
 #ifdef SK_INF_STAMPS
 		const u64 t_blk = __builtin_amdgcn_s_memtime();
 #endif
-		if (blk.out_len != 0u || blk.in_len != 0u) st = inf_block(L, wave, comp, blk, out, lane);
+		if (blk.in_len != 0u) st = inf_block(L, wave, comp, blk, out, lane);
 #ifdef SK_INF_STAMPS
 		if (lane == 0) { atomicAdd(&g_inf_stamps[15], __builtin_amdgcn_s_memtime() - t_blk); atomicAdd(&g_inf_stamps[14], 1ull); }
 #endif

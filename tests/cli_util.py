@@ -27,7 +27,11 @@ def gunzip_dir(d):
 
 def bgzf_block(data: bytes) -> bytes:
     c = zlib.compressobj(6, zlib.DEFLATED, -15)
-    comp = c.compress(data) + c.flush()
+    return bgzf_member(c.compress(data) + c.flush(), data)
+
+
+def bgzf_member(comp: bytes, data: bytes) -> bytes:
+    """the BGZF framing of one block: `comp` is taken as the raw DEFLATE of `data`, whoever wrote it"""
     bsize = len(comp) + 25
     hdr = struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, bsize)
     return hdr + comp + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data) & 0xFFFFFFFF)

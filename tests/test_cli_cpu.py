@@ -314,3 +314,48 @@ def test_own_inflate_and_crc_against_zlib_under_asan(tmp_path):
                     os.path.join(build.REPO, "tests", "cpp", "inflate_test.cpp"), os.path.join(build.CSRC, "host_inflate.cpp"), "-lz"], check=True)
     out = subprocess.run([str(exe), "800"], stdout=subprocess.PIPE, check=True, env={"ASAN_OPTIONS": "detect_leaks=0"}).stdout.decode()
     assert out.startswith("ok: 800 streams"), out
+
+
+# zlib accepts these members of the crafted corpus and host::inflate_raw reports them (the caller then asks zlib), by design:
+# a literal/length alphabet that is a single code — build() in host_inflate.cpp lets only a DISTANCE alphabet be a lone 1-bit
+# code (`const bool single = kind == 1 && ...; if (left != 0 && !single) return false;`), where zlib's rule (max == 1) allows it
+# for literals/lengths too.  No writer of BGZF makes such a block: it can only ever hold an end-of-block code.
+HOST_INFLATE_REPORTS_BY_DESIGN = ("by design: lone 1-bit end-of-block code, empty member",
+                                  "by design: lone 1-bit end-of-block code, behind a fixed block of data",
+                                  "by design: lone 1-bit end-of-block code, behind a stored block of data")
+
+
+def write_inflate_container(path, cases, by_design):
+    """the file tests/cpp/inflate_streams_test.cpp reads: count; per member in_len, out_len, flags, name_len, name, payload, expected bytes"""
+    import struct
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(cases)))
+        for c in cases:
+            name = c.name.encode()
+            f.write(struct.pack("<IIII", len(c.payload), len(c.out), (1 if c.valid else 0) | (2 if c.name in by_design else 0), len(name)))
+            f.write(name + c.payload + c.out)
+
+
+def test_own_inflate_on_crafted_streams_under_asan(tmp_path):
+    """host::inflate_raw on the DEFLATE members zlib's encoder never writes (tests/deflate_corpus.py: long codes in every alphabet
+    — the second-level tables —, headers of every legal shape, empty blocks, stored blocks at every bit phase, tokens that end
+    where the decoder leaves its unchecked loop, structured invalid streams): whatever it accepts zlib accepts with the same
+    bytes, whatever zlib accepts it accepts, except the enumerated class above.  tests/cpp/inflate_streams_test.cpp."""
+    import os
+    import subprocess
+    from seqkit_amd import build
+    from tests import deflate_corpus as dc
+    cases = dc.corpus_valid(0) + dc.corpus_invalid()
+    assert set(HOST_INFLATE_REPORTS_BY_DESIGN) <= {c.name for c in cases}
+    box = tmp_path / "members.bin"
+    write_inflate_container(box, cases, HOST_INFLATE_REPORTS_BY_DESIGN)
+    exe = tmp_path / "inflate_streams_test"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I", build.CSRC, "-I", os.path.join(build.REPO, "include"), "-o", str(exe),
+                    os.path.join(build.REPO, "tests", "cpp", "inflate_streams_test.cpp"), os.path.join(build.CSRC, "host_inflate.cpp"), "-lz"], check=True)
+    r = subprocess.run([str(exe), str(box)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env={"ASAN_OPTIONS": "detect_leaks=0"})
+    out = r.stdout.decode()
+    assert r.returncode == 0, r.stderr.decode()[-4000:]
+    n_valid = sum(1 for c in cases if c.valid) - len(HOST_INFLATE_REPORTS_BY_DESIGN)
+    assert out.startswith(f"ok: {len(cases)} members, {n_valid} accepted, {len(cases) - n_valid - len(HOST_INFLATE_REPORTS_BY_DESIGN)} refused with zlib, "
+                          f"{len(HOST_INFLATE_REPORTS_BY_DESIGN)} reported by design"), out
