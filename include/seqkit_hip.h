@@ -421,7 +421,7 @@ int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
  * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
  * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
  * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
- * sk_bam_file_rewrite (or sk_bam_file_minimize, below, whose windows it hands out too): SK_ERR_INVALID.                         */
+ * sk_bam_file_rewrite (or sk_bam_file_minimize or sk_bam_file_markdup, below, whose windows it hands out too): SK_ERR_INVALID.                         */
 #define SK_REWRITE_TRIM_QNAMES     1
 #define SK_REWRITE_QNAME_FROM_TAGS 2
 #define SK_REWRITE_TAGS_FROM_QNAME 3
@@ -454,6 +454,28 @@ int sk_bam_file_rewrite_next(sk_ctx *ctx, sk_bam_out_window *w);
 #define SK_MINIMIZE_TAGS           4
 int sk_bam_file_minimize(sk_ctx *ctx, const char *path, int flags, uint8_t baseq_fill, int level /* 0 stored, 1 deflate */,
                          uint64_t window_bytes /* 0 = default */, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
+
+/* ---- BAM out for `sam mark duplicates` (src/sam_mark_duplicates.rs:46-167) ---------------------------------------------------
+ * sk_bam_file_markdup: sk_bam_file_rewrite's front half, window pipeline and header; every record passes byte for byte except bit
+ * 0x400 of its flag.  A mapped read's signature: start_pos = pos, or for a reverse read (0x10) cigar end_pos as SK_COL_END; strand;
+ * the UMI = the value of its first RX field when that has type Z or H and ignore_umi == 0, else empty; fraglen = min(|tlen|, 65535)
+ * when the UMI is empty, else 0.  A group is the mapped reads of one run of equal refID in file order with one start_pos and strand.
+ * Per group, in file order, the first read not yet in a cluster is a seed, and every later such read joins it whose fraglen equals
+ * the seed's or either is 0, and whose UMI has the seed's length with at most one position where the bytes differ and neither is
+ * 'N', or either is empty (compatible with the SEED: not transitive).  Every read of a cluster gets 0x400 except the one with the
+ * largest l_seq, the earliest on a tie, which loses it.  Unmapped reads (0x4) keep their flag.  That is what the reference's FIFO
+ * loop writes for a file it accepts as sorted whose mapped reads have 0 <= pos and end_pos <= INT32_MAX.  *n_duplicates: the
+ * output records that carry 0x400.  *handled = 0 (info[5] = -(30 + bits)) leaves the file to the caller's reader, nothing written:
+ * bit 1 a record with 0x100 or 0x800, 2 a record whose refID equals its predecessor's and whose (uint32) pos is below its
+ * predecessor's, 4 a mapped read with pos < 0 or a reverse one with end_pos > INT32_MAX, 8 a record whose variable part is shorter
+ * than its fields, 16 aux data that do not parse up to the first RX field or the record's end, 32 a CIGAR operation code above 8 on
+ * a mapped reverse read (the reference panics there), 64 2^31 - 1 or more refID runs; info[5] = -21: 2^32 records or more, or the
+ * working memory cannot be had: 18 B per record, and 44 B per record more with the sort's scratch where those do not fit into the
+ * device buffer of the compressed file, which is idle by then and serves as scratch (SK_MARKDUP_OWN_MEMORY set: never there; for
+ * tests).  A bad level: SK_ERR_INVALID.  level, window_bytes, *n_records, *raw_bytes: as sk_bam_file_rewrite.  The windows come from
+ * sk_bam_file_rewrite_next under its rules.                                                                                      */
+int sk_bam_file_markdup(sk_ctx *ctx, const char *path, int ignore_umi, int level /* 0 stored, 1 deflate */, uint64_t window_bytes /* 0 = default */,
+                        int64_t *n_records, int64_t *n_duplicates, uint64_t *raw_bytes, int *handled, double info[8]);
 
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is

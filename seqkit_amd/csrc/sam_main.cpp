@@ -1394,6 +1394,199 @@ static int minimize_cmd(int argc, char **argv)
 	return 0;
 }
 
+// ---- sam mark duplicates ---------------------------------------------------------------------------------------------------
+// src/sam_mark_duplicates.rs: reads that share start position, strand and fragment length or UMI form a cluster; all of a cluster get
+// flag 0x400 except its longest read.  A regular file goes to the device whole (sk_bam_file_markdup: signatures, a sort by (tid run,
+// start_pos, strand), a greedy per group, the rewrite windows); stdin, SEQKIT_HOST_INFLATE=1 and every file the device declines — one
+// with a record the reference stops at among them — go through the reference's own loop below: a FIFO of reads, clustered and flushed
+// every 1000 records, at a change of tid and at the end.
+static const char *USAGE_MARK_DUPLICATES =
+	"\nUsage:\n  sam mark duplicates [options] <bam_file>\n\nOptions:\n"
+	"  --uncompressed    Output in uncompressed BAM format\n"
+	"  --ignore-umi      Ignore UMI stored in RX tag even if present\n\n"
+	"Searches BAM files for DNA fragments that were read multiple times in\nsequencing. When such fragments are found, the highest quality read is\n"
+	"kept, and other reads are marked as duplicates.\n\n"
+	"The input BAM file must be position-sorted. Output is written to\nthe standard output, preserving the order and content of BAM records,\n"
+	"except for the duplicate flag (0x400).\n";
+
+namespace {
+
+struct DupRead {                                                            // :25-32
+	uint32_t start_pos, pos, l_seq;
+	bool strand, ready;
+	uint16_t fraglen;
+	std::string umi;
+	std::vector<uint8_t> rec;                                               // block_size, core and variable part; the flag at 18
+	bool duplicate() const { return rec[19] & 0x04; }
+	void set_duplicate(bool on) { rec[19] = (uint8_t)(on ? rec[19] | 0x04 : rec[19] & ~0x04); }
+};
+
+// a FIFO that find_clusters indexes: a vector whose front moves
+struct DupQueue {
+	std::vector<DupRead> v;
+	size_t head = 0;
+	size_t size() const { return v.size() - head; }
+	DupRead &operator[](size_t k) { return v[head + k]; }
+	void pop_front() { if (++head == v.size()) { v.clear(); head = 0; } else if (head >= 4096 && head * 2 >= v.size()) { v.erase(v.begin(), v.begin() + (ptrdiff_t)head); head = 0; } }
+};
+
+bool umi_matches(const std::string &a, const std::string &b)                 // :169-179
+{
+	if (a.empty() || b.empty()) return true;
+	if (a.size() != b.size()) return false;
+	unsigned mismatches = 0;
+	for (size_t k = 0; k < a.size(); k++)
+		if (!(a[k] == b[k] || a[k] == 'N' || b[k] == 'N')) mismatches++;
+	return mismatches <= 1;
+}
+
+void find_clusters(DupQueue &reads, uint32_t curr_pos)                       // :131-167
+{
+	const size_t n = reads.size();
+	for (size_t k = 0; k < n; k++) {
+		DupRead &rk = reads[k];
+		if (rk.ready) continue;
+		if (rk.start_pos >= curr_pos) continue;
+		size_t best = k;
+		uint32_t best_score = rk.l_seq;
+		rk.set_duplicate(true);
+		rk.ready = true;
+		for (size_t j = k + 1; j < n; j++) {
+			DupRead &rj = reads[j];
+			if (rj.ready) continue;
+			if (rj.pos > rk.start_pos) break;
+			if (rj.start_pos != rk.start_pos) continue;
+			if (rj.strand != rk.strand) continue;
+			if (rj.fraglen > 0 && rk.fraglen > 0 && rj.fraglen != rk.fraglen) continue;
+			if (!umi_matches(rj.umi, rk.umi)) continue;
+			rj.set_duplicate(true);
+			rj.ready = true;
+			if (rj.l_seq > best_score) { best_score = rj.l_seq; best = j; }
+		}
+		reads[best].set_duplicate(false);
+	}
+}
+
+}  // namespace
+
+// the device path of `sam mark duplicates`, as rewrite_from_file; *dups: the output records that carry 0x400
+static int64_t markdup_from_file(const std::string &path, bool ignore_umi, int level, int64_t *dups)
+{
+	sk_ctx *c = host::gpu();
+	int64_t n_rec = 0;
+	uint64_t raw = 0;
+	int handled = 0;
+	if (sk_bam_file_markdup(c, path.c_str(), ignore_umi ? 1 : 0, level, file_window_bytes(), &n_rec, dups, &raw, &handled, nullptr) != SK_OK || !handled) return -1;
+	sk_bam_out_window w;
+	for (;;) {
+		check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
+		if (w.n == 0 && w.bytes == 0) break;
+		BamOut::write_all(w.bgzf, (size_t)w.bytes);
+	}
+	return n_rec;
+}
+
+static void markdup_summary(uint64_t dups, uint64_t total)                    // :112-114
+{
+	if (total == 0) fprintf(stderr, "%llu / %llu (NaN%%) reads were marked as duplicates.\n", (unsigned long long)dups, (unsigned long long)total);
+	else fprintf(stderr, "%llu / %llu (%.1f%%) reads were marked as duplicates.\n", (unsigned long long)dups, (unsigned long long)total,
+	             (double)dups / (double)total * 100.0);
+}
+
+static int mark_duplicates_cmd(int argc, char **argv)
+{
+	std::vector<host::Opt> opts = {{"--uncompressed", false, false, ""}, {"--ignore-umi", false, false, ""}};
+	std::vector<std::string> pos;
+	if (!host::parse_args(argc, argv, 3, opts, pos, 1) || pos.size() != 1) error("Invalid arguments.\n%s", USAGE_MARK_DUPLICATES);
+	const std::string path = expand_home(pos[0]);
+	const int level = opts[0].present ? 0 : 1;
+	const bool ignore_umi = opts[1].present;
+	host::gpu_warmup();
+	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
+	if (file_path_wanted(path)) {
+		int64_t dups = 0;
+		const int64_t n = markdup_from_file(path, ignore_umi, level, &dups);
+		if (n >= 0) {
+			if (trace) fprintf(stderr, "sam mark duplicates: device path, %lld records\n", (long long)n);
+			markdup_summary((uint64_t)dups, (uint64_t)n);
+			return 0;
+		}
+	}
+	if (trace) fprintf(stderr, "sam mark duplicates: host reader\n");
+	BamStream bam(path, true);
+	BamOut out(level);
+	g_bam_out = &out;
+	host::at_exit_flush(finish_bam_out);
+	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
+	out.put(hdr.data(), hdr.size());
+	out.flush();                                                                // (the header in members of its own)
+	uint64_t total_reads = 0, total_duplicates = 0;
+	uint32_t prev_pos = 0;
+	int32_t prev_chr = -1;
+	DupQueue reads;
+	auto flush_reads = [&]() {                                                  // :120-128
+		uint64_t flushed = 0;
+		while (reads.size() && reads[0].ready) {
+			if (reads[0].duplicate()) flushed++;
+			out.put(reads[0].rec.data(), reads[0].rec.size());
+			reads.pop_front();
+		}
+		return flushed;
+	};
+	BamCore c;
+	BamStream::Var v;
+	std::vector<uint8_t> body;
+	while (bam.next_full(c, v, body)) {
+		if (c.flag & 0x900) error("BAM file contains secondary or supplementary reads. These are not currently supported.");   // :51-53
+		const uint32_t left_pos = (uint32_t)c.pos;
+		if (c.tid != prev_chr) {                                                // :58-64
+			find_clusters(reads, UINT32_MAX);
+			total_duplicates += flush_reads();
+			prev_chr = c.tid;
+		} else if (left_pos < prev_pos) error("Input BAM file is not coordinate sorted.");
+		prev_pos = left_pos;
+		const bool unmapped = c.flag & 0x4, reverse = c.flag & 0x10;
+		reads.v.emplace_back();
+		DupRead &r = reads.v.back();
+		r.start_pos = 0;
+		if (!unmapped && reverse) {                                             // :73 read.cigar().end_pos()
+			const uint8_t *cigar = body.data() + v.l_read_name;
+			int64_t e = c.pos;
+			for (uint32_t k = 0; k < v.n_cigar; k++) {
+				const uint32_t op = le32(cigar + 4 * k), code = op & 15;
+				if (code > 8) { reads.v.pop_back(); panic("Unexpected cigar operation"); }
+				if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) e += op >> 4;
+			}
+			r.start_pos = (uint32_t)(int32_t)e;
+		} else if (!unmapped) r.start_pos = left_pos;
+		r.fraglen = 0;
+		if (!unmapped) {                                                        // :79-91
+			if (!ignore_umi) {
+				const size_t aux = (size_t)v.l_read_name + 4 * (size_t)v.n_cigar + (((size_t)v.l_seq + 1) >> 1) + v.l_seq;
+				const uint8_t *val = nullptr;
+				size_t vl = 0;
+				if (find_rx(body.data() + aux, body.size() - aux, val, vl)) r.umi.assign(reinterpret_cast<const char *>(val), vl);
+			}
+			if (r.umi.empty()) r.fraglen = (uint16_t)std::min<int64_t>(std::llabs((long long)c.tlen), 65535);
+		}
+		r.pos = left_pos; r.l_seq = v.l_seq; r.strand = !reverse; r.ready = unmapped;
+		r.rec.assign(bam.head, bam.head + 36);
+		r.rec.insert(r.rec.end(), body.begin(), body.end());
+		total_reads++;
+		if (total_reads % 1000 == 0) {                                          // :101-104
+			total_duplicates += flush_reads();
+			find_clusters(reads, left_pos);
+		}
+	}
+	bam.raise_deferred();
+	find_clusters(reads, UINT32_MAX);                                           // :108-110
+	total_duplicates += flush_reads();
+	out.finish();
+	g_bam_out = nullptr;
+	markdup_summary(total_duplicates, total_reads);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	// blocks, per-sample strings and gzip jobs are hundreds of KiB each: above glibc's default mmap threshold every one of them was a
@@ -1416,6 +1609,7 @@ int main(int argc, char **argv)
 	else if (argc >= 4 && is(1, "qname") && is(2, "from") && is(3, "tags")) rc = rewrite_cmd(argc, argv, SK_REWRITE_QNAME_FROM_TAGS, 4, USAGE_QNAME_FROM_TAGS, true);
 	else if (argc >= 3 && is(1, "trim") && is(2, "qnames")) rc = rewrite_cmd(argc, argv, SK_REWRITE_TRIM_QNAMES, 3, USAGE_TRIM, false);
 	else if (argc >= 2 && is(1, "minimize")) rc = minimize_cmd(argc, argv);
+	else if (argc >= 3 && is(1, "mark") && is(2, "duplicates")) rc = mark_duplicates_cmd(argc, argv);
 	else fprintf(stderr, "%s\n", USAGE_TOP);
 	host::out().flush();
 	// everything is written and closed: what is left is taking the process apart (static destructors, the HIP runtime's exit handlers,

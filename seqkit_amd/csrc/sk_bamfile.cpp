@@ -215,8 +215,10 @@ struct ReadsState : WindowedState {
 // sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot
 // kKeepFileCols), the window plan (output bytes of window w from wo[w] on), one device area for the window being rewritten and
 // compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
+constexpr int kOpMarkdup = -1;                   // RewriteState::op of sk_bam_file_markdup (SK_REWRITE_* are 1 .. 3, 0 is minimize)
 struct RewriteState : WindowedState {
 	int op = 0, level = 1;                       // op 0: sk_bam_file_minimize, with its flags, fill byte and ids (ctx slot kKeepMinimize)
+	const uint16_t *md_flags = nullptr;          // op kOpMarkdup: sk_bam_file_markdup, every record's flag (ctx slot kKeepMinimize)
 	int min_flags = 0;
 	uint8_t min_fill = 255;
 	const uint32_t *ids = nullptr;
@@ -323,6 +325,7 @@ struct Front {
 	const char *who = nullptr;                   // the file call, in trace lines and messages
 	bool ready = false;
 	const uint8_t *d_out = nullptr;
+	uint8_t *d_comp = nullptr;                   // the compressed file's device buffer (fsize + 64 bytes): idle once the stream is verified
 	uint64_t stream_len = 0, first = 0, n_records = 0, fsize = 0, n_host = 0;
 	uint64_t *d_bend = nullptr, *d_entry = nullptr;
 	int64_t nb = 0;
@@ -657,7 +660,7 @@ static int bam_file_front(sk_ctx *c, const char *path, Cleanup &cl, Front &fr, d
 	if (nb) BF_HIP(hipMemcpy(fr.nrec.data(), d_nrec, (size_t)nb * 4, hipMemcpyDeviceToHost));
 	fr.header.assign(hd_keep.begin(), hd_keep.begin() + (ptrdiff_t)first);
 	fr.ready = true;
-	fr.d_out = d_out; fr.stream_len = stream_len; fr.first = first; fr.n_records = n_records; fr.fsize = fsize; fr.n_host = n_host;
+	fr.d_out = d_out; fr.d_comp = d_comp; fr.stream_len = stream_len; fr.first = first; fr.n_records = n_records; fr.fsize = fsize; fr.n_host = n_host;
 	fr.d_bend = d_bend; fr.d_entry = d_entry; fr.nb = nb; fr.rounds = rounds; fr.n_ref = n_ref_hdr;
 	fr.t0 = t0; fr.t_alloc = t_alloc; fr.t_read = t_read; fr.t_inflated = t_inflated; fr.t_header = t_header; fr.t_walk = now_ms();
 	return SK_OK;
@@ -976,8 +979,9 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		if (!s.next_window(w)) return false;
 		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
 		raw_len = s.wo[w + 1] - s.wo[w];
-		e = s.op ? sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st)
-		         : sk::launch_bam_min_write(s.d_out, s.krec, s.kout, s.ids, first, n, s.wo[w], s.min_flags, s.min_fill, s.d_raw, sk::ctx_n_cu(c), st);
+		e = s.op == kOpMarkdup ? sk::launch_bam_md_write(s.d_out, s.krec, s.kout, s.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st)
+		    : s.op ? sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st)
+		           : sk::launch_bam_min_write(s.d_out, s.krec, s.kout, s.ids, first, n, s.wo[w], s.min_flags, s.min_fill, s.d_raw, sk::ctx_n_cu(c), st);
 	}
 	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
 	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
@@ -1182,6 +1186,104 @@ extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint
 	BF_HIP(hipStreamSynchronize(st));
 	s.op = 0; s.min_flags = flags; s.min_fill = baseq_fill;
 	return rw_begin(c, cl, fr, s, R->gen, level, window_bytes, total, t_size, n_records, raw_bytes, handled, info);
+}
+
+// ---- sam mark duplicates (include/seqkit_hip.h: sk_bam_file_markdup; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then the passes of sk_bammarkdup.hip.  Their working memory — two key and two index buffers for the sort (before the
+// sort the second of each holds (tid, pos) and the run flags, and the first index buffer the run indices), five u32 signature columns
+// and the scratch of the sort and the scan: 44 B per record — is needed only until the clusters are found, and lies in the device
+// buffer of the COMPRESSED file, which is idle once the stream is verified (a BAM record takes more compressed bytes than that; where
+// it does not, ctx slot kKeepMinimize serves).  Only the u16 flag column, which the windows read, is kept in that slot: a gigabyte
+// taken and given back for a 20 M-record file cost the command 0.1 s.  The records' bytes and sizes do not
+// change: a record's output offset is its stream offset less the header's, the windows are planned over those, and the write kernel
+// patches the flag.  Declined files: the list in include/seqkit_hip.h.
+extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, int level, uint64_t window_bytes, int64_t *n_records,
+                                   int64_t *n_duplicates, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_markdup", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (n_duplicates) *n_duplicates = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const double t_size = now_ms();
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	uint64_t *d_blk = nullptr;
+	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 8 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+	cl.dev.push_back(d_blk);
+	uint64_t *d_rb = d_blk, *d_count = d_rb + nb;
+	uint32_t *d_decline = (uint32_t *)(d_count + 1);
+	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
+	std::vector<uint64_t> rb;
+	if (int r = block_first_records(c, fr, rb)) return r;
+	if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
+	int krc = SK_OK;
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * up(N * 8 + 8), false, &krc);
+	if (!kb) BF_LEAVE(21);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	RewriteState &s = R->rw;
+	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
+	uint64_t *key[2] = {nullptr, nullptr};
+	uint32_t *idx[2] = {nullptr, nullptr};
+	size_t sort_bytes = 0, scan_bytes = 0;
+	BF_HIP(sk::bam_min_sort(nullptr, &sort_bytes, key, idx, N ? N : 1, 64, nullptr, st));
+	BF_HIP(sk::bam_md_run_scan(nullptr, &scan_bytes, nullptr, nullptr, N ? N : 1, st));
+	const size_t a_key = up(N * 8 + 8), a_idx = up(N * 4 + 4), a_flag = up(N * 2 + 2), temp_bytes = std::max(sort_bytes, scan_bytes);
+	const size_t work = 2 * a_key + 7 * a_idx + up(temp_bytes);
+	const bool in_comp = fr.fsize + 64 >= work && !getenv("SK_MARKDUP_OWN_MEMORY");      // (the knob: for tests of the other placement)
+	uint8_t *fb = (uint8_t *)sk::ctx_keep(c, sk::kKeepMinimize, a_flag + (in_comp ? 0 : work), false, &krc);
+	if (!fb) BF_LEAVE(21);
+	uint8_t *mb = in_comp ? fr.d_comp : fb + a_flag;
+	if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_markdup: %zu bytes of scratch in %s\n", work, in_comp ? "the compressed file's buffer" : "its own buffer");
+	key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
+	idx[0] = (uint32_t *)(mb + 2 * a_key); idx[1] = (uint32_t *)(mb + 2 * a_key + a_idx);
+	sk::MdCols cols;
+	cols.krec = s.krec; cols.kout = s.kout; cols.tidpos = key[1];
+	uint8_t *sig = mb + 2 * a_key + 2 * a_idx;
+	cols.start = (uint32_t *)sig; cols.fl = (uint32_t *)(sig + a_idx); cols.lseq = (uint32_t *)(sig + 2 * a_idx);
+	cols.uoff = (uint32_t *)(sig + 3 * a_idx); cols.ulen = (uint32_t *)(sig + 4 * a_idx);
+	cols.nflag = (uint16_t *)fb;
+	void *temp = sig + 5 * a_idx;
+	// ---- signatures, order, runs: the decision to serve the file
+	BF_HIP(sk::launch_bam_md_sig(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, ignore_umi ? 1 : 0, fr.first, cols, d_decline, st));
+	BF_HIP(sk::launch_bam_md_order(cols.tidpos, N, idx[1], d_decline, st));
+	uint32_t decline = 0, runs = 0;
+	if (N) {
+		size_t tb = temp_bytes;
+		BF_HIP(sk::bam_md_run_scan(temp, &tb, idx[1], idx[0], N, st));
+		BF_HIP(hipMemcpyAsync(&runs, idx[0] + (N - 1), 4, hipMemcpyDeviceToHost, st));
+	}
+	BF_HIP(hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipStreamSynchronize(st));                                  // (rb is read by the copy above)
+	if (runs >= 0x7fffffffu) decline |= 64u;
+	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_markdup: declined (bits %#x)\n", decline);
+	if (decline) BF_LEAVE(30 + decline);
+	// ---- keys, the sort (only the bits the keys use: the all-ones key of the unmapped reads stays the largest), clusters, count
+	int bits = 34;
+	while (bits < 64 && ((uint64_t)1 << (bits - 33)) <= (uint64_t)runs) bits++;
+	uint64_t dups = 0;
+	if (N) {
+		BF_HIP(sk::launch_bam_md_keys(idx[0], cols, N, key[0], idx[0], st));
+		int cur = 0;
+		size_t tb = temp_bytes;
+		BF_HIP(sk::bam_min_sort(temp, &tb, key, idx, N, bits, &cur, st));
+		BF_HIP(sk::launch_bam_md_cluster(fr.d_out, cols, key[cur], idx[cur], N, d_count, sk::ctx_n_cu(c), st));
+		BF_HIP(hipMemcpyAsync(&dups, d_count, 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	s.op = kOpMarkdup; s.md_flags = cols.nflag;
+	const int rc = rw_begin(c, cl, fr, s, R->gen, level, window_bytes, fr.stream_len - fr.first, t_size, n_records, raw_bytes, handled, info);
+	if (rc == SK_OK && *handled && n_duplicates) *n_duplicates = (int64_t)dups;
+	return rc;
 }
 
 extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)

@@ -218,6 +218,28 @@ hipError_t launch_bam_min_index(const uint8_t *stream, const uint64_t *bend, con
                                 const uint32_t *ids, const uint64_t *bo, uint64_t *krec, uint64_t *kout, hipStream_t st);
 hipError_t launch_bam_min_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint32_t *ids, int64_t first, int64_t n,
                                 uint64_t o0, int flags, uint8_t fill, uint8_t *out, int n_cu, hipStream_t st);
+// ---- sam mark duplicates: the record passes of sk_bam_file_markdup (sk_bammarkdup.hip) ----
+// The per-record columns, in file order: stream and output offsets, (tid << 32 | (u32) pos), start_pos, fraglen | strand << 16 |
+// mapped << 17 (bit 31 is the cluster pass's), l_seq, the UMI's offset in the record and its length, and the flag to write.
+struct MdCols {
+	uint64_t *krec, *kout, *tidpos;
+	uint32_t *start, *fl, *lseq, *uoff, *ulen;
+	uint16_t *nflag;
+};
+// sig: the columns and the decline bits 1, 4, 8, 16, 32 of include/seqkit_hip.h (first: the stream offset of the first record).  order:
+// runflag[k] = 1 where record k's tid differs from its predecessor's; decline bit 2.  run_scan: run = the inclusive sum of runflag (temp
+// == nullptr: only *temp_bytes).  keys: (key, index) for bam_min_sort, key = (run - 1) << 33 | start_pos << 1 | strand, all ones for an
+// unmapped read.  cluster: over the sorted pairs, every mapped read's flag into cols.nflag, then *count = the records with 0x400.
+// write: as launch_bam_rw_write, bytes 18-19 of every record from nflag.
+hipError_t launch_bam_md_sig(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int ignore_umi,
+                             uint64_t first, const MdCols &cols, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_md_order(const uint64_t *tidpos, uint64_t n, uint32_t *runflag, uint32_t *decline, hipStream_t st);
+hipError_t bam_md_run_scan(void *temp, size_t *temp_bytes, const uint32_t *runflag, uint32_t *run, uint64_t n, hipStream_t st);
+hipError_t launch_bam_md_keys(const uint32_t *run, const MdCols &cols, uint64_t n, uint64_t *key, uint32_t *idx, hipStream_t st);
+hipError_t launch_bam_md_cluster(const uint8_t *stream, const MdCols &cols, const uint64_t *key, const uint32_t *idx, uint64_t n, uint64_t *count,
+                                 int n_cu, hipStream_t st);
+hipError_t launch_bam_md_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint16_t *nflag, int64_t first, int64_t n,
+                               uint64_t o0, uint8_t *out, int n_cu, hipStream_t st);
 // BGZF members of raw[0 .. raw_len): the cut into blocks of at most 0xff00 bytes (blocks: device sk_deflate_block[n]), and, after the
 // deflate (or at level 0 the CRC alone), the members back to back into out: msz[n + 1] scratch, msz[n] = their total bytes afterwards
 hipError_t launch_bgzf_cut(uint64_t raw_len, void *blocks, int64_t n, hipStream_t st);
@@ -255,7 +277,7 @@ enum KeepSlot {
 	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
 	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
 	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize: per-record columns, windows
-	kKeepMinimize = 12,                                 // sk_bam_file_minimize: the sort's keys and indices, then the read ids
+	kKeepMinimize = 12,                                 // sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small)
 	kKeepSlots = 13
 };
 hipStream_t ctx_stream(sk_ctx *c);

@@ -7,7 +7,15 @@ to sk_bam_file_reduce's on the same file in one process.
 The fragments file is tools/bam_e2e.py's (100 k paired records, one in two kept, repeated); the count file is the same unit once per
 reference, with tid = the repeat's index, so it is coordinate-sorted with positions restarting per reference; the BED file holds
 about 20 k regions over those references.  usage: bam_cmd_e2e.py [million records (20)] [runs per path (3)] [--lib-only: the library
-calls alone, e.g. under rocprofv3 --kernel-trace --stats] [--no-gz: without the `sam to fastq <prefix>` row]
+calls alone, e.g. under rocprofv3 --kernel-trace --stats] [--no-gz: without the `sam to fastq <prefix>` row] [--markdup: only the
+`sam mark duplicates` rows, see below] [--markdup-file=PATH: only write that row's file to PATH, for a profiler run of the command]
+
+--markdup: the count file (position-sorted, one reference per repeat) with duplicates: every fourth pair lies at the position and has
+the fragment length of the pair before it, and the pairs of every second group of four carry an RX:Z UMI (a duplicate pair its
+original's).  So half of the records are in groups of two and a quarter are marked; the other groups have one member.  Rows: `sam
+mark duplicates` to /dev/null, device path against the host reader, and `sam trim qnames` to /dev/null on the same file (no name
+has a space: every record passes unchanged through the same inflate, window, deflate and pack pipeline, without signatures, sort and
+clusters).  With --check both paths also write a file each, and the inflated outputs and the stderr lines are compared.
 
 The `sam to interleaved fastq` row is also run with stdout to /dev/null (no oracle there: the row before checked the outputs), which
 takes the writer's cost out of both paths."""
@@ -32,7 +40,10 @@ build.build_all()
 SAM = os.path.join(build.BINDIR, "sam")
 lib_only = "--lib-only" in sys.argv
 no_gz = "--no-gz" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--lib-only", "--no-gz")]
+markdup = "--markdup" in sys.argv
+markdup_check = "--check" in sys.argv
+markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 millions = int(argv[0]) if len(argv) > 0 else 20
 runs = int(argv[1]) if len(argv) > 1 else 3
 PAIRS = 50_000
@@ -51,16 +62,25 @@ def bgzf(data, level=1):
 
 unit = bytearray()
 starts, ends = [], []
+dup_mode = markdup or markdup_file is not None
+tl_prev, umi_prev = 0, b""
 for i in range(PAIRS):
     tl = int(rng.lognormal(np.log(170), 0.35))
+    pos, aux = i, b""
+    if dup_mode:
+        umi = bytes(b"ACGT"[k] for k in rng.integers(0, 4, size=8)) if (i & 4) == 0 else b""
+        if i % 4 == 3:                                                      # a duplicate of the pair before it
+            pos, tl, umi = i - 1, tl_prev, umi_prev
+        tl_prev, umi_prev = tl, umi
+        aux = b"RXZ" + umi + b"\0" if umi else b""
     for mate in (0, 1):
         name = b"read%d\0" % i
         nib = codes[rng.integers(0, 4, size=150)]
         packed = ((nib[0::2] << 4) | nib[1::2]).astype(np.uint8).tobytes()
         q = rng.integers(2, 41, size=150, dtype=np.uint8).tobytes()
         flag = 1 | 2 | (64 | 32 if mate == 0 else 128 | 16)
-        body = struct.pack("<iiBBHHHiiii", 0, i, len(name), 60 if i % 7 else 10, 4680, 1, flag, 150, 0, i + (tl if mate == 0 else -tl),
-                           tl if mate == 0 else -tl) + name + struct.pack("<I", 150 << 4) + packed + q
+        body = struct.pack("<iiBBHHHiiii", 0, pos, len(name), 60 if i % 7 else 10, 4680, 1, flag, 150, 0, pos + (tl if mate == 0 else -tl),
+                           tl if mate == 0 else -tl) + name + struct.pack("<I", 150 << 4) + packed + q + aux
         starts.append(len(unit))
         unit += struct.pack("<i", len(body)) + body
         ends.append(len(unit))
@@ -186,6 +206,68 @@ def compare(label, args):
 
 
 n = reps * 2 * PAIRS
+
+
+def write_count_file(path):
+    with open(path, "wb") as f:
+        f.write(header(reps))
+        with ThreadPoolExecutor(16) as ex:
+            for blob in ex.map(with_tid, range(reps)):
+                f.write(blob)
+        f.write(bgzf(b""))
+
+
+def inflated_digest(path):
+    """sha256 of the BGZF file's inflated bytes"""
+    p = subprocess.Popen(["gzip", "-dc", path], stdout=subprocess.PIPE)
+    h = sha256()
+    for chunk in iter(lambda: p.stdout.read(1 << 24), b""):
+        h.update(chunk)
+    assert p.wait() == 0
+    return h.hexdigest()[:16]
+
+
+def markdup_rows():
+    t0 = time.perf_counter()
+    write_count_file(bam)
+    print(f"mark duplicates file: {n} BAM records on {reps} references, sorted, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; "
+          f"1 pair in 4 duplicates the pair before it (half of the records in groups of two, the others alone), RX:Z on every second group of four pairs; "
+          f"{runs} runs per path, alternating", flush=True)
+    rows = {}
+    for k in range(runs):
+        for label, args, env in (("sam mark duplicates  device", ["mark", "duplicates", bam], None),
+                                 ("sam mark duplicates  host  ", ["mark", "duplicates", bam], {"SEQKIT_HOST_INFLATE": "1"}),
+                                 ("sam trim qnames      device", ["trim", "qnames", bam], None)):
+            dt, cpu, rc, _, err = timed([SAM] + args, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+            served = [ln for ln in err.decode(errors="replace").split("\n") if ln.startswith("sam ")]
+            assert rc == 0 and served and ("host reader" if env else "device path") in served[0], (label, rc, err[-400:])
+            rows.setdefault(label, []).append((dt, cpu, [ln for ln in err.decode(errors="replace").split("\n") if "reads were marked" in ln]))
+    for label, r in rows.items():
+        print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r) + ("  " + r[0][2][0] if r[0][2] else ""), flush=True)
+    md = [x[0] for x in rows["sam mark duplicates  device"]]
+    tq = [x[0] for x in rows["sam trim qnames      device"]]
+    print("mark duplicates / trim qnames, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(md, tq))
+          + f"; medians {float(np.median(md)) / float(np.median(tq)):.2f}x", flush=True)
+    if markdup_check:
+        got = []
+        for env in (None, {"SEQKIT_HOST_INFLATE": "1"}):
+            dt, cpu, rc, _, err = timed([SAM, "mark", "duplicates", bam], env, sink=out)
+            got.append((rc, inflated_digest(out), err))
+        assert got[0] == got[1], got
+        print(f"sam mark duplicates > file: inflated outputs and stderr identical on both paths ({got[0][1]})", flush=True)
+        os.remove(out)
+    os.remove(bam)
+    os.rmdir(d)
+
+
+if markdup_file is not None:
+    write_count_file(markdup_file)
+    print(f"wrote {markdup_file}: {n} records, {os.path.getsize(markdup_file) / 1e6:.0f} MB", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if markdup:
+    markdup_rows()
+    sys.exit(0)
 t0 = time.perf_counter()
 with open(bam, "wb") as f:
     f.write(header(1))
@@ -240,12 +322,7 @@ if lib_only:
     sys.exit(0)
 
 t0 = time.perf_counter()
-with open(bam, "wb") as f:
-    f.write(header(reps))
-    with ThreadPoolExecutor(16) as ex:
-        for blob in ex.map(with_tid, range(reps)):
-            f.write(blob)
-    f.write(bgzf(b""))
+write_count_file(bam)
 brng = np.random.default_rng(5)
 with open(bed, "w") as f:
     for k in range(20_000):
