@@ -448,34 +448,31 @@ class Context:
                    "kind": arr(w.kind, n, np.uint8), "key": arr(w.key, n, np.uint64),
                    "names": C.string_at(w.names, int(name_off[-1])) if name_off[-1] else b"", "name_off": name_off}
 
+    def _bam_out_call(self, name: str, path: str, args, with_duplicates: bool = False):
+        """One of the calls that set rewrite windows up (sk_bam_file_rewrite, _minimize, _markdup): its own arguments, which end with the
+        window size, then the out-parameters they share.  (handled, records, [duplicates,] inflated output bytes, info f64[8])."""
+        n_rec, n_dup, raw_bytes, handled = C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_int32(0)
+        info = (C.c_double * 8)()
+        counts = [n_rec, n_dup] if with_duplicates else [n_rec]
+        outs = [C.byref(v) for v in counts + [raw_bytes, handled]]
+        self._check(getattr(self._lib, name)(self._h, os.fsencode(path), *args, *outs, info), name)
+        return (bool(handled.value), *(int(v.value) for v in counts), int(raw_bytes.value), [float(x) for x in info])
+
     def bam_file_rewrite(self, path: str, op, level: int = 1, window_bytes: int = 0):
         """sk_bam_file_rewrite: (handled, records, inflated output bytes, info f64[8]); then bam_file_rewrite_windows() yields the windows.
         op: a REWRITE_OP key or its number."""
-        n_rec, raw_bytes, handled = C.c_int64(0), C.c_uint64(0), C.c_int32(0)
-        info = (C.c_double * 8)()
-        o = REWRITE_OP[op] if isinstance(op, str) else int(op)
-        self._check(self._lib.sk_bam_file_rewrite(self._h, os.fsencode(path), o, level, window_bytes, C.byref(n_rec), C.byref(raw_bytes),
-                                                  C.byref(handled), info), "sk_bam_file_rewrite")
-        return bool(handled.value), int(n_rec.value), int(raw_bytes.value), [float(x) for x in info]
+        return self._bam_out_call("sk_bam_file_rewrite", path, (REWRITE_OP[op] if isinstance(op, str) else int(op), level, window_bytes))
 
     def bam_file_minimize(self, path: str, read_ids: bool, base_qualities: bool, tags: bool, baseq_fill: int = 255, level: int = 1,
                           window_bytes: int = 0):
         """sk_bam_file_minimize: (handled, records, inflated output bytes, info f64[8]); then bam_file_rewrite_windows() yields the windows."""
-        n_rec, raw_bytes, handled = C.c_int64(0), C.c_uint64(0), C.c_int32(0)
-        info = (C.c_double * 8)()
         flags = (MINIMIZE_READ_IDS if read_ids else 0) | (MINIMIZE_BASE_QUALITIES if base_qualities else 0) | (MINIMIZE_TAGS if tags else 0)
-        self._check(self._lib.sk_bam_file_minimize(self._h, os.fsencode(path), flags, baseq_fill, level, window_bytes, C.byref(n_rec),
-                                                   C.byref(raw_bytes), C.byref(handled), info), "sk_bam_file_minimize")
-        return bool(handled.value), int(n_rec.value), int(raw_bytes.value), [float(x) for x in info]
+        return self._bam_out_call("sk_bam_file_minimize", path, (flags, baseq_fill, level, window_bytes))
 
     def bam_file_markdup(self, path: str, ignore_umi: bool = False, level: int = 1, window_bytes: int = 0):
         """sk_bam_file_markdup: (handled, records, duplicates, inflated output bytes, info f64[8]); then bam_file_rewrite_windows() yields the
         windows."""
-        n_rec, n_dup, raw_bytes, handled = C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_int32(0)
-        info = (C.c_double * 8)()
-        self._check(self._lib.sk_bam_file_markdup(self._h, os.fsencode(path), 1 if ignore_umi else 0, level, window_bytes, C.byref(n_rec),
-                                                  C.byref(n_dup), C.byref(raw_bytes), C.byref(handled), info), "sk_bam_file_markdup")
-        return bool(handled.value), int(n_rec.value), int(n_dup.value), int(raw_bytes.value), [float(x) for x in info]
+        return self._bam_out_call("sk_bam_file_markdup", path, (1 if ignore_umi else 0, level, window_bytes), with_duplicates=True)
 
     def bam_file_rewrite_windows(self):
         """sk_bam_file_rewrite_next (after bam_file_rewrite, bam_file_minimize or bam_file_markdup) until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""

@@ -14,7 +14,9 @@
 // file is first offered to the device whole (sk_bam_file_reduce, sk_bam_file_columns): it inflates and walks it; `sam fragments`
 // and `sam count` then run their order checks and their text on the device too, and whatever is irregular falls back to the reader
 // here before anything has been written.  `sam to` takes the file the same way: the device writes every record's text, window by
-// window, and the mate pairing stays here.
+// window, and the mate pairing stays here.  The commands that write BAM to stdout (trim qnames, tags from qname, qname from tags, minimize,
+// mark duplicates) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
+// device does not take the reader and writer of HostBamRewrite around the command's own per-record loop.
 #include <unistd.h>
 #include <malloc.h>
 #include <zlib.h>
@@ -56,6 +58,30 @@ static void check(int rc, const char *what)
 
 // ---- BGZF/BAM container walk ---------------------------------------------------------------------------------
 struct BamCore { int32_t tid, pos; uint16_t flag; int32_t mtid, mpos, tlen, end_pos; uint8_t mapq; };
+
+// cigar().end_pos(): pos and the lengths of the operations that consume the reference (M D N = X).  *bad, where given: an operation
+// code above 8, at which rust-htslib's cigar() panics.
+static int64_t cigar_end_pos(const uint8_t *cigar, uint32_t n_cigar, int64_t pos, bool *bad = nullptr)
+{
+	for (uint32_t k = 0; k < n_cigar; k++) {
+		const uint32_t op = le32(cigar + 4 * k), code = op & 15;
+		if (code > 8 && bad) *bad = true;
+		if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) pos += op >> 4;
+	}
+	return pos;
+}
+
+// the columns of a line, split at tabs
+static std::vector<std::string> split_tabs(const std::string &t)
+{
+	std::vector<std::string> cols;
+	for (size_t a = 0;;) {
+		const size_t b = t.find('\t', a);
+		cols.push_back(t.substr(a, b == std::string::npos ? b : b - a));
+		if (b == std::string::npos) return cols;
+		a = b + 1;
+	}
+}
 
 class BamStream {
 public:
@@ -100,8 +126,11 @@ public:
 	// returns false and the caller, once it has written what the records before the error produce, calls
 	// raise_deferred() — the point the record-at-a-time reference would have reached.
 	void raise_deferred() const { if (!err_.empty()) error("%s", err_.c_str()); }
-	// the sizes of a record's variable part (qname, cigar, packed bases, qualities, aux)
-	struct Var { uint32_t l_read_name, n_cigar, l_seq; };
+	// the sizes of a record's variable part (qname, cigar, packed bases, qualities, aux), and where in it the aux data begin
+	struct Var {
+		uint32_t l_read_name, n_cigar, l_seq;
+		size_t aux_off() const { return (size_t)l_read_name + 4 * (size_t)n_cigar + (((size_t)l_seq + 1) >> 1) + l_seq; }
+	};
 	// next record; want_end computes cigar().end_pos() (needed only by the on-target sweep for unpaired reads)
 	bool next(BamCore &c, bool want_end)
 	{
@@ -113,13 +142,7 @@ public:
 			var_.resize(l_read_name + 4 * n_cigar);
 			if (!need(var_.data(), var_.size())) return false;
 			rest -= (uint32_t)var_.size();
-			int64_t e = c.pos;
-			for (uint32_t k = 0; k < n_cigar; k++) {
-				const uint32_t op = le32(var_.data() + l_read_name + 4 * k);
-				const uint32_t code = op & 15, len = op >> 4;
-				if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) e += len;   // M D N = X consume the reference
-			}
-			c.end_pos = (int32_t)e;
+			c.end_pos = (int32_t)cigar_end_pos(var_.data() + l_read_name, n_cigar, c.pos);
 		}
 		return skip(rest);
 	}
@@ -153,8 +176,7 @@ public:
 		if (!next_core(c, v)) return false;
 		const uint32_t rest = le32(head) - 32;
 		// htslib bam_read1: a record whose variable part cannot hold its own fields is invalid
-		if (v.l_read_name < 1 || v.l_seq > 0x7fffffffu ||
-		    (uint64_t)v.n_cigar * 4 + v.l_read_name + (((uint64_t)v.l_seq + 1) >> 1) + v.l_seq > rest) return rd_fail("Invalid BAM record.");
+		if (v.l_read_name < 1 || v.l_seq > 0x7fffffffu || v.aux_off() > rest) return rd_fail("Invalid BAM record.");
 		// the record's size comes from the file: take it in steps, so that a damaged size field runs into the end of the data
 		// ("BAM file ended prematurely.") instead of into one allocation of gigabytes
 		body.clear();
@@ -241,6 +263,8 @@ static const size_t kBatch = 4u << 20;
 struct Columns {
 	std::vector<uint16_t> flag;
 	std::vector<int32_t> tid, mtid, tlen, pos, mpos, end_pos;
+	std::vector<BamCore> chunk;                  // fill_batch: the reader's last chunk, and whether the stream goes on
+	bool more = true;
 	void clear() { flag.clear(); tid.clear(); mtid.clear(); tlen.clear(); pos.clear(); mpos.clear(); end_pos.clear(); }
 	void push(const BamCore &c, bool extra)
 	{
@@ -248,6 +272,16 @@ struct Columns {
 		if (extra) { pos.push_back(c.pos); mpos.push_back(c.mpos); end_pos.push_back(c.end_pos); }
 	}
 };
+
+// The next batch of a stream's records as columns: kBatch records, and those that come with the last chunk.  Their number; 0: the stream
+// has ended (or failed: raise_deferred() says).
+static int64_t fill_batch(BamStream &bam, Columns &col, bool want_end, bool extra)
+{
+	col.clear();
+	while (col.more && col.flag.size() < kBatch && (col.more = bam.next_chunk(col.chunk, want_end)))
+		for (const BamCore &c : col.chunk) col.push(c, extra);
+	return (int64_t)col.flag.size();
+}
 
 static std::string expand_home(const std::string &path)      // PathArgs::get_path, src/common.rs:28-38
 {
@@ -290,6 +324,21 @@ struct DevBufs {
 
 static bool file_path_wanted(const std::string &path) { return path != "-" && !getenv("SEQKIT_HOST_INFLATE"); }
 
+static bool bamfile_trace() { static const bool on = getenv("SK_BAMFILE_TRACE") != nullptr; return on; }
+
+// The device-or-host gate of a command: a file the device path is wanted for goes to `from_file` (the number of records, or -1: nothing
+// has been written), and SK_BAMFILE_TRACE says which way the command went.  -1: the caller's host reader serves the file.
+template <class FromFile>
+static int64_t device_path(const char *who, const std::string &path, FromFile from_file)
+{
+	const int64_t n = file_path_wanted(path) ? from_file() : -1;
+	if (bamfile_trace()) {
+		if (n >= 0) fprintf(stderr, "%s: device path, %lld records\n", who, (long long)n);
+		else fprintf(stderr, "%s: host reader\n", who);
+	}
+	return n;
+}
+
 // the window size the windowed file calls are asked for (SK_BAMFILE_WINDOW bytes; 0: the library's default)
 static uint64_t file_window_bytes()
 {
@@ -326,13 +375,12 @@ static int statistics(int argc, char **argv)
 	if (targets_path.empty() && file_path_wanted(bam_path)) {
 		int handled = 0;
 		uint64_t fc[3] = {0, 0, 0};
-		const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
 		auto now_ms = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
 		const double t0 = now_ms();
 		sk_ctx *c = host::gpu();
 		const double t1 = now_ms();
 		check(sk_bam_file_reduce(c, bam_path.c_str(), 0, fc, nullptr, nullptr, &handled, nullptr), "sk_bam_file_reduce");
-		if (trace) fprintf(stderr, "sam statistics: waited %.1f ms for the device contexts, sk_bam_file_reduce %.1f ms\n", t1 - t0, now_ms() - t1);
+		if (bamfile_trace()) fprintf(stderr, "sam statistics: waited %.1f ms for the device contexts, sk_bam_file_reduce %.1f ms\n", t1 - t0, now_ms() - t1);
 		if (handled) { print_counters(fc); return 0; }
 	}
 	BamStream bam(bam_path);
@@ -349,10 +397,7 @@ static int statistics(int argc, char **argv)
 			if (!ok) break;
 			const size_t off = host::trim_start_off(line), end = host::trim_end_len(line);
 			if (end <= off || line[0] == '#') continue;                                                // :37
-			const std::string t = line.substr(off, end - off);
-			std::vector<std::string> cols;
-			size_t a = 0;
-			for (;;) { const size_t b = t.find('\t', a); cols.push_back(t.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; }
+			const std::vector<std::string> cols = split_tabs(line.substr(off, end - off));
 			if (cols.size() < 3) error("Invalid line in BED file %s:\n%s", targets_path.c_str(), line.c_str());
 			int tid = -1;
 			for (size_t k = 0; k < bam.names.size(); k++) if (bam.names[k] == cols[0]) { tid = (int)k; break; }
@@ -368,14 +413,7 @@ static int statistics(int argc, char **argv)
 	uint64_t counters[3] = {0, 0, 0};
 	uint64_t total_fragments = 0, on_target_fragments = 0;
 	Columns col;
-	std::vector<BamCore> chunk;
-	bool more = true;
-	while (more) {
-		col.clear();
-		while (col.flag.size() < kBatch && (more = bam.next_chunk(chunk, on_target)))
-			for (const BamCore &c : chunk) col.push(c, on_target);
-		const int64_t n = (int64_t)col.flag.size();
-		if (n == 0) break;
+	for (int64_t n; (n = fill_batch(bam, col, on_target, on_target)) > 0;) {
 		// S1 on the device: src/sam_statistics.rs:63-69
 		check(sk_bam_flag_tlen(host::gpu(), col.flag.data(), nullptr, nullptr, nullptr, n, 0, counters, nullptr, nullptr), "sk_bam_flag_tlen");
 		if (!on_target) continue;
@@ -450,14 +488,8 @@ static int fragment_lengths(int argc, char **argv)
 	}
 	std::unique_ptr<BamStream> bam_p(by_file ? nullptr : new BamStream(pos[0]));                      // :30
 	Columns col;
-	std::vector<BamCore> chunk;
-	bool more = !by_file, stopped = false;
-	while (more && !stopped) {
-		col.clear();
-		while (col.flag.size() < kBatch && (more = bam_p->next_chunk(chunk, false)))
-			for (const BamCore &c : chunk) col.push(c, false);
-		const int64_t n = (int64_t)col.flag.size();
-		if (n == 0) break;
+	bool stopped = false;
+	for (int64_t n; !by_file && !stopped && (n = fill_batch(*bam_p, col, false, false)) > 0;) {
 		// H1 on the device: src/sam_fragment_lengths.rs:29-43
 		std::vector<uint64_t> bh(max_frag + 1, 0);
 		uint64_t bt = 0;
@@ -542,27 +574,12 @@ static int fragments(int argc, char **argv)                        // src/sam_fr
 	if (!parse_i64(opts[0].value, min_size)) panic("called `Result::unwrap()` on an `Err` value: ParseIntError (--min-size)");   // :17
 	if (!parse_i64(opts[1].value, max_size)) panic("called `Result::unwrap()` on an `Err` value: ParseIntError (--max-size)");   // :18
 	host::gpu_warmup();
-	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
-	if (file_path_wanted(pos[0])) {
-		const int64_t n = fragments_from_file(pos[0], min_size, max_size);
-		if (n >= 0) {
-			if (trace) fprintf(stderr, "sam fragments: device path, %lld records\n", (long long)n);
-			return 0;
-		}
-	}
-	if (trace) fprintf(stderr, "sam fragments: host reader\n");
+	if (device_path("sam fragments", pos[0], [&] { return fragments_from_file(pos[0], min_size, max_size); }) >= 0) return 0;
 	BamStream bam(pos[0]);
 	Columns col;
-	std::vector<BamCore> chunk;
-	bool more = true;
 	std::vector<uint8_t> bits;
 	char buf[128];
-	while (more) {
-		col.clear();
-		while (col.flag.size() < kBatch && (more = bam.next_chunk(chunk, false)))
-			for (const BamCore &c : chunk) col.push(c, true);
-		const int64_t n = (int64_t)col.flag.size();
-		if (n == 0) break;
+	for (int64_t n; (n = fill_batch(bam, col, false, true)) > 0;) {
 		bits.assign((size_t)(n + 7) / 8, 0);
 		uint64_t kept = 0;
 		// the record filter on the device: src/sam_fragments.rs:27-38
@@ -670,10 +687,7 @@ static int count(int argc, char **argv)                            // src/sam_co
 			if (!ok) break;
 			if (!line.empty() && line[0] == '#') continue;
 			const size_t off = host::trim_start_off(line), end = host::trim_end_len(line);
-			const std::string t = end > off ? line.substr(off, end - off) : std::string();
-			std::vector<std::string> cols;
-			size_t a = 0;
-			for (;;) { const size_t b = t.find('\t', a); cols.push_back(t.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; }
+			const std::vector<std::string> cols = split_tabs(end > off ? line.substr(off, end - off) : std::string());
 			if (cols.size() < 3) error("Invalid region in BED file:\n%s", line.c_str());
 			uint64_t s, e;
 			if (!host::parse_uint(cols[1].c_str(), 0xffffffffull, s) || !host::parse_uint(cols[2].c_str(), 0xffffffffull, e))
@@ -683,15 +697,7 @@ static int count(int argc, char **argv)                            // src/sam_co
 	}
 	fprintf(stderr, "Counting %s...\n", single_end ? "reads" : "DNA fragments");                                            // :34-35
 	host::gpu_warmup();
-	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
-	if (file_path_wanted(pos[0])) {
-		const int64_t n = count_from_file(pos[0], regions, min_mapq, max_frag_len, single_end, count_centers);
-		if (n >= 0) {
-			if (trace) fprintf(stderr, "sam count: device path, %lld records\n", (long long)n);
-			return 0;
-		}
-	}
-	if (trace) fprintf(stderr, "sam count: host reader\n");
+	if (device_path("sam count", pos[0], [&] { return count_from_file(pos[0], regions, min_mapq, max_frag_len, single_end, count_centers); }) >= 0) return 0;
 	BamStream bam(pos[0]);                                                                                                 // :36
 	for (const std::string &nm : bam.names)                                                                                // :37-38
 		if (!host::utf8_valid(reinterpret_cast<const uint8_t *>(nm.data()), nm.size())) panic("called `Result::unwrap()` on an `Err` value: Utf8Error");
@@ -943,16 +949,10 @@ static int to_reads(int argc, char **argv)
 		host::at_exit_flush(close_sinks);
 	}
 	host::gpu_warmup();
-	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
-	if (file_path_wanted(pos[0])) {
-		const int64_t n = to_reads_from_file(pos[0], format, interleaved, out_1, out_2, out_single);
-		if (n >= 0) {
-			if (trace) fprintf(stderr, "sam to: device path, %lld records\n", (long long)n);
-			close_sinks();
-			return 0;
-		}
+	if (device_path("sam to", pos[0], [&] { return to_reads_from_file(pos[0], format, interleaved, out_1, out_2, out_single); }) >= 0) {
+		close_sinks();
+		return 0;
 	}
-	if (trace) fprintf(stderr, "sam to: host reader\n");
 	BamStream bam(pos[0]);                                                                                   // :96
 	PendingReads reads_1, reads_2;
 
@@ -1168,16 +1168,17 @@ static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
 	return false;
 }
 
-// the rewrite over the FILE: the device rewrites and compresses every window (sk_bam_file_rewrite), and the members go to stdout as they
-// arrive.  -1: nothing has been written, and the caller's reader serves the file (one the file path does not take, a device without room,
-// or a record the reference would stop at).  Otherwise the number of records.
-static int64_t rewrite_from_file(const std::string &path, int op, int level)
+// The device path of a BAM-writing command: `start` makes the file call that sets the windows up (sk_bam_file_rewrite, _minimize or
+// _markdup), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
+// the file path does not take, a device without room, or a record the reference would stop at).  Otherwise the number of records.
+template <class Start>
+static int64_t bam_out_from_file(Start start)
 {
 	sk_ctx *c = host::gpu();
 	int64_t n_rec = 0;
 	uint64_t raw = 0;
 	int handled = 0;
-	if (sk_bam_file_rewrite(c, path.c_str(), op, level, file_window_bytes(), &n_rec, &raw, &handled, nullptr) != SK_OK || !handled) return -1;
+	if (start(c, file_window_bytes(), &n_rec, &raw, &handled) != SK_OK || !handled) return -1;
 	sk_bam_out_window w;
 	for (;;) {
 		check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
@@ -1185,6 +1186,37 @@ static int64_t rewrite_from_file(const std::string &path, int op, int level)
 		BamOut::write_all(w.bgzf, (size_t)w.bytes);
 	}
 	return n_rec;
+}
+
+// The host path of a BAM-writing command: the reader with the header's bytes kept, the writer on stdout (finished too where the process
+// is left through error() or panic()), and the header written in members of its own.  close(): the error the reader met — after the
+// records before it have been put —, then what is left and the EOF block.
+struct HostBamRewrite {
+	BamStream bam;
+	BamOut out;
+	HostBamRewrite(const std::string &path, int level) : bam(path, true), out(level)
+	{
+		g_bam_out = &out;
+		host::at_exit_flush(finish_bam_out);
+		const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
+		out.put(hdr.data(), hdr.size());
+		out.flush();
+	}
+	void close() { bam.raise_deferred(); out.finish(); g_bam_out = nullptr; }
+};
+
+// A record with a new name into rec: the block_size and core as read, the name and its NUL, the `n_tail` bytes kept of what followed the
+// old name, and `app` (aux data appended); block_size and l_read_name say so.
+static void renamed_record(std::vector<uint8_t> &rec, const uint8_t *head, const std::string &name, const uint8_t *tail, size_t n_tail, const std::vector<uint8_t> &app)
+{
+	const uint32_t bs = (uint32_t)(32 + name.size() + 1 + n_tail + app.size());
+	rec.assign(head, head + 36);
+	for (int k = 0; k < 4; k++) rec[k] = (uint8_t)(bs >> (8 * k));
+	rec[12] = (uint8_t)(name.size() + 1);
+	rec.insert(rec.end(), name.begin(), name.end());
+	rec.push_back(0);
+	rec.insert(rec.end(), tail, tail + n_tail);
+	rec.insert(rec.end(), app.begin(), app.end());
 }
 
 static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usage, bool has_uncompressed)
@@ -1197,22 +1229,11 @@ static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usa
 	const int level = has_uncompressed && opts[0].present ? 0 : 1;
 	const char *who = op == SK_REWRITE_TRIM_QNAMES ? "sam trim qnames" : op == SK_REWRITE_TAGS_FROM_QNAME ? "sam tags from qname" : "sam qname from tags";
 	host::gpu_warmup();
-	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
-	if (file_path_wanted(path)) {
-		const int64_t n = rewrite_from_file(path, op, level);
-		if (n >= 0) {
-			if (trace) fprintf(stderr, "%s: device path, %lld records\n", who, (long long)n);
-			return 0;
-		}
-	}
-	if (trace) fprintf(stderr, "%s: host reader\n", who);
-	BamStream bam(path, true);
-	BamOut out(level);
-	g_bam_out = &out;
-	host::at_exit_flush(finish_bam_out);
-	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
-	out.put(hdr.data(), hdr.size());
-	out.flush();                                                                // (the header in members of its own)
+	if (device_path(who, path, [&] { return bam_out_from_file([&](sk_ctx *ctx, uint64_t window, int64_t *n, uint64_t *raw, int *handled) {
+		    return sk_bam_file_rewrite(ctx, path.c_str(), op, level, window, n, raw, handled, nullptr); }); }) >= 0) return 0;
+	HostBamRewrite io(path, level);
+	BamStream &bam = io.bam;
+	BamOut &out = io.out;
 	BamCore c;
 	BamStream::Var v;
 	std::vector<uint8_t> body, rec, app;
@@ -1254,7 +1275,7 @@ static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usa
 			}
 			changed = true;
 		} else if (op == SK_REWRITE_QNAME_FROM_TAGS) {                               // src/sam_qname_from_tags.rs:32-38
-			const size_t aux = (size_t)v.l_read_name + 4 * (size_t)v.n_cigar + (((size_t)v.l_seq + 1) >> 1) + v.l_seq;
+			const size_t aux = v.aux_off();
 			const uint8_t *val = nullptr;
 			size_t vl = 0;
 			if (find_rx(body.data() + aux, body.size() - aux, val, vl)) {
@@ -1270,20 +1291,10 @@ static int rewrite_cmd(int argc, char **argv, int op, int first, const char *usa
 			out.put(body.data(), body.size());
 			continue;
 		}
-		const size_t tail = body.size() - v.l_read_name;
-		const uint32_t bs = (uint32_t)(32 + name.size() + 1 + tail + app.size());
-		rec.assign(bam.head, bam.head + 36);
-		for (int k = 0; k < 4; k++) rec[k] = (uint8_t)(bs >> (8 * k));
-		rec[12] = (uint8_t)(name.size() + 1);
-		rec.insert(rec.end(), name.begin(), name.end());
-		rec.push_back(0);
-		rec.insert(rec.end(), body.begin() + v.l_read_name, body.end());
-		rec.insert(rec.end(), app.begin(), app.end());
+		renamed_record(rec, bam.head, name, body.data() + v.l_read_name, body.size() - v.l_read_name, app);
 		out.put(rec.data(), rec.size());
 	}
-	bam.raise_deferred();
-	out.finish();
-	g_bam_out = nullptr;
+	io.close();
 	return 0;
 }
 
@@ -1301,23 +1312,6 @@ static const char *USAGE_MINIMIZE =
 	"  --baseq-fill=N    Base quality value to fill in as placeholder [default: 255]\n\n"
 	"Changes read IDs into simple numeric identifiers, removes per-base qualities,\nand removes all auxiliary fields (tags).\n";
 
-// the device path of `sam minimize`, as rewrite_from_file
-static int64_t minimize_from_file(const std::string &path, int flags, uint8_t fill, int level)
-{
-	sk_ctx *c = host::gpu();
-	int64_t n_rec = 0;
-	uint64_t raw = 0;
-	int handled = 0;
-	if (sk_bam_file_minimize(c, path.c_str(), flags, fill, level, file_window_bytes(), &n_rec, &raw, &handled, nullptr) != SK_OK || !handled) return -1;
-	sk_bam_out_window w;
-	for (;;) {
-		check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
-		if (w.n == 0 && w.bytes == 0) break;
-		BamOut::write_all(w.bgzf, (size_t)w.bytes);
-	}
-	return n_rec;
-}
-
 static int minimize_cmd(int argc, char **argv)
 {
 	std::vector<host::Opt> opts = {{"--uncompressed", false, false, ""}, {"--read-ids", false, false, ""}, {"--base-qualities", false, false, ""},
@@ -1334,25 +1328,15 @@ static int minimize_cmd(int argc, char **argv)
 	const int level = opts[0].present ? 0 : 1;
 	const int flags = (read_ids ? SK_MINIMIZE_READ_IDS : 0) | (baseq ? SK_MINIMIZE_BASE_QUALITIES : 0) | (tags ? SK_MINIMIZE_TAGS : 0);
 	host::gpu_warmup();
-	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
-	if (file_path_wanted(path)) {
-		const int64_t n = minimize_from_file(path, flags, fill, level);
-		if (n >= 0) {
-			if (trace) fprintf(stderr, "sam minimize: device path, %lld records\n", (long long)n);
-			return 0;
-		}
-	}
-	if (trace) fprintf(stderr, "sam minimize: host reader\n");
-	BamStream bam(path, true);
-	BamOut out(level);
-	g_bam_out = &out;
-	host::at_exit_flush(finish_bam_out);
-	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
-	out.put(hdr.data(), hdr.size());
-	out.flush();                                                                // (the header in members of its own)
+	if (device_path("sam minimize", path, [&] { return bam_out_from_file([&](sk_ctx *ctx, uint64_t window, int64_t *n, uint64_t *raw, int *handled) {
+		    return sk_bam_file_minimize(ctx, path.c_str(), flags, fill, level, window, n, raw, handled, nullptr); }); }) >= 0) return 0;
+	HostBamRewrite io(path, level);
+	BamStream &bam = io.bam;
+	BamOut &out = io.out;
 	BamCore c;
 	BamStream::Var v;
 	std::vector<uint8_t> body, rec;
+	const std::vector<uint8_t> no_aux;
 	std::string name;
 	std::unordered_map<std::string, uint32_t> qname_to_id;                        // :39-40
 	uint32_t highest_id = 0;
@@ -1370,27 +1354,20 @@ static int minimize_cmd(int argc, char **argv)
 			name = std::to_string(id);
 		}
 		const uint8_t *cigar = nm + v.l_read_name;                                // :61 read.cigar()
-		for (uint32_t k = 0; k < v.n_cigar; k++)
-			if ((cigar[4 * k] & 15) > 8) panic("Unexpected cigar operation");
+		bool bad_op = false;
+		(void)cigar_end_pos(cigar, v.n_cigar, 0, &bad_op);
+		if (bad_op) panic("Unexpected cigar operation");
 		const size_t cs = 4 * (size_t)v.n_cigar + (((size_t)v.l_seq + 1) >> 1);
 		const size_t tail = tags ? cs + v.l_seq : body.size() - v.l_read_name;    // set(): core, name, CIGAR, bases, qualities; set_qname(): all
-		const uint32_t bs = (uint32_t)(32 + name.size() + 1 + tail);
-		rec.assign(bam.head, bam.head + 36);
-		for (int k = 0; k < 4; k++) rec[k] = (uint8_t)(bs >> (8 * k));
-		rec[12] = (uint8_t)(name.size() + 1);
-		rec.insert(rec.end(), name.begin(), name.end());
-		rec.push_back(0);
-		const size_t t0 = rec.size();
-		rec.insert(rec.end(), cigar, cigar + tail);
+		renamed_record(rec, bam.head, name, cigar, tail, no_aux);
+		const size_t t0 = rec.size() - tail;
 		if (tags) {
 			if (v.l_seq & 1) rec[t0 + cs - 1] &= 0xf0;                            // (the bases go through as_bytes() and the encoder: the pad nibble is 0)
 			if (baseq) memset(rec.data() + t0 + cs, fill, v.l_seq);
 		}
 		out.put(rec.data(), rec.size());
 	}
-	bam.raise_deferred();
-	out.finish();
-	g_bam_out = nullptr;
+	io.close();
 	return 0;
 }
 
@@ -1469,23 +1446,6 @@ void find_clusters(DupQueue &reads, uint32_t curr_pos)                       // 
 
 }  // namespace
 
-// the device path of `sam mark duplicates`, as rewrite_from_file; *dups: the output records that carry 0x400
-static int64_t markdup_from_file(const std::string &path, bool ignore_umi, int level, int64_t *dups)
-{
-	sk_ctx *c = host::gpu();
-	int64_t n_rec = 0;
-	uint64_t raw = 0;
-	int handled = 0;
-	if (sk_bam_file_markdup(c, path.c_str(), ignore_umi ? 1 : 0, level, file_window_bytes(), &n_rec, dups, &raw, &handled, nullptr) != SK_OK || !handled) return -1;
-	sk_bam_out_window w;
-	for (;;) {
-		check(sk_bam_file_rewrite_next(c, &w), "sk_bam_file_rewrite_next");
-		if (w.n == 0 && w.bytes == 0) break;
-		BamOut::write_all(w.bgzf, (size_t)w.bytes);
-	}
-	return n_rec;
-}
-
 static void markdup_summary(uint64_t dups, uint64_t total)                    // :112-114
 {
 	if (total == 0) fprintf(stderr, "%llu / %llu (NaN%%) reads were marked as duplicates.\n", (unsigned long long)dups, (unsigned long long)total);
@@ -1502,24 +1462,16 @@ static int mark_duplicates_cmd(int argc, char **argv)
 	const int level = opts[0].present ? 0 : 1;
 	const bool ignore_umi = opts[1].present;
 	host::gpu_warmup();
-	const bool trace = getenv("SK_BAMFILE_TRACE") != nullptr;
-	if (file_path_wanted(path)) {
-		int64_t dups = 0;
-		const int64_t n = markdup_from_file(path, ignore_umi, level, &dups);
-		if (n >= 0) {
-			if (trace) fprintf(stderr, "sam mark duplicates: device path, %lld records\n", (long long)n);
-			markdup_summary((uint64_t)dups, (uint64_t)n);
-			return 0;
-		}
+	int64_t dups = 0;                                                           // the output records that carry 0x400
+	const int64_t n_dev = device_path("sam mark duplicates", path, [&] { return bam_out_from_file([&](sk_ctx *ctx, uint64_t window, int64_t *n, uint64_t *raw, int *handled) {
+		    return sk_bam_file_markdup(ctx, path.c_str(), ignore_umi ? 1 : 0, level, window, n, &dups, raw, handled, nullptr); }); });
+	if (n_dev >= 0) {
+		markdup_summary((uint64_t)dups, (uint64_t)n_dev);
+		return 0;
 	}
-	if (trace) fprintf(stderr, "sam mark duplicates: host reader\n");
-	BamStream bam(path, true);
-	BamOut out(level);
-	g_bam_out = &out;
-	host::at_exit_flush(finish_bam_out);
-	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
-	out.put(hdr.data(), hdr.size());
-	out.flush();                                                                // (the header in members of its own)
+	HostBamRewrite io(path, level);
+	BamStream &bam = io.bam;
+	BamOut &out = io.out;
 	uint64_t total_reads = 0, total_duplicates = 0;
 	uint32_t prev_pos = 0;
 	int32_t prev_chr = -1;
@@ -1550,19 +1502,14 @@ static int mark_duplicates_cmd(int argc, char **argv)
 		DupRead &r = reads.v.back();
 		r.start_pos = 0;
 		if (!unmapped && reverse) {                                             // :73 read.cigar().end_pos()
-			const uint8_t *cigar = body.data() + v.l_read_name;
-			int64_t e = c.pos;
-			for (uint32_t k = 0; k < v.n_cigar; k++) {
-				const uint32_t op = le32(cigar + 4 * k), code = op & 15;
-				if (code > 8) { reads.v.pop_back(); panic("Unexpected cigar operation"); }
-				if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) e += op >> 4;
-			}
-			r.start_pos = (uint32_t)(int32_t)e;
+			bool bad_op = false;
+			r.start_pos = (uint32_t)(int32_t)cigar_end_pos(body.data() + v.l_read_name, v.n_cigar, c.pos, &bad_op);
+			if (bad_op) { reads.v.pop_back(); panic("Unexpected cigar operation"); }
 		} else if (!unmapped) r.start_pos = left_pos;
 		r.fraglen = 0;
 		if (!unmapped) {                                                        // :79-91
 			if (!ignore_umi) {
-				const size_t aux = (size_t)v.l_read_name + 4 * (size_t)v.n_cigar + (((size_t)v.l_seq + 1) >> 1) + v.l_seq;
+				const size_t aux = v.aux_off();
 				const uint8_t *val = nullptr;
 				size_t vl = 0;
 				if (find_rx(body.data() + aux, body.size() - aux, val, vl)) r.umi.assign(reinterpret_cast<const char *>(val), vl);
@@ -1578,11 +1525,10 @@ static int mark_duplicates_cmd(int argc, char **argv)
 			find_clusters(reads, left_pos);
 		}
 	}
-	bam.raise_deferred();
+	bam.raise_deferred();                                                       // (before the reads still queued would be written)
 	find_clusters(reads, UINT32_MAX);                                           // :108-110
 	total_duplicates += flush_reads();
-	out.finish();
-	g_bam_out = nullptr;
+	io.close();
 	markdup_summary(total_duplicates, total_reads);
 	return 0;
 }

@@ -72,6 +72,8 @@ bool pread_full(int fd, uint8_t *dst, size_t n, uint64_t off)
 
 }  // namespace
 
+static inline size_t up(uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); }   // to the next multiple of 256
+
 // not this path's file: say at which check (info[5] = -check) and leave it to the caller's reader
 #define BF_LEAVE(code)                                                                                                  \
 	do {                                                                                                                \
@@ -175,7 +177,7 @@ static bool blocking_event(hipEvent_t &e)
 	return true;
 }
 
-// The double buffer of a windowed file call (sk_bam_file_reads, sk_bam_file_rewrite): the window plan, the next window to issue, and per
+// The double buffer of a windowed file call (sk_bam_file_reads; sk_bam_file_rewrite, _minimize and _markdup): the window plan, the next window to issue, and per
 // buffer the window in it and the event its work ends with.  One window is in flight while the caller works on the other.
 struct WindowedState {
 	bool live = false;
@@ -200,7 +202,7 @@ struct WindowedState {
 	}
 };
 
-// sk_bam_file_reads / sk_bam_file_reads_next: the kept records' columns (device, ctx slot kKeepFileCols), the window plan (text and name
+// sk_bam_file_reads / sk_bam_file_reads_next (`sam to`): the kept records' columns (device, ctx slot kKeepFileCols), the window plan (text and name
 // bytes of window w from wt[w] / wn[w] on), and two window buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
 struct ReadsState : WindowedState {
 	int fmt = 0;
@@ -212,16 +214,22 @@ struct ReadsState : WindowedState {
 	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
 };
 
-// sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_rewrite_next: every record's stream and output offsets (device, ctx slot
-// kKeepFileCols), the window plan (output bytes of window w from wo[w] on), one device area for the window being rewritten and
-// compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
-constexpr int kOpMarkdup = -1;                   // RewriteState::op of sk_bam_file_markdup (SK_REWRITE_* are 1 .. 3, 0 is minimize)
+// Which of the three rewrite-window calls is running — the kernel that writes a window's records — and what that kernel takes
+struct WriteOp {
+	enum Kind { kRewrite, kMinimize, kMarkdup } kind = kRewrite;
+	int flags = 0;                               // kRewrite: SK_REWRITE_*; kMinimize: SK_MINIMIZE_*
+	uint8_t fill = 255;                          // kMinimize: the qualities' fill byte
+	const uint32_t *ids = nullptr;               // kMinimize: the read ids (ctx slot kKeepPassWork; nullptr without SK_MINIMIZE_READ_IDS)
+	const uint16_t *md_flags = nullptr;          // kMarkdup: every record's flag (ctx slot kKeepPassWork)
+};
+
+// sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_markdup and sk_bam_file_rewrite_next: every record's stream and output offsets
+// (device, ctx slot kKeepFileCols), the window plan (output bytes of window w from wo[w] on), the write kernel of the call that runs,
+// one device area for the window being rewritten and compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on
+// each side (ctx slots kKeepFileWin / kKeepFilePin)
 struct RewriteState : WindowedState {
-	int op = 0, level = 1;                       // op 0: sk_bam_file_minimize, with its flags, fill byte and ids (ctx slot kKeepMinimize)
-	const uint16_t *md_flags = nullptr;          // op kOpMarkdup: sk_bam_file_markdup, every record's flag (ctx slot kKeepMinimize)
-	int min_flags = 0;
-	uint8_t min_fill = 255;
-	const uint32_t *ids = nullptr;
+	WriteOp write;
+	int level = 1;
 	uint64_t *krec = nullptr, *kout = nullptr;
 	std::vector<uint64_t> wo;
 	std::vector<uint8_t> header;                 // the output header (the first window)
@@ -240,7 +248,7 @@ struct Ranges {
 	OutRange comp, out;
 	std::vector<uint8_t> header;                 // sk_bam_file_columns: the last file's header bytes (cols->header)
 	uint64_t gen = 0;                            // file calls so far: a reads state of an earlier call is stale
-	ReadsState reads;                            // (only one of the two is live: the next file call ends either)
+	ReadsState reads;                            // (only one of the two is live: the next file call, windowed or not, ends either)
 	RewriteState rw;
 	static void destroy(void *p) { Ranges *r = (Ranges *)p; r->comp.release(); r->out.release(); delete r; }
 };
@@ -346,7 +354,7 @@ static int bam_file_front(sk_ctx *c, const char *path, Cleanup &cl, Front &fr, d
 	if (!both) { both = new Ranges; sk::ctx_set_ext(c, both, Ranges::destroy); }
 	// an earlier sk_bam_file_reads may have left a window in flight on the ctx stream: its text kernel reads the inflated stream and its
 	// copies write the page-locked window buffers.  It ends before this call remaps the ranges or takes the kept buffers again.
-	// (the same for an sk_bam_file_rewrite, whose window copies run on the second stream)
+	// (the same for an sk_bam_file_rewrite, _minimize or _markdup, whose window copies run on the second stream)
 	if (both->reads.busy() || both->rw.busy()) {
 		BF_HIP(hipStreamSynchronize(sk::ctx_stream(c)));
 		BF_HIP(hipStreamSynchronize(sk::ctx_stream2(c)));
@@ -738,6 +746,26 @@ static int plan_windows(sk_ctx *c, Cleanup &cl, uint64_t window_bytes, const uin
 	return SK_OK;
 }
 
+// The decline word of a call's record passes, read back: the copy, the wait for the stream (and so for every copy issued before), and
+// under SK_BAMFILE_TRACE the line that names the caller.  The bits, `found` (what the caller has seen itself) among them: the file is
+// left to the caller's reader with info[5] = -(30 + bits); < 0: the copy failed, and the message is set.
+static int read_decline(sk_ctx *c, const char *who, const uint32_t *d_decline, uint32_t found)
+{
+	hipStream_t st = sk::ctx_stream(c);
+	uint32_t word = 0;
+	hipError_t e = hipMemcpyAsync(&word, d_decline, 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e != hipSuccess) { sk::ctx_fail(c, SK_ERR_HIP, "%s: the decline word: %s", who, hipGetErrorString(e)); return -1; }
+	word |= found;
+	if (word && getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "%s: declined (bits %#x)\n", who, word);
+	return (int)word;
+}
+#define BF_LEAVE_DECLINED(d_decline, found)                                                                             \
+	do {                                                                                                                \
+		const int d_ = read_decline(c, fr.who, d_decline, found);                                                       \
+		if (d_) { if (d_ < 0) return SK_ERR_HIP; BF_LEAVE(30 + d_); }                                                   \
+	} while (0)
+
 extern "C" int sk_bam_file_reduce(sk_ctx *c, const char *path, int32_t max_frag, uint64_t counters[3], uint64_t *hist, uint64_t *hist_total,
                                   int *handled, double info[8])
 {
@@ -877,14 +905,10 @@ extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_
 	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
 	BF_HIP(sk::launch_bam_reads_size(fr.d_out, fr.d_bend, fr.d_entry, nb, format, want_unpaired ? 1 : 0, bk, bt, bn, d_decline, st));
 	uint64_t tot[3] = {0, 0, 0};                                        // kept, text, names
-	uint32_t decline = 0;
 	BF_HIP(hipMemcpyAsync(tot, bk + nb, 8, hipMemcpyDeviceToHost, st));
 	BF_HIP(hipMemcpyAsync(tot + 1, bt + nb, 8, hipMemcpyDeviceToHost, st));
 	BF_HIP(hipMemcpyAsync(tot + 2, bn + nb, 8, hipMemcpyDeviceToHost, st));
-	BF_HIP(hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st));
-	BF_HIP(hipStreamSynchronize(st));
-	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_reads: declined (bits %#x)\n", decline);
-	if (decline) BF_LEAVE(30 + decline);                                // (1 qname, 2 fastq quality, 4 l_seq, 8 invalid record: info[5] = -31 .. -45)
+	BF_LEAVE_DECLINED(d_decline, 0);                                    // (1 qname, 2 fastq quality, 4 l_seq, 8 invalid record: info[5] = -31 .. -45)
 	const int64_t K = (int64_t)tot[0];
 	const uint64_t T = tot[1], N = tot[2];
 	// ---- the kept records' columns: stream offset, text offset, name offset, key, kind
@@ -903,7 +927,6 @@ extern "C" int sk_bam_file_reads(sk_ctx *c, const char *path, int format, uint8_
 	if (!room) BF_LEAVE(21);
 	const uint64_t max_n = mx[0], max_t = mx[1], max_nm = mx[2];
 	// ---- two window buffers, on the device and page-locked, in one layout
-	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
 	s.at_toff = up(max_t + 16);
 	s.at_noff = s.at_toff + up((max_n + 1) * 8);
 	s.at_names = s.at_noff + up((max_n + 1) * 4);
@@ -954,10 +977,10 @@ extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
 	return SK_OK;
 }
 
-// ---- sam trim qnames / tags from qname / qname from tags (include/seqkit_hip.h: sk_bam_file_rewrite, sk_bam_file_rewrite_next) ---
-// The front half above, then the sizing pass (per block: rewritten bytes, decline bits) and its scan; the decision to serve the file is
-// taken there, before any window exists.  Then every record's stream and output offsets, the windows, and the header's members on their
-// way.  A window is rewritten into one device buffer, cut into blocks of at most 0xff00 bytes, deflated where it lies and packed into
+// ---- BAM out (include/seqkit_hip.h: sk_bam_file_rewrite, sk_bam_file_minimize, sk_bam_file_markdup; sk_bam_file_rewrite_next) ---
+// The front half above, then the call's own passes, among them a sizing pass (per block: output bytes, decline bits) and its scan; the
+// decision to serve the file is taken there, before any window exists.  Then every record's stream and output offsets, the windows, and
+// the header's members on their way.  A window is rewritten into one device buffer, cut into blocks of at most 0xff00 bytes, deflated where it lies and packed into
 // complete members; only the members' bytes are copied back.  Every allocation that fails leaves the file to the caller's reader
 // (info[5] = -21).
 
@@ -979,9 +1002,12 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		if (!s.next_window(w)) return false;
 		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
 		raw_len = s.wo[w + 1] - s.wo[w];
-		e = s.op == kOpMarkdup ? sk::launch_bam_md_write(s.d_out, s.krec, s.kout, s.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st)
-		    : s.op ? sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.op, s.d_raw, sk::ctx_n_cu(c), st)
-		           : sk::launch_bam_min_write(s.d_out, s.krec, s.kout, s.ids, first, n, s.wo[w], s.min_flags, s.min_fill, s.d_raw, sk::ctx_n_cu(c), st);
+		const WriteOp &op = s.write;
+		switch (op.kind) {
+		case WriteOp::kRewrite: e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], op.flags, s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kMinimize: e = sk::launch_bam_min_write(s.d_out, s.krec, s.kout, op.ids, first, n, s.wo[w], op.flags, op.fill, s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kMarkdup: e = sk::launch_bam_md_write(s.d_out, s.krec, s.kout, op.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
+		}
 	}
 	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
 	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
@@ -998,13 +1024,47 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 	return true;
 }
 
-// What sk_bam_file_rewrite and sk_bam_file_minimize share once every record's stream and output offsets (s.krec, s.kout) are there: the
-// window plan, the window area, and the header's members on their way.  `total`: the records' output bytes.
-static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, RewriteState &s, uint64_t gen, int level, uint64_t window_bytes, uint64_t total,
-                    double t_size, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
+// What sk_bam_file_rewrite, sk_bam_file_minimize and sk_bam_file_markdup open with once the stream is verified: the per-block scratch of
+// their passes with the decline word behind it, the blocks' first record indices on the device, and the rewrite state with room for
+// every record's stream and output offsets (ctx slot kKeepFileCols).  s == nullptr afterwards: that memory cannot be had, and the file
+// is left to the caller's reader (info[5] = -21).
+struct RwOpen {
+	RewriteState *s = nullptr;
+	uint64_t *d_blk = nullptr;                   // blk_cols columns of nb + 1 u64 each
+	uint64_t *d_rb = nullptr;                    // block b's first record: nb entries, and one word more that is the caller's
+	uint32_t *d_decline = nullptr;               // zeroed
+	std::vector<uint64_t> rb;                    // (what d_rb is copied from: it lives until the caller has waited for the stream)
+	double t_size = 0;
+};
+static int rw_open(sk_ctx *c, Cleanup &cl, const Front &fr, int blk_cols, RwOpen &o, double info[8])
 {
+	o.t_size = now_ms();
+	hipStream_t st = sk::ctx_stream(c);
+	const int64_t nb = fr.nb;
+	if (hipMalloc((void **)&o.d_blk, (size_t)(nb + 1) * 8 * (size_t)(blk_cols + 1) + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+	cl.dev.push_back(o.d_blk);
+	o.d_rb = o.d_blk + (size_t)(nb + 1) * (size_t)blk_cols;
+	o.d_decline = (uint32_t *)(o.d_rb + nb + 1);
+	BF_HIP(hipMemsetAsync(o.d_decline, 0, 4, st));
+	if (int r = block_first_records(c, fr, o.rb)) return r;
+	if (nb) BF_HIP(hipMemcpyAsync(o.d_rb, o.rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+	int krc = SK_OK;
+	const size_t a_col = up(fr.n_records * 8 + 8);
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * a_col, false, &krc);
+	if (!kb) BF_LEAVE(21);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	R->rw.krec = (uint64_t *)kb; R->rw.kout = (uint64_t *)(kb + a_col);
+	o.s = &R->rw;
+	return SK_OK;
+}
+
+// What the three share once every record's stream and output offsets (s.krec, s.kout) are there: the window plan, the window area, and
+// the header's members on their way.  `write`: the kernel that writes a window; `total`: the records' output bytes.
+static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WriteOp &write, int level, uint64_t window_bytes, uint64_t total,
+                    int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	RewriteState &s = *o.s;
 	const uint64_t N = fr.n_records;
-	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
 	int krc = SK_OK;
 	// ---- the windows: at most W rewritten bytes each
 	uint64_t mx[3];                                                     // records, rewritten bytes
@@ -1033,8 +1093,8 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, RewriteState &s, ui
 	for (int b = 0; b < 2; b++)
 		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
 	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
-	s.level = level; s.header_done = false;
-	s.begin(fr.d_out, gen);
+	s.write = write; s.level = level; s.header_done = false;
+	s.begin(fr.d_out, ((Ranges *)sk::ctx_ext(c))->gen);
 	int rc = SK_OK;
 	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
 	if (rc) return rc;
@@ -1044,7 +1104,7 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, RewriteState &s, ui
 	*handled = 1;
 	char tail[128];
 	snprintf(tail, sizeof tail, "; %llu records, %llu rewritten bytes, %lld windows", (unsigned long long)N, (unsigned long long)total, (long long)s.ws.size() - 1);
-	file_call_close(fr, "size + index + plan", t_size, tail, info);
+	file_call_close(fr, "size + index + plan", o.t_size, tail, info);
 	return SK_OK;
 }
 
@@ -1062,47 +1122,25 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 	    }))
 		return r;
 	if (!fr.ready) return SK_OK;
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 1, o, info)) return r;
+	if (!o.s) return SK_OK;
 	hipStream_t st = sk::ctx_stream(c);
-	const double t_size = now_ms();
 	const int64_t nb = fr.nb;
-	const uint64_t N = fr.n_records;
 	// ---- the sizing pass: per block the rewritten bytes (then their exclusive offsets), the decline bits
-	uint64_t *d_blk = nullptr;
-	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 16 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
-	cl.dev.push_back(d_blk);
-	uint64_t *bo = d_blk, *d_rb = bo + nb + 1;
-	uint32_t *d_decline = (uint32_t *)(d_rb + nb);
-	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
-	BF_HIP(sk::launch_bam_rw_size(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, d_decline, st));
+	uint64_t *bo = o.d_blk;
+	BF_HIP(sk::launch_bam_rw_size(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, o.d_decline, st));
 	uint64_t total = 0;
-	uint32_t decline = 0;
 	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
-	BF_HIP(hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st));
-	BF_HIP(hipStreamSynchronize(st));
-	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_rewrite: declined (bits %#x)\n", decline);
-	if (decline) BF_LEAVE(30 + decline);                                // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
+	BF_LEAVE_DECLINED(o.d_decline, 0);                                  // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
 	// ---- every record's stream and output offsets
-	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
-	int krc = SK_OK;
-	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * up(N * 8 + 8), false, &krc);
-	if (!kb) BF_LEAVE(21);
-	Ranges *R = (Ranges *)sk::ctx_ext(c);
-	RewriteState &s = R->rw;
-	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
-	{
-		std::vector<uint64_t> rb;
-		if (int r = block_first_records(c, fr, rb)) return r;
-		if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-		BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, d_rb, s.krec, s.kout, st));
-		BF_HIP(hipStreamSynchronize(st));                              // (rb is this scope's)
-	}
-	s.op = op;
-	return rw_begin(c, cl, fr, s, R->gen, level, window_bytes, total, t_size, n_records, raw_bytes, handled, info);
+	BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, o.d_rb, o.s->krec, o.s->kout, st));
+	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kRewrite, op}, level, window_bytes, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam minimize (include/seqkit_hip.h: sk_bam_file_minimize; the windows come from sk_bam_file_rewrite_next) ---
 // The front half, then with SK_MINIMIZE_READ_IDS the id passes (sk_bamminimize.hip: keys, sort, runs, ids) in the working memory of ctx
-// slot kKeepMinimize — two key and two index buffers for the sort (24 B per record and the sort's own scratch); behind the sort the idle
+// slot kKeepPassWork — two key and two index buffers for the sort (24 B per record and the sort's own scratch); behind the sort the idle
 // key buffer holds src and the opener counts and the idle index buffer the ids — then the sizing pass with the ids' digits, and from
 // there on what sk_bam_file_rewrite does.  The file is left to the caller's reader (info[5] = -21) when that memory cannot be had or
 // the file has 2^32 records or more (the ids are u32), and with info[5] = -(30 + bits) on an invalid record (8), a CIGAR operation
@@ -1123,69 +1161,45 @@ extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint
 	    }))
 		return r;
 	if (!fr.ready) return SK_OK;
-	hipStream_t st = sk::ctx_stream(c);
-	const double t_size = now_ms();
 	const int64_t nb = fr.nb;
 	const uint64_t N = fr.n_records;
 	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
-	uint64_t *d_blk = nullptr;
-	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 16 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
-	cl.dev.push_back(d_blk);
-	uint64_t *bo = d_blk, *d_rb = bo + nb + 1;
-	uint32_t *d_decline = (uint32_t *)(d_rb + nb);
-	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
-	std::vector<uint64_t> rb;
-	if (int r = block_first_records(c, fr, rb)) return r;
-	if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
-	int krc = SK_OK;
-	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * up(N * 8 + 8), false, &krc);
-	if (!kb) BF_LEAVE(21);
-	Ranges *R = (Ranges *)sk::ctx_ext(c);
-	RewriteState &s = R->rw;
-	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
-	uint32_t decline = 0;
-	auto declined = [&](void) -> int {                                   // the bits so far; < 0: the copy failed
-		if (hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-		if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_minimize: declined (bits %#x)\n", decline);
-		return (int)decline;
-	};
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 1, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *bo = o.d_blk, *krec = o.s->krec, *kout = o.s->kout;
 	// ---- the read ids
-	s.ids = nullptr;
+	const uint32_t *ids = nullptr;
 	if ((flags & SK_MINIMIZE_READ_IDS) && N) {
 		int bits = 64;                                                  // (a test knob: fewer bits make hash collisions reachable)
 		if (const char *ev = getenv("SK_MINIMIZE_KEY_BITS")) { const int v = atoi(ev); if (v >= 1 && v <= 64) bits = v; }
 		uint64_t *key[2] = {nullptr, nullptr};
 		uint32_t *idx[2] = {nullptr, nullptr};
 		size_t temp_bytes = 0;
-		BF_HIP(sk::bam_min_sort(nullptr, &temp_bytes, key, idx, N, bits, nullptr, st));
+		BF_HIP(sk::bam_sort_pairs(nullptr, &temp_bytes, key, idx, N, bits, nullptr, st));
 		const size_t a_key = up(N * 8), a_idx = up(N * 4), a_agg = up((N / 1024 + 2) * 4);
-		uint8_t *mb = (uint8_t *)sk::ctx_keep(c, sk::kKeepMinimize, 2 * a_key + 2 * a_idx + a_agg + up(temp_bytes), false, &krc);
+		int krc = SK_OK;
+		uint8_t *mb = (uint8_t *)sk::ctx_keep(c, sk::kKeepPassWork, 2 * a_key + 2 * a_idx + a_agg + up(temp_bytes), false, &krc);
 		if (!mb) BF_LEAVE(21);
 		key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
 		idx[0] = (uint32_t *)(mb + 2 * a_key); idx[1] = (uint32_t *)(mb + 2 * a_key + a_idx);
 		uint32_t *agg = (uint32_t *)(mb + 2 * a_key + 2 * a_idx);
-		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, bits, s.krec, key[0], idx[0], d_decline, st));
-		const int d0 = declined();                                      // (the passes below read the names of valid records only)
-		if (d0 < 0) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_minimize: the key pass failed");
-		if (d0) BF_LEAVE(30 + d0);
+		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, bits, krec, key[0], idx[0], o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (the passes below read the names of valid records only)
 		int cur = 0;
-		BF_HIP(sk::bam_min_sort(mb + 2 * a_key + 2 * a_idx + a_agg, &temp_bytes, key, idx, N, bits, &cur, st));
-		uint32_t *src = (uint32_t *)key[cur ^ 1], *cnt = src + N, *ids = idx[cur ^ 1];
-		BF_HIP(sk::launch_bam_min_ids(fr.d_out, s.krec, key[cur], idx[cur], N, agg, src, cnt, ids, d_decline, st));
-		s.ids = ids;
+		BF_HIP(sk::bam_sort_pairs(mb + 2 * a_key + 2 * a_idx + a_agg, &temp_bytes, key, idx, N, bits, &cur, st));
+		uint32_t *src = (uint32_t *)key[cur ^ 1], *cnt = src + N;
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, key[cur], idx[cur], N, agg, src, cnt, idx[cur ^ 1], o.d_decline, st));
+		ids = idx[cur ^ 1];
 	}
 	// ---- the sizing pass: per block the output bytes (then their exclusive offsets), the decline bits
-	BF_HIP(sk::launch_bam_min_size(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, flags, s.ids, bo, d_decline, st));
+	BF_HIP(sk::launch_bam_min_size(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, flags, ids, bo, o.d_decline, st));
 	uint64_t total = 0;
 	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
-	const int d1 = declined();
-	if (d1 < 0) return sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_minimize: the sizing pass failed");
-	if (d1) BF_LEAVE(30 + d1);
-	BF_HIP(sk::launch_bam_min_index(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, flags, s.ids, bo, s.krec, s.kout, st));
-	BF_HIP(hipStreamSynchronize(st));
-	s.op = 0; s.min_flags = flags; s.min_fill = baseq_fill;
-	return rw_begin(c, cl, fr, s, R->gen, level, window_bytes, total, t_size, n_records, raw_bytes, handled, info);
+	BF_LEAVE_DECLINED(o.d_decline, 0);
+	BF_HIP(sk::launch_bam_min_index(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, flags, ids, bo, krec, kout, st));
+	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMinimize, flags, baseq_fill, ids}, level, window_bytes, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam mark duplicates (include/seqkit_hip.h: sk_bam_file_markdup; the windows come from sk_bam_file_rewrite_next) ---
@@ -1193,10 +1207,10 @@ extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint
 // sort the second of each holds (tid, pos) and the run flags, and the first index buffer the run indices), five u32 signature columns
 // and the scratch of the sort and the scan: 44 B per record — is needed only until the clusters are found, and lies in the device
 // buffer of the COMPRESSED file, which is idle once the stream is verified (a BAM record takes more compressed bytes than that; where
-// it does not, ctx slot kKeepMinimize serves).  Only the u16 flag column, which the windows read, is kept in that slot: a gigabyte
-// taken and given back for a 20 M-record file cost the command 0.1 s.  The records' bytes and sizes do not
-// change: a record's output offset is its stream offset less the header's, the windows are planned over those, and the write kernel
-// patches the flag.  Declined files: the list in include/seqkit_hip.h.
+// it does not, ctx slot kKeepPassWork serves).  Only the u16 flag column, which the windows read, is kept in that slot: a gigabyte
+// taken and given back for a 20 M-record file cost the command 0.1 s.  The records' bytes and sizes do not change: a record's output
+// offset is its stream offset less the header's, the windows are planned over those, and the write kernel patches the flag.  Declined
+// files: the list in include/seqkit_hip.h.
 extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, int level, uint64_t window_bytes, int64_t *n_records,
                                    int64_t *n_duplicates, uint64_t *raw_bytes, int *handled, double info[8])
 {
@@ -1211,62 +1225,47 @@ extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, 
 	    }))
 		return r;
 	if (!fr.ready) return SK_OK;
-	hipStream_t st = sk::ctx_stream(c);
-	const double t_size = now_ms();
 	const int64_t nb = fr.nb;
 	const uint64_t N = fr.n_records;
 	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
-	uint64_t *d_blk = nullptr;
-	if (hipMalloc((void **)&d_blk, (size_t)(nb + 1) * 8 + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
-	cl.dev.push_back(d_blk);
-	uint64_t *d_rb = d_blk, *d_count = d_rb + nb;
-	uint32_t *d_decline = (uint32_t *)(d_count + 1);
-	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
-	std::vector<uint64_t> rb;
-	if (int r = block_first_records(c, fr, rb)) return r;
-	if (nb) BF_HIP(hipMemcpyAsync(d_rb, rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-	auto up = [](uint64_t v) { return (size_t)((v + 255) & ~(uint64_t)255); };
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 0, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *d_count = o.d_rb + nb;                                    // (no per-block column, one word: the duplicates)
 	int krc = SK_OK;
-	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * up(N * 8 + 8), false, &krc);
-	if (!kb) BF_LEAVE(21);
-	Ranges *R = (Ranges *)sk::ctx_ext(c);
-	RewriteState &s = R->rw;
-	s.krec = (uint64_t *)kb; s.kout = (uint64_t *)(kb + up(N * 8 + 8));
 	uint64_t *key[2] = {nullptr, nullptr};
 	uint32_t *idx[2] = {nullptr, nullptr};
 	size_t sort_bytes = 0, scan_bytes = 0;
-	BF_HIP(sk::bam_min_sort(nullptr, &sort_bytes, key, idx, N ? N : 1, 64, nullptr, st));
+	BF_HIP(sk::bam_sort_pairs(nullptr, &sort_bytes, key, idx, N ? N : 1, 64, nullptr, st));
 	BF_HIP(sk::bam_md_run_scan(nullptr, &scan_bytes, nullptr, nullptr, N ? N : 1, st));
 	const size_t a_key = up(N * 8 + 8), a_idx = up(N * 4 + 4), a_flag = up(N * 2 + 2), temp_bytes = std::max(sort_bytes, scan_bytes);
 	const size_t work = 2 * a_key + 7 * a_idx + up(temp_bytes);
 	const bool in_comp = fr.fsize + 64 >= work && !getenv("SK_MARKDUP_OWN_MEMORY");      // (the knob: for tests of the other placement)
-	uint8_t *fb = (uint8_t *)sk::ctx_keep(c, sk::kKeepMinimize, a_flag + (in_comp ? 0 : work), false, &krc);
+	uint8_t *fb = (uint8_t *)sk::ctx_keep(c, sk::kKeepPassWork, a_flag + (in_comp ? 0 : work), false, &krc);
 	if (!fb) BF_LEAVE(21);
 	uint8_t *mb = in_comp ? fr.d_comp : fb + a_flag;
 	if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_markdup: %zu bytes of scratch in %s\n", work, in_comp ? "the compressed file's buffer" : "its own buffer");
 	key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
 	idx[0] = (uint32_t *)(mb + 2 * a_key); idx[1] = (uint32_t *)(mb + 2 * a_key + a_idx);
 	sk::MdCols cols;
-	cols.krec = s.krec; cols.kout = s.kout; cols.tidpos = key[1];
+	cols.krec = o.s->krec; cols.kout = o.s->kout; cols.tidpos = key[1];
 	uint8_t *sig = mb + 2 * a_key + 2 * a_idx;
 	cols.start = (uint32_t *)sig; cols.fl = (uint32_t *)(sig + a_idx); cols.lseq = (uint32_t *)(sig + 2 * a_idx);
 	cols.uoff = (uint32_t *)(sig + 3 * a_idx); cols.ulen = (uint32_t *)(sig + 4 * a_idx);
 	cols.nflag = (uint16_t *)fb;
 	void *temp = sig + 5 * a_idx;
 	// ---- signatures, order, runs: the decision to serve the file
-	BF_HIP(sk::launch_bam_md_sig(fr.d_out, fr.d_bend, fr.d_entry, nb, d_rb, ignore_umi ? 1 : 0, fr.first, cols, d_decline, st));
-	BF_HIP(sk::launch_bam_md_order(cols.tidpos, N, idx[1], d_decline, st));
-	uint32_t decline = 0, runs = 0;
+	BF_HIP(sk::launch_bam_md_sig(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, ignore_umi ? 1 : 0, fr.first, cols, o.d_decline, st));
+	BF_HIP(sk::launch_bam_md_order(cols.tidpos, N, idx[1], o.d_decline, st));
+	uint32_t runs = 0;
 	if (N) {
 		size_t tb = temp_bytes;
 		BF_HIP(sk::bam_md_run_scan(temp, &tb, idx[1], idx[0], N, st));
 		BF_HIP(hipMemcpyAsync(&runs, idx[0] + (N - 1), 4, hipMemcpyDeviceToHost, st));
 	}
-	BF_HIP(hipMemcpyAsync(&decline, d_decline, 4, hipMemcpyDeviceToHost, st));
-	BF_HIP(hipStreamSynchronize(st));                                  // (rb is read by the copy above)
-	if (runs >= 0x7fffffffu) decline |= 64u;
-	if (getenv("SK_BAMFILE_TRACE") && decline) fprintf(stderr, "sk_bam_file_markdup: declined (bits %#x)\n", decline);
-	if (decline) BF_LEAVE(30 + decline);
+	BF_HIP(hipStreamSynchronize(st));                                  // (runs)
+	BF_LEAVE_DECLINED(o.d_decline, runs >= 0x7fffffffu ? 64u : 0u);
 	// ---- keys, the sort (only the bits the keys use: the all-ones key of the unmapped reads stays the largest), clusters, count
 	int bits = 34;
 	while (bits < 64 && ((uint64_t)1 << (bits - 33)) <= (uint64_t)runs) bits++;
@@ -1275,13 +1274,12 @@ extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, 
 		BF_HIP(sk::launch_bam_md_keys(idx[0], cols, N, key[0], idx[0], st));
 		int cur = 0;
 		size_t tb = temp_bytes;
-		BF_HIP(sk::bam_min_sort(temp, &tb, key, idx, N, bits, &cur, st));
+		BF_HIP(sk::bam_sort_pairs(temp, &tb, key, idx, N, bits, &cur, st));
 		BF_HIP(sk::launch_bam_md_cluster(fr.d_out, cols, key[cur], idx[cur], N, d_count, sk::ctx_n_cu(c), st));
 		BF_HIP(hipMemcpyAsync(&dups, d_count, 8, hipMemcpyDeviceToHost, st));
 		BF_HIP(hipStreamSynchronize(st));
 	}
-	s.op = kOpMarkdup; s.md_flags = cols.nflag;
-	const int rc = rw_begin(c, cl, fr, s, R->gen, level, window_bytes, fr.stream_len - fr.first, t_size, n_records, raw_bytes, handled, info);
+	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMarkdup, 0, 255, nullptr, cols.nflag}, level, window_bytes, fr.stream_len - fr.first, n_records, raw_bytes, handled, info);
 	if (rc == SK_OK && *handled && n_duplicates) *n_duplicates = (int64_t)dups;
 	return rc;
 }

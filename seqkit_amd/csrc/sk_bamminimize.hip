@@ -357,7 +357,7 @@ hipError_t launch_bam_min_keys(const uint8_t *stream, const uint64_t *bend, cons
 	return hipGetLastError();
 }
 
-hipError_t bam_min_sort(void *temp, size_t *temp_bytes, uint64_t *key[2], uint32_t *idx[2], uint64_t n, int key_bits, int *sorted, hipStream_t st)
+hipError_t bam_sort_pairs(void *temp, size_t *temp_bytes, uint64_t *key[2], uint32_t *idx[2], uint64_t n, int key_bits, int *sorted, hipStream_t st)
 {
 	rocprim::double_buffer<u64> k((u64 *)key[0], (u64 *)key[1]);
 	rocprim::double_buffer<u32> v(idx[0], idx[1]);

@@ -186,7 +186,7 @@ size_t deflate_tokens_per_block();
 hipError_t launch_bgzf_crc(const uint8_t *in, const void *blocks, int64_t n_blocks, uint32_t *crc, int n_cu, hipStream_t st);
 
 hipError_t launch_scan_u64(uint64_t *v, int64_t n, hipStream_t st);     // sk_bamtext.hip: v[0 .. n) -> exclusive offsets, v[n] the sum
-// the window plan of sk_bam_file_reads and sk_bam_file_rewrite (sk_bamtext.hip): window w holds the records whose key off0[j] + off1[j]
+// the window plan of sk_bam_file_reads and of sk_bam_file_rewrite, _minimize and _markdup (sk_bamtext.hip): window w holds the records whose key off0[j] + off1[j]
 // (off1 == nullptr: off0[j]) lies in [w W, (w + 1) W); ws[w] = its first record, w0[w] / w1[w] = that record's off0 / off1 (w1 only with
 // off1).  The entries past the last record's window hold (n, total0, total1).  nw entries in all.
 hipError_t launch_bam_windows(const uint64_t *off0, const uint64_t *off1, int64_t n, uint64_t W, uint64_t total0, uint64_t total1, uint64_t *ws,
@@ -203,13 +203,13 @@ hipError_t launch_bam_rw_write(const uint8_t *stream, const uint64_t *krec, cons
                                uint8_t *out, int n_cu, hipStream_t st);
 // ---- sam minimize: the read ids and the per-record rewrite of sk_bam_file_minimize (sk_bamminimize.hip) ----
 // keys: every record's stream offset, the hash of its name up to the first '/' (its low key_bits bits) and its index; decline bit 8: an
-// invalid record.  sort: (hash, index) by hash, stable, between the two buffers of each kind (*sorted: the one that holds the result);
+// invalid record.  bam_sort_pairs: (u64 key, u32 index) by the key's low key_bits bits, stable, between the two buffers of each kind (*sorted: the one that holds the result);
 // temp == nullptr: only *temp_bytes.  ids: from the sorted pairs the records' ids (agg: u32[n / 1024 + 1] scratch; src, cnt: u32[n]
 // scratch); decline bit 64: two different keys with one hash.  size / index / write: as launch_bam_rw_*; flags SK_MINIMIZE_*; ids ==
 // nullptr without SK_MINIMIZE_READ_IDS; decline bit 32: a CIGAR operation code above 8.
 hipError_t launch_bam_min_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int key_bits,
                                uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st);
-hipError_t bam_min_sort(void *temp, size_t *temp_bytes, uint64_t *key[2], uint32_t *idx[2], uint64_t n, int key_bits, int *sorted, hipStream_t st);
+hipError_t bam_sort_pairs(void *temp, size_t *temp_bytes, uint64_t *key[2], uint32_t *idx[2], uint64_t n, int key_bits, int *sorted, hipStream_t st);
 hipError_t launch_bam_min_ids(const uint8_t *stream, const uint64_t *krec, const uint64_t *key, const uint32_t *idx, uint64_t n, uint32_t *agg,
                               uint32_t *src, uint32_t *cnt, uint32_t *ids, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_min_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int flags,
@@ -228,7 +228,7 @@ struct MdCols {
 };
 // sig: the columns and the decline bits 1, 4, 8, 16, 32 of include/seqkit_hip.h (first: the stream offset of the first record).  order:
 // runflag[k] = 1 where record k's tid differs from its predecessor's; decline bit 2.  run_scan: run = the inclusive sum of runflag (temp
-// == nullptr: only *temp_bytes).  keys: (key, index) for bam_min_sort, key = (run - 1) << 33 | start_pos << 1 | strand, all ones for an
+// == nullptr: only *temp_bytes).  keys: (key, index) for bam_sort_pairs, key = (run - 1) << 33 | start_pos << 1 | strand, all ones for an
 // unmapped read.  cluster: over the sorted pairs, every mapped read's flag into cols.nflag, then *count = the records with 0x400.
 // write: as launch_bam_rw_write, bytes 18-19 of every record from nflag.
 hipError_t launch_bam_md_sig(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int ignore_umi,
@@ -276,8 +276,8 @@ enum KeepSlot {
 	kKeepComp = 0, kKeepOut = 1, kKeepPin = 2, kKeepTable = 3, kKeepBlocks = 4, kKeepStatus = 5,   // the front half
 	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
 	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
-	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize: per-record columns, windows
-	kKeepMinimize = 12,                                 // sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small)
+	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize / _markdup: per-record columns, windows
+	kKeepPassWork = 12,                                 // the record passes' working memory. sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small)
 	kKeepSlots = 13
 };
 hipStream_t ctx_stream(sk_ctx *c);

@@ -3,18 +3,10 @@ inflated stdout, equal to literal() of tests/bam_markdup_model.py, the same stde
 import pytest
 
 from tests import bam_markdup_model as m
-from tests import cli_util as cu
+from tests import bam_out_util as bu
+from tests.bam_out_util import sam  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
-
-WHO = b"sam mark duplicates: "
-
-
-@pytest.fixture(scope="module")
-def sam(hip_lib):
-    from seqkit_amd import build
-    build.build_hosts()
-    return cu.SAM
 
 
 @pytest.fixture(scope="module")
@@ -23,28 +15,8 @@ def bam(tmp_path_factory):
     return path, m.write(path, m.sorted_records(11, 25000, big=1100))
 
 
-def inflated(data):
-    return b"".join(x for x, _ in m.members(data))
-
-
 def three(sam, path, extra, expect_path="device path"):
-    """device path, host reader, stdin: (code, inflated stdout, stderr) of each, checked equal; the trace names the path"""
-    runs = []
-    for e, argv, stdin in (({"SK_BAMFILE_TRACE": "1"}, ["mark", "duplicates"] + list(extra) + [str(path)], None),
-                           ({"SK_BAMFILE_TRACE": "1", "SEQKIT_HOST_INFLATE": "1"}, ["mark", "duplicates"] + list(extra) + [str(path)], None),
-                           ({"SK_BAMFILE_TRACE": "1"}, ["mark", "duplicates"] + list(extra) + ["-"], open(path, "rb").read())):
-        runs.append(cu.run(sam, argv, stdin=stdin, env=e))
-    traces = [[ln for ln in err.split(b"\n") if ln.startswith(WHO)] for _, _, err in runs]
-    assert traces[0] and traces[0][0].startswith(WHO + expect_path.encode()), traces[0]
-    assert traces[1] == [WHO + b"host reader"] and traces[2] == traces[1]
-    assert runs[0][0] == runs[1][0] == runs[2][0]
-    for _, out, _ in runs:
-        assert out.endswith(m.EOF_BLOCK)
-    outs = [inflated(out) for _, out, _ in runs]
-    assert outs[0] == outs[1] == outs[2]
-    strip = [b"\n".join(ln for ln in err.split(b"\n") if not ln.startswith(WHO) and not ln.startswith(b"sk_bam")) for _, _, err in runs]
-    assert strip[0] == strip[1] == strip[2]
-    return runs[0][0], outs[0], strip[0], runs
+    return bu.three(sam, m, ["mark", "duplicates"], path, extra, expect_path)
 
 
 @pytest.mark.parametrize("ignore_umi", [False, True])

@@ -3,40 +3,15 @@
 import pytest
 
 from tests import bam_rewrite_model as m
+from tests import bam_out_util as bu
 from tests import cli_util as cu
+from tests.bam_out_util import sam  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def sam(hip_lib):
-    from seqkit_amd import build
-    build.build_hosts()
-    return cu.SAM
-
-
-def inflated(data):
-    return b"".join(x for x, _ in m.members(data))
-
-
 def three(sam, words, path, extra=(), expect_path="device path"):
-    """device path, host reader, stdin: (code, inflated stdout, stderr) of each, checked equal; the trace names the path"""
-    who = "sam " + " ".join(words)
-    runs = []
-    for env, args, stdin in (({"SK_BAMFILE_TRACE": "1"}, list(words) + list(extra) + [str(path)], None),
-                             ({"SK_BAMFILE_TRACE": "1", "SEQKIT_HOST_INFLATE": "1"}, list(words) + list(extra) + [str(path)], None),
-                             ({"SK_BAMFILE_TRACE": "1"}, list(words) + list(extra) + ["-"], open(path, "rb").read())):
-        code, out, err = cu.run(sam, args, stdin=stdin, env=env)
-        runs.append((code, out, err))
-    traces = [[ln for ln in err.split(b"\n") if ln.startswith(who.encode() + b": ")] for _, _, err in runs]
-    assert traces[0] and traces[0][0].startswith((who + ": " + expect_path).encode()), traces[0]
-    assert traces[1] == [(who + ": host reader").encode()] and traces[2] == traces[1]
-    assert runs[0][0] == runs[1][0] == runs[2][0]
-    outs = [inflated(out) for _, out, _ in runs]
-    assert outs[0] == outs[1] == outs[2]
-    strip = [b"\n".join(ln for ln in err.split(b"\n") if not ln.startswith((who + ": ").encode()) and not ln.startswith(b"sk_bam")) for _, _, err in runs]
-    assert strip[0] == strip[1] == strip[2]
-    return runs[0][0], outs[0], strip[0], runs
+    return bu.three(sam, m, words, path, extra, expect_path)
 
 
 @pytest.mark.parametrize("op,uncompressed", [("trim qnames", False), ("tags from qname", False), ("tags from qname", True),
@@ -105,7 +80,7 @@ def test_round_trip_umi(sam, tmp_path):
     mid.write_bytes(tagged)
     code, back, err = cu.run(sam, ["qname", "from", "tags", str(mid)])
     assert code == 0, err
-    raw = inflated(back)
+    raw = bu.inflated(m, back)
     got = [r[36:36 + r[12] - 1] for r in m.records(raw)]
     want = [n.replace(b" UMI:", b" RX:") for n in names]
     assert got == want

@@ -6,32 +6,15 @@ import struct
 import pytest
 
 from tests import bam_markdup_model as m
+from tests.bam_out_util import checked_windows
 
 pytestmark = pytest.mark.gpu
 
 
 def collect(ctx, path, ignore_umi=False, level=1, window_bytes=0):
-    handled, n_rec, n_dup, raw_bytes, info = ctx.bam_file_markdup(str(path), ignore_umi, level, window_bytes)
-    if not handled:
-        assert n_rec == 0 and n_dup == 0 and raw_bytes == 0
-        return False, info, None, 0, 0
-    wins = list(ctx.bam_file_rewrite_windows())
-    assert wins[0]["n"] == 0 and wins[0]["first"] == 0 and wins[0]["bgzf"]          # the header's members first
-    at = 0
-    for w in wins[1:]:                                                                # then the records, in order
-        assert w["first"] == at and w["n"] > 0
-        at += w["n"]
-    assert at == n_rec
-    data = b"".join(w["bgzf"] for w in wins)
-    assert data.endswith(m.EOF_BLOCK)
-    mem = m.members(data)
-    assert mem[-1][0] == b""
-    assert all(0 < len(x) <= 0xFF00 for x, _ in mem[:-1])
-    for w in wins:                                                                    # each window's members inflate to its raw bytes
-        assert len(b"".join(x for x, _ in m.members(w["bgzf"]))) == w["raw_bytes"]
-    out = b"".join(x for x, _ in mem)
-    assert len(out) == raw_bytes
-    return True, out, mem, len(wins), n_dup
+    result = ctx.bam_file_markdup(str(path), ignore_umi, level, window_bytes)
+    handled, out, mem, n_win, info = checked_windows(ctx, result, m)
+    return handled, out if handled else info, mem, n_win, result[2]
 
 
 def check(ctx, path, raw, ignore_umi=False, level=1, window_bytes=0):

@@ -3,32 +3,13 @@ BGZF-compressed on the device from the inflated BAM file — against the plain-P
 import pytest
 
 from tests import bam_rewrite_model as m
+from tests.bam_out_util import checked_windows
 
 pytestmark = pytest.mark.gpu
 
 
 def collect(ctx, path, op, level, window_bytes):
-    handled, n_rec, raw_bytes, info = ctx.bam_file_rewrite(str(path), op, level, window_bytes)
-    if not handled:
-        return False, None, None
-    wins = list(ctx.bam_file_rewrite_windows())
-    assert wins[0]["n"] == 0 and wins[0]["first"] == 0 and wins[0]["bgzf"]          # the header's members first
-    at = 0
-    for w in wins[1:]:                                                                # then the records, in order
-        assert w["first"] == at and w["n"] > 0
-        at += w["n"]
-    assert at == n_rec
-    data = b"".join(w["bgzf"] for w in wins)
-    assert data.endswith(m.EOF_BLOCK)
-    mem = m.members(data)
-    assert mem[-1][0] == b""
-    assert all(0 < len(x) <= 0xFF00 for x, _ in mem[:-1])
-    for w in wins:                                                                    # each window's members inflate to its raw bytes
-        got = b"".join(x for x, _ in m.members(w["bgzf"]))
-        assert len(got) == w["raw_bytes"]
-    out = b"".join(x for x, _ in mem)
-    assert len(out) == raw_bytes
-    return True, out, mem
+    return checked_windows(ctx, ctx.bam_file_rewrite(str(path), op, level, window_bytes), m)[:3]
 
 
 def ctx_windows(ctx, path, op, level, window_bytes):
