@@ -365,6 +365,15 @@ class Context:
         self._check(self._lib.sk_bgzf_deflate(self._h, src.ctypes.data, len(data), blocks.ctypes.data, n, out.ctypes.data, out.nbytes, off.ctypes.data), "sk_bgzf_deflate")
         return out[:int(off[n])].tobytes()
 
+    DEFLATE_MAX_IN = 0xff00          # SK_DEFLATE_MAX_IN
+    DEFLATE_SLOT = 81920             # SK_DEFLATE_SLOT
+
+    def bgzf_deflate_dev(self, src: int, blocks: int, n_blocks: int, slots: int, slot_stride: int, tokens: int, result: int, crc: int) -> None:
+        """sk_bgzf_deflate_dev, the device half alone (all pointers are device addresses): block i's DEFLATE payload to
+        slots[i * slot_stride ..], result[2 i] its bytes and result[2 i + 1] its tokens, crc[i] the CRC-32 of its input;
+        tokens is scratch of n_blocks * DEFLATE_MAX_IN * 4 bytes.  `src` must be readable 8 bytes behind the last block."""
+        self._check(self._lib.sk_bgzf_deflate_dev(self._h, src, blocks, n_blocks, slots, slot_stride, tokens, result, crc), "sk_bgzf_deflate_dev")
+
     # ---- B1 on the device: BGZF inflate, record walk (all pointers are device addresses) ----
     BGZF_BLOCK_DTYPE = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("out_off", "<u8"), ("crc32", "<u4"), ("reserved", "<u4")])
 

@@ -10,7 +10,7 @@
 // bgzf_deflate_kernel — ONE WAVE PER BLOCK of at most 0xff00 input bytes, three phases:
 //   A  tokens.  64 positions at a time, a lane each: the four bytes at the position are hashed (12 bits), the table of last
 //      positions (LDS) gives a candidate, the lane measures the match (4 bytes per step, up to 258); the table then takes
-//      the chunk's own positions.  The greedy parse — a match of three or more is taken and skips what it covers — is a
+//      the chunk's own positions.  The greedy parse — a match of four or more is taken and skips what it covers — is a
 //      scalar loop over the chunk's 64 lengths (v_readlane, a few instructions a position); the positions where a token
 //      begins leave as 4-byte tokens (a ballot's prefix count places them) and are counted in the two histograms (LDS
 //      atomics).

@@ -2,7 +2,9 @@
 member with the BC subfield, the right CRC32 and ISIZE, a DEFLATE stream zlib accepts — and inflate to exactly the bytes that
 went in (parity is on the decompressed stream: the reference's compressed bytes are its gzip child's).  Every kind of input the
 three phases have a path for: nothing to match, everything a match, runs, matches at the longest distance a block allows,
-blocks of 1 .. 5 bytes, exactly 0xff00 bytes, skewed histograms (codes that want more than 15 bits), bytes the host stores."""
+blocks of 1 .. 5 bytes, exactly 0xff00 bytes, skewed histograms (codes that want more than 15 bits), bytes the host stores.
+This file sees the deflater through the framed round trip alone; which tokens and codes the kernel produces, payloads the host
+would store, and every edge the phases have are tests/test_gpu_deflate_crafted.py's."""
 import gzip
 import zlib
 
@@ -11,6 +13,7 @@ import pytest
 
 from seqkit_amd import synth
 from tests import bam_spec
+from tests import deflate_device_model as dm
 
 pytestmark = pytest.mark.gpu
 
@@ -27,15 +30,22 @@ def corpus():
            ("a block and one byte", (b"ACGTTGCAAC" * 7000)[:0xff00 + 1]),
            ("period 3", b"abc" * 30000),
            ("4 letters uniform (no matches worth taking)", rng.integers(0, 4, 100_000, dtype=np.uint8).tobytes()),
-           ("far matches", (lambda p: p + rng.integers(0, 256, 30000, dtype=np.uint8).tobytes() + p + rng.integers(0, 256, 32000, dtype=np.uint8).tobytes() + p)(rng.integers(0, 256, 500, dtype=np.uint8).tobytes())),
+           # a phrase between random filler: the filler overwrites the table's 4096 slots long before the phrase returns (one match
+           # survives, at distance 3276), the block does not shrink and is framed as stored
+           ("a phrase in random filler (stored)", (lambda p: p + rng.integers(0, 256, 30000, dtype=np.uint8).tobytes() + p + rng.integers(0, 256, 32000, dtype=np.uint8).tobytes() + p)(rng.integers(0, 256, 500, dtype=np.uint8).tobytes())),
+           # the same with a filler that leaves the phrase's slots alone: matches of 258 bytes at distances of 30500 and 32500
+           ("far matches that are real", dm.far_match_case().data),
            ]
-    # a Fibonacci-shaped histogram: an unbounded Huffman code would be deeper than 15 bits
+    # a Fibonacci-shaped histogram of BYTES: the matcher turns most of them into matches, the literal histogram that is left is not
+    # Fibonacci-shaped and its code is 14 bits deep (def_huffman's retry does not run)
     fib = [1, 1]
     while len(fib) < 24:
         fib.append(fib[-1] + fib[-2])
     skew = np.concatenate([np.full(f, i, dtype=np.uint8) for i, f in enumerate(fib)])
     rng.shuffle(skew)
-    out.append(("fibonacci histogram", skew.tobytes()[:0xff00]))
+    out.append(("fibonacci bytes (matched away)", skew.tobytes()[:0xff00]))
+    # the literal/length code that does need the retry with halved frequencies, in a block that shrinks
+    out.append(("a literal/length code that needs the retry", dm.retry_case().data))
     return out
 
 
