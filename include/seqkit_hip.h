@@ -421,7 +421,8 @@ int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
  * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
  * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
  * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
- * sk_bam_file_rewrite (or sk_bam_file_minimize or sk_bam_file_markdup, below, whose windows it hands out too): SK_ERR_INVALID.                         */
+ * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup or sk_bam_file_subsample, below, whose windows it hands out too):
+ * SK_ERR_INVALID.                                                                                                                 */
 #define SK_REWRITE_TRIM_QNAMES     1
 #define SK_REWRITE_QNAME_FROM_TAGS 2
 #define SK_REWRITE_TAGS_FROM_QNAME 3
@@ -476,6 +477,30 @@ int sk_bam_file_minimize(sk_ctx *ctx, const char *path, int flags, uint8_t baseq
  * sk_bam_file_rewrite_next under its rules.                                                                                      */
 int sk_bam_file_markdup(sk_ctx *ctx, const char *path, int ignore_umi, int level /* 0 stored, 1 deflate */, uint64_t window_bytes /* 0 = default */,
                         int64_t *n_records, int64_t *n_duplicates, uint64_t *raw_bytes, int *handled, double info[8]);
+
+/* ---- BAM out for `sam subsample` (src/sam_subsample.rs:30-62) ----------------------------------------------------------------
+ * sk_subsample_keep: the fate of draw number `draw` (1, 2, 3 ..) under `seed`, host code that needs no device: with all arithmetic mod
+ * 2^64, z = seed + draw * 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >>
+ * 31 (splitmix64's draw-th output from state seed); m = z >> 40; 1 (keep) iff m <= floor(fraction * 2^24), else 0.  In integers that is
+ * rand 0.5's random::<f32>() <= fraction with random::<f32>() = (u32 >> 8) * 2^-24.  A fraction outside [0, 1] or NaN: SK_ERR_INVALID.
+ * sk_bam_file_subsample: sk_bam_file_rewrite's front half, window pipeline and header; a record is written byte for byte or not at all.
+ * A record with 0x800 is passed over: not counted, not written.  Every other record is counted, and its key is its qname; in file order
+ * the 1st, 3rd, 5th .. counted record of a key makes the next draw, starting at 1, and the 2nd, 4th .. takes the decision of the counted
+ * record of that key just before it (the reference's map, whose entry is removed when the mate arrives).  *n_records: the records
+ * written; *n_total: the records counted; *raw_bytes: the whole output BAM, inflated.  The windows come from sk_bam_file_rewrite_next
+ * under its rules, first and n numbering the records WRITTEN; a file none of whose records is written yields, as a file without
+ * records does there, one window: the header's members and the EOF block.  *handled = 0 (info[5] = -(30 + bits)) leaves the file to the caller's reader, nothing
+ * written: bit 1 a counted record without 0x1 (the reference ends there), 8 a record whose variable part is shorter than its fields, 64
+ * two different keys with one hash (verified byte for byte, never guessed); info[5] = -21: 2^32 records or more, or the working memory
+ * (16 B per record for the offsets; 32 B per record and the sort's scratch for the passes where those do not fit into the device buffer
+ * of the compressed file, which is idle by then) cannot be had.  A fraction outside [0, 1] or NaN, or a bad
+ * level: SK_ERR_INVALID.  level, window_bytes: as sk_bam_file_rewrite.  SK_SUBSAMPLE_KEY_BITS=k (1 .. 64, read per call) keeps only the
+ * low k bits of the hash (at most 63: the bit above them marks a record with 0x800): a knob for tests of the collision check, of no
+ * other use.                                                                                                                      */
+int sk_subsample_keep(uint64_t seed, uint64_t draw, float fraction);
+int sk_bam_file_subsample(sk_ctx *ctx, const char *path, float fraction, uint64_t seed, int level /* 0 stored, 1 deflate */,
+                          uint64_t window_bytes /* 0 = default */, int64_t *n_records, int64_t *n_total, uint64_t *raw_bytes, int *handled,
+                          double info[8]);
 
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
     "sk_timer_start", "sk_timer_stop",
@@ -244,6 +244,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_file_rewrite_next": (i32, [vp, C.POINTER(_OutWindow)]),
         "sk_bam_file_minimize": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_markdup": (i32, [vp, C.c_char_p, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_subsample_keep": (i32, [C.c_uint64, C.c_uint64, C.c_float]),
+        "sk_bam_file_subsample": (i32, [vp, C.c_char_p, C.c_float, C.c_uint64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
         "sk_bam_fragments_bed_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(i64)]),
@@ -282,6 +284,11 @@ def blocked_layout(n_mates: int, stride: int, bc_stride: int, flags: int, lib=No
     if rc != 0:
         raise SeqkitHipError(f"sk_blocked_layout_init({n_mates}, {stride}, {bc_stride}, {flags}) failed ({rc})")
     return lay
+
+
+def subsample_keep(seed: int, draw: int, fraction: float, lib=None) -> int:
+    """sk_subsample_keep (no device): 1 keep, 0 drop, -1 (SK_ERR_INVALID) for a fraction outside [0, 1] or NaN."""
+    return int((lib or load_library()).sk_subsample_keep(seed, draw, fraction))
 
 
 def comm_unique_id(lib=None) -> bytes:
@@ -458,8 +465,9 @@ class Context:
                    "names": C.string_at(w.names, int(name_off[-1])) if name_off[-1] else b"", "name_off": name_off}
 
     def _bam_out_call(self, name: str, path: str, args, with_duplicates: bool = False):
-        """One of the calls that set rewrite windows up (sk_bam_file_rewrite, _minimize, _markdup): its own arguments, which end with the
-        window size, then the out-parameters they share.  (handled, records, [duplicates,] inflated output bytes, info f64[8])."""
+        """One of the calls that set rewrite windows up (sk_bam_file_rewrite, _minimize, _markdup, _subsample): its own arguments, which end with
+        the window size, then the out-parameters they share.  (handled, records, [second count,] inflated output bytes, info f64[8]);
+        with_duplicates: the call has a second count (markdup: the duplicates; subsample: the records counted)."""
         n_rec, n_dup, raw_bytes, handled = C.c_int64(0), C.c_int64(0), C.c_uint64(0), C.c_int32(0)
         info = (C.c_double * 8)()
         counts = [n_rec, n_dup] if with_duplicates else [n_rec]
@@ -483,8 +491,13 @@ class Context:
         windows."""
         return self._bam_out_call("sk_bam_file_markdup", path, (1 if ignore_umi else 0, level, window_bytes), with_duplicates=True)
 
+    def bam_file_subsample(self, path: str, fraction: float, seed: int, level: int = 1, window_bytes: int = 0):
+        """sk_bam_file_subsample: (handled, records written, records counted, inflated output bytes, info f64[8]); then
+        bam_file_rewrite_windows() yields the windows."""
+        return self._bam_out_call("sk_bam_file_subsample", path, (fraction, seed, level, window_bytes), with_duplicates=True)
+
     def bam_file_rewrite_windows(self):
-        """sk_bam_file_rewrite_next (after bam_file_rewrite, bam_file_minimize or bam_file_markdup) until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""
+        """sk_bam_file_rewrite_next (after bam_file_rewrite, bam_file_minimize, bam_file_markdup or bam_file_subsample) until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""
         while True:
             w = _OutWindow()
             self._check(self._lib.sk_bam_file_rewrite_next(self._h, C.byref(w)), "sk_bam_file_rewrite_next")

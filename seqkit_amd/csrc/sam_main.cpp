@@ -15,10 +15,11 @@
 // and `sam count` then run their order checks and their text on the device too, and whatever is irregular falls back to the reader
 // here before anything has been written.  `sam to` takes the file the same way: the device writes every record's text, window by
 // window, and the mate pairing stays here.  The commands that write BAM to stdout (trim qnames, tags from qname, qname from tags, minimize,
-// mark duplicates) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
+// mark duplicates, subsample) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
 // device does not take the reader and writer of HostBamRewrite around the command's own per-record loop.
 #include <unistd.h>
 #include <malloc.h>
+#include <sys/random.h>
 #include <zlib.h>
 #include <fcntl.h>
 
@@ -1087,7 +1088,9 @@ public:
 		std::vector<sk_deflate_block> blocks(nblk);
 		for (size_t i = 0; i < nblk; i++) { blocks[i].in_off = i * SK_DEFLATE_MAX_IN; blocks[i].in_len = (uint32_t)std::min<size_t>(SK_DEFLATE_MAX_IN, n - i * SK_DEFLATE_MAX_IN); blocks[i].reserved = 0; }
 		std::vector<uint64_t> off(nblk + 1);
-		if (level_) {
+		static const bool here = [] { const char *e = getenv("SEQKIT_GPU_DEFLATE"); return e && atoi(e) == 0; }();
+		if (level_ && here) deflate_here(blocks, off);
+		else if (level_) {
 			comp_.resize(nblk * SK_DEFLATE_MAX_MEMBER);
 			check(sk_bgzf_deflate(host::gpu(), buf_.data(), n, blocks.data(), (int64_t)nblk, comp_.data(), comp_.size(), off.data()), "sk_bgzf_deflate");
 		} else {
@@ -1126,11 +1129,45 @@ public:
 		}
 	}
 private:
+	void deflate_here(const std::vector<sk_deflate_block> &blocks, std::vector<uint64_t> &off);
 	static constexpr size_t kBatch = (size_t)256 * SK_DEFLATE_MAX_IN;
 	int level_;
 	bool done_ = false;
 	std::vector<uint8_t> buf_, comp_;
 };
+
+// (SEQKIT_GPU_DEFLATE=0, the gzip writers' switch: level 1 is deflated here by zlib instead — the inflated stream is the same, and a
+// command without --uncompressed can then be run where there is no device)
+void BamOut::deflate_here(const std::vector<sk_deflate_block> &blocks, std::vector<uint64_t> &off)
+{
+	comp_.resize(blocks.size() * SK_DEFLATE_MAX_MEMBER);
+	size_t at = 0;
+	static const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+	for (size_t i = 0; i < blocks.size(); i++) {
+		const uint32_t len = blocks[i].in_len;
+		const uint8_t *src = buf_.data() + blocks[i].in_off;
+		uint8_t *m = comp_.data() + at;
+		z_stream z;
+		memset(&z, 0, sizeof z);
+		if (deflateInit2(&z, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) error("zlib: deflateInit2 failed");
+		z.next_in = const_cast<uint8_t *>(src); z.avail_in = len;
+		z.next_out = m + 18; z.avail_out = SK_DEFLATE_MAX_MEMBER - 26;
+		const int zr = deflate(&z, Z_FINISH);
+		uint32_t clen = (uint32_t)z.total_out;
+		deflateEnd(&z);
+		if (zr != Z_STREAM_END) {                                          // (it does not fit a member: stored)
+			m[18] = 1; m[19] = (uint8_t)(len & 0xff); m[20] = (uint8_t)(len >> 8); m[21] = (uint8_t)(~len & 0xff); m[22] = (uint8_t)((~len >> 8) & 0xff);
+			memcpy(m + 23, src, len);
+			clen = len + 5;
+		}
+		const uint32_t bsize = clen + 26, crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, len);
+		memcpy(m, head, 16);
+		m[16] = (uint8_t)((bsize - 1) & 0xff); m[17] = (uint8_t)((bsize - 1) >> 8);
+		for (int k = 0; k < 4; k++) { m[18 + clen + k] = (uint8_t)(crc >> (8 * k)); m[22 + clen + k] = (uint8_t)(len >> (8 * k)); }
+		at += bsize;
+	}
+	off[blocks.size()] = at;
+}
 
 static BamOut *g_bam_out = nullptr;
 static void finish_bam_out() { if (g_bam_out) g_bam_out->finish(); }    // a panic unwinds through the Writer's drop: what was written stays valid BAM
@@ -1168,8 +1205,8 @@ static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
 	return false;
 }
 
-// The device path of a BAM-writing command: `start` makes the file call that sets the windows up (sk_bam_file_rewrite, _minimize or
-// _markdup), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
+// The device path of a BAM-writing command: `start` makes the file call that sets the windows up (sk_bam_file_rewrite, _minimize,
+// _markdup or _subsample), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
 // the file path does not take, a device without room, or a record the reference would stop at).  Otherwise the number of records.
 template <class Start>
 static int64_t bam_out_from_file(Start start)
@@ -1533,6 +1570,113 @@ static int mark_duplicates_cmd(int argc, char **argv)
 	return 0;
 }
 
+// ---- sam subsample -----------------------------------------------------------------------------------------------------
+// src/sam_subsample.rs: a fraction of the fragments is kept, mates together.  The reference draws from an unseeded generator; here draw
+// number d is a pure function of (seed, d) (sk_subsample_keep), the seed --seed=N or 8 bytes from the OS, so that the device, which
+// numbers the fragments with a sort, and the loop below write the same bytes.  A regular file goes to the device whole
+// (sk_bam_file_subsample: fragment numbers, decisions, the kept records compacted, then the rewrite windows); stdin,
+// SEQKIT_HOST_INFLATE=1 and every file the device declines — a counted record without 0x1, an invalid record, or two names with one
+// hash — are read record by record below.
+static const char *USAGE_SUBSAMPLE =
+	"\nUsage:\n  sam subsample [options] <bam_file> <fraction>\n\nOptions:\n"
+	"  --seed=N    Seed of the random draws, for a reproducible result [default: from the OS]\n\n"
+	"If your BAM file has been duplicate-flagged, remember to re-run duplicate\nflagging after subsampling, otherwise random subsampling can delete the only\n"
+	"non-duplicate-flagged DNA fragment in a duplicate cluster.\n";
+
+// str::parse::<f32>(): [+-] then inf | infinity | nan in any case, or digits with at most one '.' and at least one digit, then an
+// optional exponent [eE][+-]digits; nothing else, no blanks.  The value is the nearest f32 (strtof rounds correctly).
+static bool parse_f32(const std::string &s, float &out)
+{
+	size_t i = 0;
+	if (i < s.size() && (s[i] == '+' || s[i] == '-')) i++;
+	std::string low;
+	for (size_t k = i; k < s.size(); k++) low.push_back((char)(s[k] >= 'A' && s[k] <= 'Z' ? s[k] + 32 : s[k]));
+	if (low != "inf" && low != "infinity" && low != "nan") {
+		size_t digits = 0;
+		while (i < s.size() && s[i] >= '0' && s[i] <= '9') { i++; digits++; }
+		if (i < s.size() && s[i] == '.') i++;
+		while (i < s.size() && s[i] >= '0' && s[i] <= '9') { i++; digits++; }
+		if (!digits) return false;
+		if (i < s.size() && (s[i] == 'e' || s[i] == 'E')) {
+			i++;
+			if (i < s.size() && (s[i] == '+' || s[i] == '-')) i++;
+			size_t ed = 0;
+			while (i < s.size() && s[i] >= '0' && s[i] <= '9') { i++; ed++; }
+			if (!ed) return false;
+		}
+		if (i != s.size()) return false;
+	}
+	out = strtof(s.c_str(), nullptr);
+	return true;
+}
+
+static void subsample_summary(uint64_t kept, uint64_t total)                  // :61-62
+{
+	fprintf(stderr, "Total reads: %llu\n", (unsigned long long)total);
+	fprintf(stderr, "Kept reads: %llu (%s%% of all reads)\n", (unsigned long long)kept, host::fmt_pct((double)kept / (double)total * 100.0).c_str());
+}
+
+static int subsample_cmd(int argc, char **argv)
+{
+	// (a fraction such as -0.1 is a positional whose value the command itself refuses: it goes behind a "--" of its own)
+	std::vector<char *> av(argv, argv + 2), rest;
+	bool only_pos = false;
+	for (int i = 2; i < argc; i++) {
+		char *a = argv[i];
+		if (!only_pos && strcmp(a, "--") == 0) { only_pos = true; continue; }
+		const bool number = a[0] == '-' && ((a[1] >= '0' && a[1] <= '9') || a[1] == '.');
+		(only_pos || number ? rest : av).push_back(a);
+	}
+	static char dashes[] = "--";
+	av.push_back(dashes);
+	av.insert(av.end(), rest.begin(), rest.end());
+	std::vector<host::Opt> opts = {{"--seed", true, false, ""}};
+	std::vector<std::string> pos;
+	if (!host::parse_args((int)av.size(), av.data(), 2, opts, pos, 2) || pos.size() != 2) error("Invalid arguments.\n%s", USAGE_SUBSAMPLE);
+	const std::string path = expand_home(pos[0]);
+	uint64_t seed = 0;
+	if (opts[0].present) {
+		if (!host::parse_uint(opts[0].value.c_str(), UINT64_MAX, seed)) error("--seed must be an integer between 0 and 18446744073709551615.");
+	} else if (getrandom(&seed, sizeof seed, 0) != (ssize_t)sizeof seed) error("Cannot get a seed from the operating system.");
+	float frac = -1.0f;
+	if (!parse_f32(pos[1], frac) || !(frac >= 0.0f && frac <= 1.0f)) error("Subsampling fraction must be between 0 - 1.");     // :19-22
+	host::gpu_warmup();
+	int64_t counted = 0;
+	const int64_t n_dev = device_path("sam subsample", path, [&] { return bam_out_from_file([&](sk_ctx *ctx, uint64_t window, int64_t *n, uint64_t *raw, int *handled) {
+		    return sk_bam_file_subsample(ctx, path.c_str(), frac, seed, 1, window, n, &counted, raw, handled, nullptr); }); });
+	if (n_dev >= 0) {
+		subsample_summary((uint64_t)n_dev, (uint64_t)counted);
+		return 0;
+	}
+	HostBamRewrite io(path, 1);
+	BamStream &bam = io.bam;
+	BamOut &out = io.out;
+	uint64_t total_reads = 0, kept_reads = 0, draws = 0;
+	std::unordered_map<std::string, bool> keep_mate;                              // :33
+	BamCore c;
+	BamStream::Var v;
+	std::vector<uint8_t> body;
+	std::string name;
+	while (bam.next_full(c, v, body)) {
+		if (c.flag & 0x800) continue;                                             // :36
+		if (!(c.flag & 0x1)) error("Only paired end sequencing data supported for now.");      // :57
+		name.assign(reinterpret_cast<const char *>(body.data()), v.l_read_name - 1);
+		bool keep;
+		auto it = keep_mate.find(name);
+		if (it != keep_mate.end()) { keep = it->second; keep_mate.erase(it); }
+		else { keep = sk_subsample_keep(seed, ++draws, frac) == 1; keep_mate.emplace(name, keep); }
+		if (keep) {
+			out.put(bam.head, 36);
+			out.put(body.data(), body.size());
+			kept_reads++;
+		}
+		total_reads++;
+	}
+	io.close();
+	subsample_summary(kept_reads, total_reads);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	// blocks, per-sample strings and gzip jobs are hundreds of KiB each: above glibc's default mmap threshold every one of them was a
@@ -1556,6 +1700,7 @@ int main(int argc, char **argv)
 	else if (argc >= 3 && is(1, "trim") && is(2, "qnames")) rc = rewrite_cmd(argc, argv, SK_REWRITE_TRIM_QNAMES, 3, USAGE_TRIM, false);
 	else if (argc >= 2 && is(1, "minimize")) rc = minimize_cmd(argc, argv);
 	else if (argc >= 3 && is(1, "mark") && is(2, "duplicates")) rc = mark_duplicates_cmd(argc, argv);
+	else if (argc >= 2 && is(1, "subsample")) rc = subsample_cmd(argc, argv);
 	else fprintf(stderr, "%s\n", USAGE_TOP);
 	host::out().flush();
 	// everything is written and closed: what is left is taking the process apart (static destructors, the HIP runtime's exit handlers,

@@ -177,7 +177,7 @@ static bool blocking_event(hipEvent_t &e)
 	return true;
 }
 
-// The double buffer of a windowed file call (sk_bam_file_reads; sk_bam_file_rewrite, _minimize and _markdup): the window plan, the next window to issue, and per
+// The double buffer of a windowed file call (sk_bam_file_reads; sk_bam_file_rewrite, _minimize, _markdup and _subsample): the window plan, the next window to issue, and per
 // buffer the window in it and the event its work ends with.  One window is in flight while the caller works on the other.
 struct WindowedState {
 	bool live = false;
@@ -214,16 +214,16 @@ struct ReadsState : WindowedState {
 	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
 };
 
-// Which of the three rewrite-window calls is running — the kernel that writes a window's records — and what that kernel takes
+// Which of the rewrite-window calls is running — the kernel that writes a window's records — and what that kernel takes
 struct WriteOp {
-	enum Kind { kRewrite, kMinimize, kMarkdup } kind = kRewrite;
+	enum Kind { kRewrite, kMinimize, kMarkdup, kSubsample } kind = kRewrite;
 	int flags = 0;                               // kRewrite: SK_REWRITE_*; kMinimize: SK_MINIMIZE_*
 	uint8_t fill = 255;                          // kMinimize: the qualities' fill byte
 	const uint32_t *ids = nullptr;               // kMinimize: the read ids (ctx slot kKeepPassWork; nullptr without SK_MINIMIZE_READ_IDS)
 	const uint16_t *md_flags = nullptr;          // kMarkdup: every record's flag (ctx slot kKeepPassWork)
 };
 
-// sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_markdup and sk_bam_file_rewrite_next: every record's stream and output offsets
+// sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_markdup / sk_bam_file_subsample and sk_bam_file_rewrite_next: every written record's stream and output offsets
 // (device, ctx slot kKeepFileCols), the window plan (output bytes of window w from wo[w] on), the write kernel of the call that runs,
 // one device area for the window being rewritten and compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on
 // each side (ctx slots kKeepFileWin / kKeepFilePin)
@@ -977,7 +977,7 @@ extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
 	return SK_OK;
 }
 
-// ---- BAM out (include/seqkit_hip.h: sk_bam_file_rewrite, sk_bam_file_minimize, sk_bam_file_markdup; sk_bam_file_rewrite_next) ---
+// ---- BAM out (include/seqkit_hip.h: sk_bam_file_rewrite, sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample; sk_bam_file_rewrite_next) ---
 // The front half above, then the call's own passes, among them a sizing pass (per block: output bytes, decline bits) and its scan; the
 // decision to serve the file is taken there, before any window exists.  Then every record's stream and output offsets, the windows, and
 // the header's members on their way.  A window is rewritten into one device buffer, cut into blocks of at most 0xff00 bytes, deflated where it lies and packed into
@@ -1007,6 +1007,7 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		case WriteOp::kRewrite: e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], op.flags, s.d_raw, sk::ctx_n_cu(c), st); break;
 		case WriteOp::kMinimize: e = sk::launch_bam_min_write(s.d_out, s.krec, s.kout, op.ids, first, n, s.wo[w], op.flags, op.fill, s.d_raw, sk::ctx_n_cu(c), st); break;
 		case WriteOp::kMarkdup: e = sk::launch_bam_md_write(s.d_out, s.krec, s.kout, op.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kSubsample: e = sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
 		}
 	}
 	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
@@ -1024,7 +1025,7 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 	return true;
 }
 
-// What sk_bam_file_rewrite, sk_bam_file_minimize and sk_bam_file_markdup open with once the stream is verified: the per-block scratch of
+// What sk_bam_file_rewrite, sk_bam_file_minimize, sk_bam_file_markdup and sk_bam_file_subsample open with once the stream is verified: the per-block scratch of
 // their passes with the decline word behind it, the blocks' first record indices on the device, and the rewrite state with room for
 // every record's stream and output offsets (ctx slot kKeepFileCols).  s == nullptr afterwards: that memory cannot be had, and the file
 // is left to the caller's reader (info[5] = -21).
@@ -1058,13 +1059,13 @@ static int rw_open(sk_ctx *c, Cleanup &cl, const Front &fr, int blk_cols, RwOpen
 	return SK_OK;
 }
 
-// What the three share once every record's stream and output offsets (s.krec, s.kout) are there: the window plan, the window area, and
-// the header's members on their way.  `write`: the kernel that writes a window; `total`: the records' output bytes.
-static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WriteOp &write, int level, uint64_t window_bytes, uint64_t total,
-                    int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
+// What they share once the stream and output offsets (s.krec, s.kout) of the N records that go out are there — every record of the file,
+// or for sk_bam_file_subsample the kept ones —: the window plan, the window area, and the header's members on their way.  `write`: the
+// kernel that writes a window; `total`: the records' output bytes.
+static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WriteOp &write, int level, uint64_t window_bytes, uint64_t N,
+                    uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
 {
 	RewriteState &s = *o.s;
-	const uint64_t N = fr.n_records;
 	int krc = SK_OK;
 	// ---- the windows: at most W rewritten bytes each
 	uint64_t mx[3];                                                     // records, rewritten bytes
@@ -1135,7 +1136,7 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 	BF_LEAVE_DECLINED(o.d_decline, 0);                                  // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
 	// ---- every record's stream and output offsets
 	BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, o.d_rb, o.s->krec, o.s->kout, st));
-	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kRewrite, op}, level, window_bytes, total, n_records, raw_bytes, handled, info);
+	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kRewrite, op}, level, window_bytes, fr.n_records, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam minimize (include/seqkit_hip.h: sk_bam_file_minimize; the windows come from sk_bam_file_rewrite_next) ---
@@ -1185,12 +1186,12 @@ extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint
 		key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
 		idx[0] = (uint32_t *)(mb + 2 * a_key); idx[1] = (uint32_t *)(mb + 2 * a_key + a_idx);
 		uint32_t *agg = (uint32_t *)(mb + 2 * a_key + 2 * a_idx);
-		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, bits, krec, key[0], idx[0], o.d_decline, st));
+		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, bits, sk::IdRule{0, 0u}, krec, key[0], idx[0], o.d_decline, st));
 		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (the passes below read the names of valid records only)
 		int cur = 0;
 		BF_HIP(sk::bam_sort_pairs(mb + 2 * a_key + 2 * a_idx + a_agg, &temp_bytes, key, idx, N, bits, &cur, st));
 		uint32_t *src = (uint32_t *)key[cur ^ 1], *cnt = src + N;
-		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, key[cur], idx[cur], N, agg, src, cnt, idx[cur ^ 1], o.d_decline, st));
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, key[cur], idx[cur], N, bits, sk::IdRule{0, 0u}, agg, src, cnt, idx[cur ^ 1], o.d_decline, st));
 		ids = idx[cur ^ 1];
 	}
 	// ---- the sizing pass: per block the output bytes (then their exclusive offsets), the decline bits
@@ -1199,7 +1200,7 @@ extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint
 	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
 	BF_LEAVE_DECLINED(o.d_decline, 0);
 	BF_HIP(sk::launch_bam_min_index(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, flags, ids, bo, krec, kout, st));
-	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMinimize, flags, baseq_fill, ids}, level, window_bytes, total, n_records, raw_bytes, handled, info);
+	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMinimize, flags, baseq_fill, ids}, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam mark duplicates (include/seqkit_hip.h: sk_bam_file_markdup; the windows come from sk_bam_file_rewrite_next) ---
@@ -1279,8 +1280,87 @@ extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, 
 		BF_HIP(hipMemcpyAsync(&dups, d_count, 8, hipMemcpyDeviceToHost, st));
 		BF_HIP(hipStreamSynchronize(st));
 	}
-	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMarkdup, 0, 255, nullptr, cols.nflag}, level, window_bytes, fr.stream_len - fr.first, n_records, raw_bytes, handled, info);
+	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMarkdup, 0, 255, nullptr, cols.nflag}, level, window_bytes, N, fr.stream_len - fr.first, n_records, raw_bytes, handled, info);
 	if (rc == SK_OK && *handled && n_duplicates) *n_duplicates = (int64_t)dups;
+	return rc;
+}
+
+// ---- sam subsample (include/seqkit_hip.h: sk_bam_file_subsample; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then sk_bamminimize.hip's id passes under the rule {the whole name is the key, 0x800 takes no part} — they number the
+// fragments — and the passes of sk_bamsubsample.hip: the keep pass, two scans and the compaction, which leaves the KEPT records' stream
+// and output offsets where sk_bam_file_rewrite leaves every record's.  The working memory (the compressed file's device buffer, idle by
+// then, or where that is too small ctx slot kKeepPassWork): two key and two
+// index buffers for the sort and every record's stream offset, 32 B per record, and the scratch of the sort and the scans; behind the
+// sort the idle key buffer holds src and the opener counts and then the kept lengths and places, the idle index buffer the fragment
+// numbers, and the sorted keys' buffer the output offsets.  Declined files: the list in include/seqkit_hip.h.
+extern "C" int sk_bam_file_subsample(sk_ctx *c, const char *path, float fraction, uint64_t seed, int level, uint64_t window_bytes, int64_t *n_records,
+                                     int64_t *n_total, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_subsample", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (n_total) *n_total = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (!(fraction >= 0.0f && fraction <= 1.0f)) return sk::ctx_fail(c, SK_ERR_INVALID, "fraction = %g", (double)fraction);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 3, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *d_counts = o.d_blk;                                       // (no per-block column, three words: counted, kept, kept bytes)
+	uint64_t counts[3] = {0, 0, 0};
+	if (N) {
+		const sk::IdRule rule{1, 0x800u};
+		int bits = 63;                                                  // (a test knob: fewer bits make hash collisions reachable; bit `bits` marks a record with 0x800)
+		if (const char *ev = getenv("SK_SUBSAMPLE_KEY_BITS")) { const int v = atoi(ev); if (v >= 1 && v <= 64) bits = std::min(v, 63); }
+		uint64_t *key[2] = {nullptr, nullptr};
+		uint32_t *idx[2] = {nullptr, nullptr};
+		size_t sort_bytes = 0, scan_bytes = 0;
+		BF_HIP(sk::bam_sort_pairs(nullptr, &sort_bytes, key, idx, N, bits + 1, nullptr, st));
+		BF_HIP(sk::bam_sub_scans(nullptr, &scan_bytes, nullptr, nullptr, nullptr, N, st));
+		const size_t a_key = up(N * 8), a_idx = up(N * 4), a_agg = up((N / 1024 + 2) * 4), temp_bytes = std::max(sort_bytes, scan_bytes);
+		// (all of it is idle once the kept records are compacted: as sk_bam_file_markdup's scratch it lies in the device buffer of the
+		// compressed file where that is large enough, and a gigabyte is not taken and given back for a 20 M-record file)
+		const size_t work = 3 * a_key + 2 * a_idx + a_agg + up(temp_bytes);
+		const bool in_comp = fr.fsize + 64 >= work;
+		int krc = SK_OK;
+		uint8_t *mb = in_comp ? fr.d_comp : (uint8_t *)sk::ctx_keep(c, sk::kKeepPassWork, work, false, &krc);
+		if (!mb) BF_LEAVE(21);
+		if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_subsample: %zu bytes of scratch in %s\n", work, in_comp ? "the compressed file's buffer" : "its own buffer");
+		key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
+		uint64_t *krec = (uint64_t *)(mb + 2 * a_key);
+		idx[0] = (uint32_t *)(mb + 3 * a_key); idx[1] = (uint32_t *)(mb + 3 * a_key + a_idx);
+		uint32_t *agg = (uint32_t *)(mb + 3 * a_key + 2 * a_idx);
+		void *temp = mb + 3 * a_key + 2 * a_idx + a_agg;
+		// ---- the fragment numbers
+		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, bits, rule, krec, key[0], idx[0], o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (8: the passes below read the names and flags of valid records only)
+		int cur = 0;
+		size_t tb = temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(temp, &tb, key, idx, N, bits + 1, &cur, st));
+		uint32_t *src = (uint32_t *)key[cur ^ 1], *cnt = src + N, *ids = idx[cur ^ 1];
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, key[cur], idx[cur], N, bits, rule, agg, src, cnt, ids, o.d_decline, st));
+		// ---- the decisions: the file is served or left here
+		uint32_t *len = src, *pos = cnt;
+		uint64_t *off = key[cur];
+		BF_HIP(sk::launch_bam_sub_keep(fr.d_out, krec, ids, N, seed, sk::subsample_threshold(fraction), len, d_counts, o.d_decline, sk::ctx_n_cu(c), st));
+		BF_HIP(hipMemcpyAsync(counts, d_counts, 24, hipMemcpyDeviceToHost, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 a counted record without 0x1, 64 two names with one hash)
+		// ---- the kept records' stream and output offsets
+		tb = temp_bytes;
+		BF_HIP(sk::bam_sub_scans(temp, &tb, len, pos, off, N, st));
+		BF_HIP(sk::launch_bam_sub_compact(krec, len, pos, off, N, o.s->krec, o.s->kout, st));
+	}
+	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kSubsample}, level, window_bytes, counts[1], counts[2], n_records, raw_bytes, handled, info);
+	if (rc == SK_OK && *handled && n_total) *n_total = (int64_t)counts[0];
 	return rc;
 }
 

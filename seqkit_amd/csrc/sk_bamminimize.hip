@@ -13,6 +13,9 @@
 //   predecessor's in the run sets decline bit 64 (a hash collision: the caller's reader serves the file).  With r the rank in the run:
 //   r even: the record opens a number, src[idx] = idx; r odd: src[idx] = the index one place before it.
 // bam_min_open_scan_kernel / bam_min_id_kernel — the inclusive count of openers in RECORD order, then id[k] = count[src[k]].
+// The id passes serve sk_bam_file_subsample too (sk_bamsubsample.hip), under its IdRule (sk_internal.h): the whole name is the key, and
+// a record with flag 0x800 takes no part — its key is the bit above the hash's alone, so it sorts behind every record that does, the run
+// pass gives it no source (kNoSrc: neither an opener nor anybody's predecessor) and its id is 0.
 //
 // The records.  min_plan says what the flags make of one record (the name replaced by the id's digits or kept; `set`: only core, name,
 // CIGAR, bases and qualities stay, the odd base count's pad nibble is cleared, the qualities are copied or filled), and
@@ -40,6 +43,7 @@ typedef unsigned long long u64;
 
 constexpr int kMinThreads = 256;                  // write kernel: 16 groups of 16 lanes; scan kernels: 4 waves, a tile each
 constexpr u32 kTile = 1024;                       // elements a wave scans: 16 rounds of 64
+constexpr u32 kNoSrc = ~0u;                       // src of a record that takes no part (no record has this index: there are fewer than 2^32)
 
 __device__ __forceinline__ u32 id_digits(u32 v)
 {
@@ -55,10 +59,11 @@ __device__ __forceinline__ bool min_valid(const uint8_t *r)
 	return !(bs < 32u || lo < 1u || S > 0x7fffffffu || 4ull * nc + lo + (((u64)S + 1) >> 1) + S > (u64)(bs - 32u));
 }
 
-// the bytes of a valid record's key: its name up to the first '/'
-__device__ __forceinline__ u32 key_len(const uint8_t *r)
+// the bytes of a valid record's key: its name up to the first '/', or (whole) all of it
+__device__ __forceinline__ u32 key_len(const uint8_t *r, bool whole = false)
 {
 	const u32 L = (u32)r[12] - 1u;
+	if (whole) return L;
 	for (u32 k = 0; k < L; k++) if (r[36 + k] == '/') return k;
 	return L;
 }
@@ -128,6 +133,8 @@ struct MinArgs {
 	int flags;
 	u32 fill;
 	u64 key_mask;
+	IdRule rule;
+	u64 skip_key;             // the key of a record that takes no part
 	const u32 *ids;           // per record, with SK_MINIMIZE_READ_IDS
 	u64 *bo;                  // [nb + 1]: per block output bytes, then (bam_scan_u64_kernel) exclusive offsets
 	uint32_t *decline;
@@ -148,8 +155,9 @@ __global__ __launch_bounds__(kBlockWaves * 64) void bam_min_key_kernel(const Min
 	for (u32 j = (u32)lane; j < n; j += 64u) {
 		const uint8_t *r = a.stream + entry + off[j];
 		u64 h = 0;
-		if (min_valid(r)) h = qname_key(r + 36, key_len(r)) & a.key_mask;
-		else dec = 8u;
+		if (!min_valid(r)) dec = 8u;
+		else if ((bam_le32_bytes(r + 16) >> 16) & a.rule.skip_flags) h = a.skip_key;
+		else h = qname_key(r + 36, key_len(r, a.rule.whole_name)) & a.key_mask;
 		a.krec[k0 + j] = entry + off[j];
 		a.key[k0 + j] = h;
 		a.idx[k0 + j] = (u32)(k0 + j);
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(1024) void min_tile_scan_kernel(u32 *agg, u64 nt)
 
 // Sorted position p: the start of its run, its rank r in the run, the check of its key's bytes against its predecessor's, and src.
 __global__ __launch_bounds__(kMinThreads) void bam_min_run_kernel(const uint8_t *stream, const u64 *krec, const u64 *key, const u32 *idx, u64 n,
-                                                                  const u32 *agg, u32 *src, uint32_t *decline)
+                                                                  bool whole, u64 skip_bit, const u32 *agg, u32 *src, uint32_t *decline)
 {
 	const int lane = threadIdx.x & 63;
 	const u64 t = (u64)blockIdx.x * (kMinThreads / 64) + (threadIdx.x >> 6);
@@ -232,11 +240,12 @@ __global__ __launch_bounds__(kMinThreads) void bam_min_run_kernel(const uint8_t 
 		if (p >= n) continue;
 		const u32 r = (u32)p - rs, me = idx[p];
 		u32 from = me;
-		if (r) {
+		if (key[p] & skip_bit) from = kNoSrc;
+		else if (r) {
 			const u32 prev = idx[p - 1];
 			const uint8_t *ra = stream + krec[me], *rb = stream + krec[prev];
-			const u32 la = key_len(ra);
-			bool same = la == key_len(rb);
+			const u32 la = key_len(ra, whole);
+			bool same = la == key_len(rb, whole);
 			for (u32 k = 0; same && k < la; k++) same = ra[36 + k] == rb[36 + k];
 			if (!same) bad = true;
 			if (r & 1u) from = prev;
@@ -264,7 +273,9 @@ __global__ __launch_bounds__(kMinThreads) void bam_min_open_scan_kernel(const u3
 __global__ __launch_bounds__(256) void bam_min_id_kernel(const u32 *src, const u32 *cnt, u64 n, u32 *ids)
 {
 	const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-	if (k < n) ids[k] = cnt[src[k]];
+	if (k >= n) return;
+	const u32 s = src[k];
+	ids[k] = s == kNoSrc ? 0u : cnt[s];
 }
 
 // ---- size, index, write ----
@@ -347,11 +358,12 @@ MinArgs min_args(const uint8_t *stream, const uint64_t *bend, const uint64_t *en
 }  // namespace
 
 hipError_t launch_bam_min_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int key_bits,
-                               uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st)
+                               IdRule rule, uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st)
 {
 	if (nb <= 0) return hipSuccess;
 	MinArgs a = min_args(stream, bend, entry, nb, rb, SK_MINIMIZE_READ_IDS);
 	a.key_mask = key_bits >= 64 ? ~0ull : (1ull << key_bits) - 1ull;
+	a.rule = rule; a.skip_key = id_skip_bit(rule, key_bits);
 	a.krec = (u64 *)krec; a.key = (u64 *)key; a.idx = idx; a.decline = decline;
 	bam_min_key_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
 	return hipGetLastError();
@@ -366,14 +378,15 @@ hipError_t bam_sort_pairs(void *temp, size_t *temp_bytes, uint64_t *key[2], uint
 	return e;
 }
 
-hipError_t launch_bam_min_ids(const uint8_t *stream, const uint64_t *krec, const uint64_t *key, const uint32_t *idx, uint64_t n, uint32_t *agg,
-                              uint32_t *src, uint32_t *cnt, uint32_t *ids, uint32_t *decline, hipStream_t st)
+hipError_t launch_bam_min_ids(const uint8_t *stream, const uint64_t *krec, const uint64_t *key, const uint32_t *idx, uint64_t n, int key_bits,
+                              IdRule rule, uint32_t *agg, uint32_t *src, uint32_t *cnt, uint32_t *ids, uint32_t *decline, hipStream_t st)
 {
 	if (n == 0) return hipSuccess;
 	const u64 nt = (n + kTile - 1) / kTile;
 	min_agg_kernel<true><<<tiles_grid(n), kMinThreads, 0, st>>>((const u64 *)key, nullptr, n, agg);
 	min_tile_scan_kernel<true><<<1, 1024, 0, st>>>(agg, nt);
-	bam_min_run_kernel<<<tiles_grid(n), kMinThreads, 0, st>>>(stream, (const u64 *)krec, (const u64 *)key, idx, n, agg, src, decline);
+	bam_min_run_kernel<<<tiles_grid(n), kMinThreads, 0, st>>>(stream, (const u64 *)krec, (const u64 *)key, idx, n, rule.whole_name != 0,
+	                                                              id_skip_bit(rule, key_bits), agg, src, decline);
 	min_agg_kernel<false><<<tiles_grid(n), kMinThreads, 0, st>>>(nullptr, src, n, agg);
 	min_tile_scan_kernel<false><<<1, 1024, 0, st>>>(agg, nt);
 	bam_min_open_scan_kernel<<<tiles_grid(n), kMinThreads, 0, st>>>(src, n, agg, cnt);

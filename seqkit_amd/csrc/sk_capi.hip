@@ -1905,6 +1905,13 @@ int sk_census_entries(sk_ctx *c, uint64_t min_count, sk_census_entry *out, uint6
 	return SK_OK;
 }
 
+// ---- sam subsample: the draw (include/seqkit_hip.h; host code, no device) ----------------------------------------
+int sk_subsample_keep(uint64_t seed, uint64_t draw, float fraction)
+{
+	if (!(fraction >= 0.0f && fraction <= 1.0f)) return SK_ERR_INVALID;
+	return sk::subsample_keeps(seed, draw, sk::subsample_threshold(fraction)) ? 1 : 0;
+}
+
 // ---- timing ----------------------------------------------------------------------------------------
 int sk_timer_start(sk_ctx *c)
 {

@@ -202,16 +202,21 @@ hipError_t launch_bam_rw_index(const uint8_t *stream, const uint64_t *bend, cons
 hipError_t launch_bam_rw_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, int op,
                                uint8_t *out, int n_cu, hipStream_t st);
 // ---- sam minimize: the read ids and the per-record rewrite of sk_bam_file_minimize (sk_bamminimize.hip) ----
-// keys: every record's stream offset, the hash of its name up to the first '/' (its low key_bits bits) and its index; decline bit 8: an
+// The key rule of the id passes.  whole_name == 0: a record's key is its name up to the first '/' (minimize); else the whole name.
+// skip_flags: a record with one of these flag bits takes no part — it neither opens nor closes an occurrence of its name, and its id is
+// 0; key_bits is then at most 63, the key of such a record is bit key_bits alone, and bam_sort_pairs sorts key_bits + 1 bits.
+struct IdRule { int whole_name; uint32_t skip_flags; };
+inline uint64_t id_skip_bit(IdRule rule, int key_bits) { return rule.skip_flags ? (uint64_t)1 << key_bits : 0; }
+// keys: every record's stream offset, the hash of its key (its low key_bits bits) and its index; decline bit 8: an
 // invalid record.  bam_sort_pairs: (u64 key, u32 index) by the key's low key_bits bits, stable, between the two buffers of each kind (*sorted: the one that holds the result);
 // temp == nullptr: only *temp_bytes.  ids: from the sorted pairs the records' ids (agg: u32[n / 1024 + 1] scratch; src, cnt: u32[n]
 // scratch); decline bit 64: two different keys with one hash.  size / index / write: as launch_bam_rw_*; flags SK_MINIMIZE_*; ids ==
 // nullptr without SK_MINIMIZE_READ_IDS; decline bit 32: a CIGAR operation code above 8.
 hipError_t launch_bam_min_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int key_bits,
-                               uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st);
+                               IdRule rule, uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st);
 hipError_t bam_sort_pairs(void *temp, size_t *temp_bytes, uint64_t *key[2], uint32_t *idx[2], uint64_t n, int key_bits, int *sorted, hipStream_t st);
-hipError_t launch_bam_min_ids(const uint8_t *stream, const uint64_t *krec, const uint64_t *key, const uint32_t *idx, uint64_t n, uint32_t *agg,
-                              uint32_t *src, uint32_t *cnt, uint32_t *ids, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_min_ids(const uint8_t *stream, const uint64_t *krec, const uint64_t *key, const uint32_t *idx, uint64_t n, int key_bits,
+                              IdRule rule, uint32_t *agg, uint32_t *src, uint32_t *cnt, uint32_t *ids, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_min_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int flags,
                                const uint32_t *ids, uint64_t *bo, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_min_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int flags,
@@ -240,6 +245,29 @@ hipError_t launch_bam_md_cluster(const uint8_t *stream, const MdCols &cols, cons
                                  int n_cu, hipStream_t st);
 hipError_t launch_bam_md_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint16_t *nflag, int64_t first, int64_t n,
                                uint64_t o0, uint8_t *out, int n_cu, hipStream_t st);
+// ---- sam subsample: the keep pass, the compaction and the window copy of sk_bam_file_subsample (sk_bamsubsample.hip) ----
+// Rule 3 of the command, the one statement of it (sk_subsample_keep, the keep pass): draw d of seed s is splitmix64's d-th output from
+// state s, its top 24 bits m; keep iff m <= T.
+__host__ __device__ inline bool subsample_keeps(uint64_t seed, uint64_t draw, uint32_t T)
+{
+	uint64_t z = seed + draw * 0x9E3779B97F4A7C15ull;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+	z ^= z >> 31;
+	return (uint32_t)(z >> 40) <= T;
+}
+inline uint32_t subsample_threshold(float fraction) { return (uint32_t)((double)fraction * 16777216.0); }   // floor(fraction 2^24), 0 <= fraction <= 1
+// keep: per record (krec: its stream offset, ids: its fragment number from the id passes under IdRule{1, 0x800}) len[k] = the record's
+// bytes when it is kept, 0 when it is dropped or has 0x800; counts[0 .. 2] += the counted records, the kept ones, the kept ones' bytes;
+// decline bit 1: a counted record without 0x1.  scans (temp == nullptr: only *temp_bytes): pos[k] = the kept records before k, off[k] =
+// their bytes.  compact: the kept records' stream and output offsets, in order.  write: as launch_bam_rw_write, every record byte for byte.
+hipError_t launch_bam_sub_keep(const uint8_t *stream, const uint64_t *krec, const uint32_t *ids, uint64_t n, uint64_t seed, uint32_t T, uint32_t *len,
+                               uint64_t *counts, uint32_t *decline, int n_cu, hipStream_t st);
+hipError_t bam_sub_scans(void *temp, size_t *temp_bytes, const uint32_t *len, uint32_t *pos, uint64_t *off, uint64_t n, hipStream_t st);
+hipError_t launch_bam_sub_compact(const uint64_t *krec, const uint32_t *len, const uint32_t *pos, const uint64_t *off, uint64_t n, uint64_t *kept_rec,
+                                  uint64_t *kept_out, hipStream_t st);
+hipError_t launch_bam_sub_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, uint8_t *out,
+                                int n_cu, hipStream_t st);
 // BGZF members of raw[0 .. raw_len): the cut into blocks of at most 0xff00 bytes (blocks: device sk_deflate_block[n]), and, after the
 // deflate (or at level 0 the CRC alone), the members back to back into out: msz[n + 1] scratch, msz[n] = their total bytes afterwards
 hipError_t launch_bgzf_cut(uint64_t raw_len, void *blocks, int64_t n, hipStream_t st);
@@ -277,7 +305,7 @@ enum KeepSlot {
 	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
 	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
 	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize / _markdup: per-record columns, windows
-	kKeepPassWork = 12,                                 // the record passes' working memory. sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small)
+	kKeepPassWork = 12,                                 // the record passes' working memory. sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_subsample: the same and every record's stream offset, until the kept records are compacted; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small)
 	kKeepSlots = 13
 };
 hipStream_t ctx_stream(sk_ctx *c);

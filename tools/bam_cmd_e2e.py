@@ -9,6 +9,9 @@ reference, with tid = the repeat's index, so it is coordinate-sorted with positi
 about 20 k regions over those references.  usage: bam_cmd_e2e.py [million records (20)] [runs per path (3)] [--lib-only: the library
 calls alone, e.g. under rocprofv3 --kernel-trace --stats] [--no-gz: without the `sam to fastq <prefix>` row] [--markdup: only the
 `sam mark duplicates` rows, see below] [--markdup-file=PATH: only write that row's file to PATH, for a profiler run of the command]
+[--subsample: only the `sam subsample` rows, see below] [--yardstick-sam=PATH: with --subsample, another build's `sam` (the parent
+commit's) whose `trim qnames` is the yardstick row instead of this build's] [--subsample-file=PATH: only write that row's file to
+PATH, for a profiler run of the command]
 
 --markdup: the count file (position-sorted, one reference per repeat) with duplicates: every fourth pair lies at the position and has
 the fragment length of the pair before it, and the pairs of every second group of four carry an RX:Z UMI (a duplicate pair its
@@ -16,6 +19,13 @@ original's).  So half of the records are in groups of two and a quarter are mark
 mark duplicates` to /dev/null, device path against the host reader, and `sam trim qnames` to /dev/null on the same file (no name
 has a space: every record passes unchanged through the same inflate, window, deflate and pack pipeline, without signatures, sort and
 clusters).  With --check both paths also write a file each, and the inflated outputs and the stderr lines are compared.
+
+--subsample: the same file without the duplicates (position-sorted, paired, mates adjacent; a name recurs once per reference).  Rows,
+all to /dev/null: `sam subsample --seed=1 <file> 1.0` and `0.5` on the device path, `0.5` through the host reader, and `sam trim
+qnames` on the device path — at fraction 1.0 the command writes what trim qnames writes (no name has a space), plus the id passes, the
+keep pass and the compaction.  The ratio 1.0 / trim qnames is printed run for run next to the spread (max - min) of the trim qnames
+repeats.  With --check the device path and the host reader also write a file each at 0.5, and the inflated outputs and the stderr
+lines are compared.
 
 The `sam to interleaved fastq` row is also run with stdout to /dev/null (no oracle there: the row before checked the outputs), which
 takes the writer's cost out of both paths."""
@@ -42,6 +52,9 @@ lib_only = "--lib-only" in sys.argv
 no_gz = "--no-gz" in sys.argv
 markdup = "--markdup" in sys.argv
 markdup_check = "--check" in sys.argv
+subsample = "--subsample" in sys.argv
+yardstick_sam = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--yardstick-sam=")), None)
+subsample_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--subsample-file=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 millions = int(argv[0]) if len(argv) > 0 else 20
@@ -260,13 +273,54 @@ def markdup_rows():
     os.rmdir(d)
 
 
-if markdup_file is not None:
+def subsample_rows():
+    t0 = time.perf_counter()
+    write_count_file(bam)
+    print(f"subsample file: {n} BAM records on {reps} references, sorted, paired, mates adjacent, {os.path.getsize(bam) / 1e6:.0f} MB, written in "
+          f"{time.perf_counter() - t0:.1f} s; {runs} runs per row, alternating", flush=True)
+    trim_sam = yardstick_sam or SAM
+    trim_label = "sam trim qnames        device" + (" (yardstick build)" if yardstick_sam else "")
+    rows = {}
+    for k in range(runs):
+        for label, cmd, env in ((trim_label, [trim_sam, "trim", "qnames", bam], None),
+                                ("sam subsample 1.0      device", [SAM, "subsample", "--seed=1", bam, "1.0"], None),
+                                ("sam subsample 0.5      device", [SAM, "subsample", "--seed=1", bam, "0.5"], None),
+                                ("sam subsample 0.5      host  ", [SAM, "subsample", "--seed=1", bam, "0.5"], {"SEQKIT_HOST_INFLATE": "1"})):
+            dt, cpu, rc, _, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+            lines = err.decode(errors="replace").split("\n")
+            served = [ln for ln in lines if ln.startswith("sam ")]
+            assert rc == 0 and served and ("host reader" if env else "device path") in served[0], (label, rc, err[-400:])
+            rows.setdefault(label, []).append((dt, cpu, [ln for ln in lines if ln.startswith("Kept reads")]))
+    for label, r in rows.items():
+        print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r) + ("  " + r[0][2][0] if r[0][2] else ""), flush=True)
+    one = [x[0] for x in rows["sam subsample 1.0      device"]]
+    tq = [x[0] for x in rows[trim_label]]
+    print("subsample 1.0 / trim qnames, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(one, tq))
+          + f"; medians {float(np.median(one)) / float(np.median(tq)):.2f}x; trim qnames max - min {max(tq) - min(tq):.2f} s = "
+          f"{(max(tq) - min(tq)) / float(np.median(tq)):.2f} of its median", flush=True)
+    if markdup_check:
+        got = []
+        for env in (None, {"SEQKIT_HOST_INFLATE": "1"}):
+            dt, cpu, rc, _, err = timed([SAM, "subsample", "--seed=1", bam, "0.5"], env, sink=out)
+            got.append((rc, inflated_digest(out), err))
+        assert got[0] == got[1], got
+        print(f"sam subsample --seed=1 0.5 > file: inflated outputs and stderr identical on both paths ({got[0][1]})", flush=True)
+        os.remove(out)
+    os.remove(bam)
+    os.rmdir(d)
+
+
+if markdup_file is not None or subsample_file is not None:
+    markdup_file = markdup_file or subsample_file
     write_count_file(markdup_file)
     print(f"wrote {markdup_file}: {n} records, {os.path.getsize(markdup_file) / 1e6:.0f} MB", flush=True)
     os.rmdir(d)
     sys.exit(0)
 if markdup:
     markdup_rows()
+    sys.exit(0)
+if subsample:
+    subsample_rows()
     sys.exit(0)
 t0 = time.perf_counter()
 with open(bam, "wb") as f:

@@ -117,5 +117,64 @@ def minimize_cases():
 
 
 minimize_cases()
+
+
+# sam subsample.  The reference's generator is unseeded, so no run of it can be held to particular records; what every run must show is
+# what tests/bam_subsample_model.py shows for any seed: the counts of its stderr lines, an output that is an in-order subset of the
+# counted records (those without 0x800) and closed under the pairing (the 2nd, 4th .. counted record of a name shares the fate of the one
+# before it), fractions 1 and an unparsable one exactly, and the status and partial output at a record without 0x1.  That rand 0.5's
+# random::<f32>() is (u32 >> 8) * 2^-24 compared with <= is unpinned: a share test of one run would not tell it apart.
+def subsample_cases():
+    global failures
+    import re
+    from tests import bam_subsample_model as sm
+
+    def differs(what, detail=""):
+        global failures
+        failures += 1
+        print(f"DIFFERENT: sam subsample: {what} {detail}")
+    d = tempfile.mkdtemp(prefix="sk_pin_sub_")
+    try:
+        raw = sm.write(os.path.join(d, "s.bam"), sm.served_records(4000, seed=9))
+        counted = [r for r in sm.records(raw) if not sm.flag_of(r) & 0x800]
+        for text in ("0.5", "1", ".25", "0"):
+            r = subprocess.run([args.ref_sam, "subsample", "s.bam", text], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+            got = list(sm.records(b"".join(x for x, _ in sm.members(r.stdout)))) if r.stdout else []
+            mt = re.fullmatch(rb"Total reads: (\d+)\nKept reads: (\d+) \(([0-9.]+)% of all reads\)\n", r.stderr)
+            if r.returncode != 0 or not mt or int(mt.group(1)) != len(counted) or int(mt.group(2)) != len(got):
+                differs("counts", f"fraction {text}: rc={r.returncode} stderr={r.stderr[-300:]!r}, {len(got)} records written")
+                continue
+            if mt.group(3) != b"%.1f" % (len(got) / len(counted) * 100.0):
+                differs("percentage", f"fraction {text}: {r.stderr!r}")
+            at, pending, closed = 0, {}, True
+            for rec in counted:
+                kept = at < len(got) and got[at] == rec
+                name = sm.qname(rec)
+                if name in pending:
+                    closed = closed and pending.pop(name) == kept
+                else:
+                    pending[name] = kept
+                at += kept
+            if at != len(got) or not closed:
+                differs("subset in order / mate closure", f"fraction {text}: {at} of {len(got)} written records matched, closed={closed}")
+            if text == "1" and len(got) != len(counted):
+                differs("fraction 1 keeps every counted record", f"{len(got)} of {len(counted)}")
+        recs = list(sm.served_records(200, seed=4))
+        recs[120] = sm.rm.record(b"single", 21, flag=0x10)
+        raw = sm.write(os.path.join(d, "u.bam"), recs)
+        r = subprocess.run([args.ref_sam, "subsample", "u.bam", "1"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        exp_out, exp_err, code, _, _ = sm.model(raw, 0, sm.parse_fraction("1"))
+        got = b"".join(x for x, _ in sm.members(r.stdout)) if r.stdout else b""
+        if r.returncode % 256 != code or r.stderr != exp_err or got != exp_out:
+            differs("a record without 0x1", f"rc={r.returncode} stderr={r.stderr[-300:]!r}")
+        for text in ("abc", "1.5", "nan", " 0.5", "0x1p-1"):
+            r = subprocess.run([args.ref_sam, "subsample", "s.bam", text], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+            if (r.returncode % 256, r.stdout, r.stderr) != (255, b"", sm.FRACTION_ERROR):
+                differs("fraction message", f"{text!r}: rc={r.returncode} stderr={r.stderr[-300:]!r}")
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+subsample_cases()
 print(f"{failures} differences")
 sys.exit(1 if failures else 0)
