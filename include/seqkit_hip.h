@@ -502,6 +502,27 @@ int sk_bam_file_subsample(sk_ctx *ctx, const char *path, float fraction, uint64_
                           uint64_t window_bytes /* 0 = default */, int64_t *n_records, int64_t *n_total, uint64_t *raw_bytes, int *handled,
                           double info[8]);
 
+/* ---- `sam coverage histogram` (src/sam_coverage_histogram.rs; this build's reading of `samtools depth -a`) --------
+ * sk_bam_file_coverage: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0
+ * cases, info[] as there), then the depth histogram of the target positions, from sorted CIGAR events on the device.  A record is
+ * counted iff 0 <= refID < n_ref and flag & 0x704 == 0 (0x800 is counted; mapq and the qualities play no part; overlapping mates
+ * each count).  From pos, its CIGAR's M = X ops (codes 0 7 8) cover [p, p + len) and advance, D N (2 3) advance, every other code
+ * does neither, in 64 bits; what falls outside [0, l_ref) is dropped (l_ref read unsigned).  The order of the records plays no part.
+ * Target positions: mode 0, every position of every reference with a counted record (targets ignored).  Mode 1, the union of the
+ * `targets`, whether or not a record lies there.  Mode 2, the union of the `targets` on the references that have a counted record
+ * whose span [pos, end) overlaps one of them; end = pos plus the lengths of the ops M D N = X, pos + 1 without one.  targets: n_targets
+ * host triples (refID, beg, end), 0-based half-open, in any order, overlapping allowed; a refID outside the header or beg >= end is
+ * ignored, beg < 0 reads as 0, and the interval is cut to [0, l_ref) as a target (not for mode 2's overlap test).
+ * hist[k], k in 0 .. SK_COVERAGE_BINS - 1 = the target positions of depth k (set, not added to); *n_dropped = those deeper, which no
+ * bin counts; *n_positions = the target positions = sum(hist) + *n_dropped; *n_counted = the counted records.  *handled = 0
+ * (info[5] = -(30 + 8)): a record whose variable part is shorter than its fields; info[5] = -21: 2^32 events or more (two per run of
+ * covering ops and per target interval), or the working memory (24 B per event and the sort's scratch, in the device buffer of the
+ * compressed file where they fit: it is idle by then) cannot be had.  A bad mode, n_targets < 0 or hist == NULL: SK_ERR_INVALID.       */
+#define SK_COVERAGE_BINS 10001
+int sk_bam_file_coverage(sk_ctx *ctx, const char *path, int mode /* 0 everywhere, 1 region, 2 BED */, const int64_t *targets, int64_t n_targets,
+                         uint64_t hist[SK_COVERAGE_BINS], uint64_t *n_positions, uint64_t *n_dropped, int64_t *n_counted, int *handled,
+                         double info[8]);
+
 /* ---- F2 on the device: the gzip writers' DEFLATE ------------------------------------------------
  * src/common.rs:49-81: every output file of the reference is a pipe into a gzip / pigz child; what a test can hold it to is
  * the decompressed stream.  sk_bgzf_deflate compresses n independent blocks of at most SK_DEFLATE_MAX_IN bytes (in +

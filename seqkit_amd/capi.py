@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
     "sk_timer_start", "sk_timer_stop",
@@ -87,6 +87,7 @@ class _OutWindow(C.Structure):
 REWRITE_OP = {"trim qnames": 1, "qname from tags": 2, "tags from qname": 3}
 # sk_bam_file_minimize: the flags
 MINIMIZE_READ_IDS, MINIMIZE_BASE_QUALITIES, MINIMIZE_TAGS = 1, 2, 4
+COVERAGE_BINS = 10001                # SK_COVERAGE_BINS
 
 
 class _Mate(C.Structure):
@@ -246,6 +247,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_file_markdup": (i32, [vp, C.c_char_p, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_subsample_keep": (i32, [C.c_uint64, C.c_uint64, C.c_float]),
         "sk_bam_file_subsample": (i32, [vp, C.c_char_p, C.c_float, C.c_uint64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_coverage": (i32, [vp, C.c_char_p, i32, vp, i64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
         "sk_bam_fragments_bed_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(i64)]),
@@ -495,6 +497,17 @@ class Context:
         """sk_bam_file_subsample: (handled, records written, records counted, inflated output bytes, info f64[8]); then
         bam_file_rewrite_windows() yields the windows."""
         return self._bam_out_call("sk_bam_file_subsample", path, (fraction, seed, level, window_bytes), with_duplicates=True)
+
+    def bam_file_coverage(self, path: str, mode: int = 0, targets=()):
+        """sk_bam_file_coverage: (handled, hist u64[COVERAGE_BINS], target positions, positions deeper than the last bin, counted records,
+        info f64[8]).  mode 0 everywhere, 1 region, 2 BED; targets: (refID, beg, end) triples, 0-based half-open."""
+        t = np.ascontiguousarray(np.asarray(list(targets), dtype=np.int64).reshape(-1, 3))
+        hist = np.zeros(COVERAGE_BINS, dtype=np.uint64)
+        n_pos, n_drop, n_counted, handled = C.c_uint64(0), C.c_uint64(0), C.c_int64(0), C.c_int32(0)
+        info = (C.c_double * 8)()
+        self._check(self._lib.sk_bam_file_coverage(self._h, os.fsencode(path), mode, t.ctypes.data if len(t) else None, len(t), hist.ctypes.data,
+                                                   C.byref(n_pos), C.byref(n_drop), C.byref(n_counted), C.byref(handled), info), "sk_bam_file_coverage")
+        return bool(handled.value), hist, int(n_pos.value), int(n_drop.value), int(n_counted.value), [float(x) for x in info]
 
     def bam_file_rewrite_windows(self):
         """sk_bam_file_rewrite_next (after bam_file_rewrite, bam_file_minimize, bam_file_markdup or bam_file_subsample) until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""

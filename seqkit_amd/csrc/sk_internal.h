@@ -268,6 +268,29 @@ hipError_t launch_bam_sub_compact(const uint64_t *krec, const uint32_t *len, con
                                   uint64_t *kept_out, hipStream_t st);
 hipError_t launch_bam_sub_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, uint8_t *out,
                                 int n_cu, hipStream_t st);
+// ---- sam coverage histogram: the record passes of sk_bam_file_coverage (sk_bamcoverage.hip) ----
+// What the two record passes take (all device memory).  base[r] = the global coordinate of reference r's position 0, base[n_ref] the
+// total.  ioff == nullptr: no intervals; else reference r's merged, sorted, disjoint intervals are [ibeg[k], iend[k]) for k in
+// [ioff[r], ioff[r + 1]).  has / hit: a bit per reference (zeroed by the caller), counted and decline: one word each (zeroed).
+constexpr uint32_t kCovDepthUp = 0u, kCovDepthDown = 1u, kCovInsideUp = 2u, kCovInsideDown = 3u;    // an event's kind: what it adds to which running sum
+struct CovArgs {
+	int32_t n_ref;
+	const uint64_t *base;
+	const uint32_t *ioff;
+	const int64_t *ibeg, *iend;
+	uint64_t *bruns;              // [nb + 1]: per block the runs of its records, then (launch_scan_u64) exclusive offsets
+	uint32_t *has, *hit;
+	unsigned long long *counted;
+	uint32_t *decline;            // bit 8: an invalid record
+};
+// mark: bruns (scanned), has, hit, counted, decline.  emit: run q's two events into key / kind[2 q], [2 q + 1].  scan (temp == nullptr:
+// only *temp_bytes): sums[i] = depth + inside * 2^32 behind sorted event i.  hist: hist[SK_COVERAGE_BINS] and totals[0 .. 1] = the
+// positions inside the targets and those deeper than the last bin (both zeroed here).
+hipError_t launch_bam_cov_mark(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const CovArgs &a, hipStream_t st);
+hipError_t launch_bam_cov_emit(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const CovArgs &a, uint64_t *key,
+                               uint32_t *kind, hipStream_t st);
+hipError_t bam_cov_scan(void *temp, size_t *temp_bytes, const uint32_t *kind, int64_t *sums, uint64_t n, hipStream_t st);
+hipError_t launch_bam_cov_hist(const uint64_t *key, const int64_t *sums, uint64_t n, uint64_t *hist, uint64_t *totals, int n_cu, hipStream_t st);
 // BGZF members of raw[0 .. raw_len): the cut into blocks of at most 0xff00 bytes (blocks: device sk_deflate_block[n]), and, after the
 // deflate (or at level 0 the CRC alone), the members back to back into out: msz[n + 1] scratch, msz[n] = their total bytes afterwards
 hipError_t launch_bgzf_cut(uint64_t raw_len, void *blocks, int64_t n, hipStream_t st);
@@ -305,7 +328,7 @@ enum KeepSlot {
 	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
 	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
 	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize / _markdup: per-record columns, windows
-	kKeepPassWork = 12,                                 // the record passes' working memory. sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_subsample: the same and every record's stream offset, until the kept records are compacted; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small)
+	kKeepPassWork = 12,                                 // the record passes' working memory. sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_subsample: the same and every record's stream offset, until the kept records are compacted; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small); sk_bam_file_coverage: the events, where that buffer is too small
 	kKeepSlots = 13
 };
 hipStream_t ctx_stream(sk_ctx *c);

@@ -8,7 +8,8 @@ The fragments file is tools/bam_e2e.py's (100 k paired records, one in two kept,
 reference, with tid = the repeat's index, so it is coordinate-sorted with positions restarting per reference; the BED file holds
 about 20 k regions over those references.  usage: bam_cmd_e2e.py [million records (20)] [runs per path (3)] [--lib-only: the library
 calls alone, e.g. under rocprofv3 --kernel-trace --stats] [--no-gz: without the `sam to fastq <prefix>` row] [--markdup: only the
-`sam mark duplicates` rows, see below] [--markdup-file=PATH: only write that row's file to PATH, for a profiler run of the command]
+`sam mark duplicates` rows, see below] [--markdup-file=PATH: only write that row's file to PATH, for a profiler run of the command] [--coverage: only the `sam coverage histogram` rows, see below] [--coverage-file=PATH: only
+write that row's file to PATH; with --human the one under the human-sized header]
 [--subsample: only the `sam subsample` rows, see below] [--yardstick-sam=PATH: with --subsample, another build's `sam` (the parent
 commit's) whose `trim qnames` is the yardstick row instead of this build's] [--subsample-file=PATH: only write that row's file to
 PATH, for a profiler run of the command]
@@ -26,6 +27,13 @@ qnames` on the device path — at fraction 1.0 the command writes what trim qnam
 keep pass and the compaction.  The ratio 1.0 / trim qnames is printed run for run next to the spread (max - min) of the trim qnames
 repeats.  With --check the device path and the host reader also write a file each at 0.5, and the inflated outputs and the stderr
 lines are compared.
+
+--coverage: the subsample file (200 references of 2^28 positions: 53.7 G positions, of which the records cover 50 k per reference) and
+the same records under a human-sized header: 25 references of 124 M positions, 3.1 G in all, record k's reference its repeat's index
+mod 25 (no longer sorted: the command does not ask for order).  Rows per file, all to /dev/null: `sam statistics` on the device path
+(--yardstick-sam: another build's, the parent commit's) — the same front half plus a reduction —, `sam coverage histogram` on the
+device path and through the host reader.  The ratio coverage / statistics is printed run for run next to the spread of the statistics
+repeats.  With --check the stdout of both paths is compared.
 
 The `sam to interleaved fastq` row is also run with stdout to /dev/null (no oracle there: the row before checked the outputs), which
 takes the writer's cost out of both paths."""
@@ -54,6 +62,9 @@ markdup = "--markdup" in sys.argv
 markdup_check = "--check" in sys.argv
 subsample = "--subsample" in sys.argv
 yardstick_sam = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--yardstick-sam=")), None)
+coverage = "--coverage" in sys.argv
+human = "--human" in sys.argv
+coverage_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--coverage-file=")), None)
 subsample_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--subsample-file=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -112,12 +123,12 @@ def blocks_of(u):
     return b"".join(out_)
 
 
-def header(n_ref):
+def header(n_ref, l_ref=1 << 28):
     text = b"@HD\tVN:1.6\tSO:coordinate\n"
     h = b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", n_ref)
     for r in range(n_ref):
         nm = b"chr%d\0" % (r + 1)
-        h += struct.pack("<i", len(nm)) + nm + struct.pack("<i", 1 << 28)
+        h += struct.pack("<i", len(nm)) + nm + struct.pack("<i", l_ref)
     return bgzf(h)
 
 
@@ -221,11 +232,12 @@ def compare(label, args):
 n = reps * 2 * PAIRS
 
 
-def write_count_file(path):
+def write_count_file(path, n_ref=None, l_ref=1 << 28):
+    """n_ref: the header's references, repeat r's records on reference r mod n_ref (None: one reference per repeat)"""
     with open(path, "wb") as f:
-        f.write(header(reps))
+        f.write(header(n_ref or reps, l_ref))
         with ThreadPoolExecutor(16) as ex:
-            for blob in ex.map(with_tid, range(reps)):
+            for blob in ex.map(with_tid, [r % (n_ref or reps) for r in range(reps)]):
                 f.write(blob)
         f.write(bgzf(b""))
 
@@ -310,6 +322,59 @@ def subsample_rows():
     os.rmdir(d)
 
 
+HUMAN_REFS, HUMAN_LEN = 25, 124_000_000
+
+
+def coverage_rows():
+    stat_sam = yardstick_sam or SAM
+    stat_label = "sam statistics          device" + (" (yardstick build)" if yardstick_sam else "")
+    for what, n_ref, l_ref in ((f"{reps} references of 2^28 positions, sorted", None, 1 << 28),
+                               (f"{HUMAN_REFS} references of {HUMAN_LEN} positions ({HUMAN_REFS * HUMAN_LEN / 1e9:.1f} G), repeat r on reference r mod {HUMAN_REFS}", HUMAN_REFS, HUMAN_LEN)):
+        t0 = time.perf_counter()
+        write_count_file(bam, n_ref, l_ref)
+        print(f"coverage file: {n} BAM records on {what}, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; "
+              f"{runs} runs per row, alternating", flush=True)
+        rows = {}
+        for k in range(runs):
+            for label, cmd, env in ((stat_label, [stat_sam, "statistics", bam], None),
+                                    ("sam coverage histogram  device", [SAM, "coverage", "histogram", bam], None),
+                                    ("sam coverage histogram  host  ", [SAM, "coverage", "histogram", bam], {"SEQKIT_HOST_INFLATE": "1"})):
+                dt, cpu, rc, _, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+                lines = err.decode(errors="replace").split("\n")
+                served = [ln for ln in lines if ln.startswith("sam ")]
+                assert rc == 0 and served and (("host reader" if env else "device path") in served[-1] or "sk_bam_file_reduce" in served[-1]), (label, rc, err[-400:])
+                rows.setdefault(label, []).append((dt, cpu, [ln for ln in lines if ln.startswith("sk_bam_file_coverage:")]))
+        for label, r in rows.items():
+            print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r), flush=True)
+        for ln in rows["sam coverage histogram  device"][-1][2]:
+            print("  " + ln, flush=True)
+        cov = [x[0] for x in rows["sam coverage histogram  device"]]
+        st = [x[0] for x in rows[stat_label]]
+        host = [x[0] for x in rows["sam coverage histogram  host  "]]
+        print("coverage histogram / statistics, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(cov, st))
+              + f"; medians {float(np.median(cov)) / float(np.median(st)):.2f}x; statistics max - min {max(st) - min(st):.2f} s = "
+              f"{(max(st) - min(st)) / float(np.median(st)):.2f} of its median; device / host reader (medians) = {float(np.median(cov)) / float(np.median(host)):.2f}", flush=True)
+        if markdup_check:
+            got = []
+            for env in (None, {"SEQKIT_HOST_INFLATE": "1"}):
+                dt, cpu, rc, h, err = timed([SAM, "coverage", "histogram", bam], env)
+                got.append((rc, h, err))
+            assert got[0] == got[1], got
+            print(f"sam coverage histogram > file: stdout identical on both paths ({got[0][1]}); first lines: "
+                  + " ".join(open(out).read().split("\n")[:3]).replace("\t", ":"), flush=True)
+            os.remove(out)
+        os.remove(bam)
+    os.rmdir(d)
+
+
+if coverage_file is not None:
+    write_count_file(coverage_file, HUMAN_REFS if human else None, HUMAN_LEN if human else 1 << 28)
+    print(f"wrote {coverage_file}: {n} records, {os.path.getsize(coverage_file) / 1e6:.0f} MB", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if coverage:
+    coverage_rows()
+    sys.exit(0)
 if markdup_file is not None or subsample_file is not None:
     markdup_file = markdup_file or subsample_file
     write_count_file(markdup_file)
