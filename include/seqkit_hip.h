@@ -421,7 +421,7 @@ int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
  * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
  * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
  * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
- * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup or sk_bam_file_subsample, below, whose windows it hands out too):
+ * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample or sk_bam_file_merge, below, whose windows it hands out too):
  * SK_ERR_INVALID.                                                                                                                 */
 #define SK_REWRITE_TRIM_QNAMES     1
 #define SK_REWRITE_QNAME_FROM_TAGS 2
@@ -501,6 +501,26 @@ int sk_subsample_keep(uint64_t seed, uint64_t draw, float fraction);
 int sk_bam_file_subsample(sk_ctx *ctx, const char *path, float fraction, uint64_t seed, int level /* 0 stored, 1 deflate */,
                           uint64_t window_bytes /* 0 = default */, int64_t *n_records, int64_t *n_total, uint64_t *raw_bytes, int *handled,
                           double info[8]);
+
+/* ---- BAM out for `sam merge` (src/sam_merge.rs:58-103) -----------------------------------------------------------------------
+ * sk_bam_file_merge: sk_bam_file_rewrite's front half for each of n_paths files (2 .. 99), its window pipeline and header (input 1's).
+ * A record's key is (uint32) refID, then pos as a signed 32-bit value: refID -1 sorts last, pos -1 before 0.  The output is what this
+ * loop writes: among the inputs' current first records take the smallest key, among equal keys the lowest input; write it; advance that
+ * input.  For inputs each sorted by the key that is the stable merge, and the reference's output byte for byte whenever no two records of
+ * different inputs share a key (there its heap decides, here the command line's order).  suffix != 0: '.' and the decimal 1-based input
+ * number are appended to every record's name, l_read_name and block_size grow by those 2 or 3 bytes, every other byte as it was;
+ * suffix == 0: every record byte for byte.  The inputs' streams stay on the device together until the last window is written: input 1's
+ * with ctx, each further one's with a helper context that ctx keeps and sk_destroy frees.  *n_records: the records of all inputs;
+ * *raw_bytes: the whole output BAM, inflated.  The windows come from sk_bam_file_rewrite_next under its rules.  *handled = 0 leaves the
+ * files to the caller's reader, nothing written: info[5] = -(30 + bits) with bit 1 a suffixed name of more than 254 bytes (the reference
+ * panics there), 2 an input with a key below its predecessor's, 4 an input whose reference names differ from input 1's (lengths are not
+ * compared), 8 a record whose variable part is shorter than its fields; info[5] = -21: more than 99 inputs, 2^32 records or more, or the
+ * working memory cannot be had (17 B per record for the offsets and input numbers; 29 B per record and the sort's scratch for the passes
+ * where those do not fit into the device buffer of input 1's compressed file, which is idle by then); any other negative info[5]: the
+ * check at which the front half left one of the files.  n_paths < 2, a NULL path or a bad level: SK_ERR_INVALID.  level, window_bytes:
+ * as sk_bam_file_rewrite.                                                                                                         */
+int sk_bam_file_merge(sk_ctx *ctx, const char *const *paths, int n_paths, int suffix, int level /* 0 stored, 1 deflate */,
+                      uint64_t window_bytes /* 0 = default */, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
 
 /* ---- `sam coverage histogram` (src/sam_coverage_histogram.rs; this build's reading of `samtools depth -a`) --------
  * sk_bam_file_coverage: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0

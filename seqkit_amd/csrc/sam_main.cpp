@@ -15,7 +15,7 @@
 // and `sam count` then run their order checks and their text on the device too, and whatever is irregular falls back to the reader
 // here before anything has been written.  `sam to` takes the file the same way: the device writes every record's text, window by
 // window, and the mate pairing stays here.  The commands that write BAM to stdout (trim qnames, tags from qname, qname from tags, minimize,
-// mark duplicates, subsample) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
+// mark duplicates, subsample, merge) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
 // device does not take the reader and writer of HostBamRewrite around the command's own per-record loop.  `sam coverage histogram` goes
 // through the same gate with sk_bam_file_coverage and prints 10 001 lines; its host reader states the rule in one sort and one sweep.
 #include <unistd.h>
@@ -1207,7 +1207,7 @@ static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
 }
 
 // The device path of a BAM-writing command: `start` makes the file call that sets the windows up (sk_bam_file_rewrite, _minimize,
-// _markdup or _subsample), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
+// _markdup, _subsample or _merge), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
 // the file path does not take, a device without room, or a record the reference would stop at).  Otherwise the number of records.
 template <class Start>
 static int64_t bam_out_from_file(Start start)
@@ -1678,6 +1678,94 @@ static int subsample_cmd(int argc, char **argv)
 	return 0;
 }
 
+// ---- sam merge -----------------------------------------------------------------------------------------------------------
+// src/sam_merge.rs: the inputs' records by (u32 refID, i32 pos), each input's own order kept.  The reference's heap leaves the order of
+// records of DIFFERENT inputs with one key to its internals; here they go by the input's place on the command line, so
+// that the command is a stable merge and the device, which sorts all records at once (sk_bam_file_merge), and the loop below write the
+// same bytes.  Regular files go to the device whole; a "-" among the inputs, SEQKIT_HOST_INFLATE=1 and every call the device declines —
+// reference names that differ, an unsorted input, an invalid record, a suffixed name above 254 bytes, more than 99 inputs — are read
+// record by record below.
+static const char *USAGE_MERGE =
+	"\nUsage:\n  sam merge [options] <bam_files>...\n\nOptions:\n"
+	"  --suffix          Add a suffix to read identifiers to avoid clashes\n"
+	"  --uncompressed    Output in uncompressed BAM format\n\n"
+	"Merges two or more position-sorted BAM files together, ensuring that the\nresulting output BAM file is also position-sorted.\n";
+
+struct MergeInput {
+	std::unique_ptr<BamStream> bam;
+	BamCore c;
+	BamStream::Var v;
+	uint8_t head[36];
+	std::vector<uint8_t> body;
+	bool have = false;
+	void advance()                                                            // (a reader's error ends the command where the reference's next() would)
+	{
+		have = bam->next_full(c, v, body);
+		if (have) memcpy(head, bam->head, 36);
+		else bam->raise_deferred();
+	}
+};
+
+static int merge_cmd(int argc, char **argv)
+{
+	std::vector<host::Opt> opts = {{"--suffix", false, false, ""}, {"--uncompressed", false, false, ""}};
+	std::vector<std::string> pos;
+	if (!host::parse_args(argc, argv, 2, opts, pos, (size_t)-1) || pos.empty()) error("Invalid arguments.\n%s", USAGE_MERGE);
+	if (pos.size() < 2) error("At least two BAM files must be provided for concatenation.");      // :62-64
+	const bool suffix = opts[0].present;
+	const int level = opts[1].present ? 0 : 1;
+	std::vector<std::string> paths;
+	bool any_stdin = false;
+	for (const std::string &p : pos) { paths.push_back(expand_home(p)); any_stdin = any_stdin || paths.back() == "-"; }
+	host::gpu_warmup();
+	if (device_path("sam merge", any_stdin ? std::string("-") : paths[0], [&] { return bam_out_from_file([&](sk_ctx *ctx, uint64_t window, int64_t *n, uint64_t *raw, int *handled) {
+		    std::vector<const char *> cp;
+		    for (const std::string &p : paths) cp.push_back(p.c_str());
+		    return sk_bam_file_merge(ctx, cp.data(), (int)cp.size(), suffix ? 1 : 0, level, window, n, raw, handled, nullptr); }); }) >= 0) return 0;
+	std::vector<MergeInput> in(paths.size());
+	for (size_t b = 0; b < paths.size(); b++) in[b].bam.reset(new BamStream(paths[b], b == 0));      // :68
+	for (size_t b = 1; b < paths.size(); b++)                                                       // :71-76
+		if (in[b].bam->names != in[0].bam->names) error("Input BAM files %s and %s have different SQ fields.", pos[0].c_str(), pos[b].c_str());
+	BamOut out(level);
+	g_bam_out = &out;
+	host::at_exit_flush(finish_bam_out);
+	{
+		const std::vector<uint8_t> hdr = bamfmt::rewrite_header(in[0].bam->header_raw);
+		out.put(hdr.data(), hdr.size());
+		out.flush();
+	}
+	for (MergeInput &m : in) m.advance();                                                           // :83-87
+	uint8_t head[36];
+	std::vector<uint8_t> body, rec;
+	const std::vector<uint8_t> none;
+	std::string name;
+	for (;;) {
+		MergeInput *first = nullptr;                                          // the smallest key; among equal keys the lowest input
+		for (MergeInput &m : in) {
+			if (!m.have) continue;
+			if (!first || (uint32_t)m.c.tid < (uint32_t)first->c.tid || (m.c.tid == first->c.tid && m.c.pos < first->c.pos)) first = &m;
+		}
+		if (!first) break;
+		const uint32_t l_read_name = first->v.l_read_name;
+		memcpy(head, first->head, 36);
+		body.swap(first->body);
+		first->advance();                                                     // :91-93 (before the record is written)
+		if (suffix) {                                                         // :94-99
+			name.assign(reinterpret_cast<const char *>(body.data()), l_read_name - 1);
+			name += "." + std::to_string((size_t)(first - in.data()) + 1);
+			if (name.size() > 254) panic("assertion failed: new_qname.len() < 255");
+			renamed_record(rec, head, name, body.data() + l_read_name, body.size() - l_read_name, none);
+			out.put(rec.data(), rec.size());
+		} else {
+			out.put(head, 36);
+			out.put(body.data(), body.size());
+		}
+	}
+	out.finish();
+	g_bam_out = nullptr;
+	return 0;
+}
+
 // ---- sam coverage histogram (src/sam_coverage_histogram.rs) ----------------------------------------------------
 // The reference starts `samtools depth -a`, parses its one line per position back and counts the positions of every depth up to
 // 10 000.  No samtools is started here: the rule of include/seqkit_hip.h (sk_bam_file_coverage) is this build's reading of it.  The
@@ -1984,6 +2072,7 @@ int main(int argc, char **argv)
 	else if (argc >= 2 && is(1, "minimize")) rc = minimize_cmd(argc, argv);
 	else if (argc >= 3 && is(1, "mark") && is(2, "duplicates")) rc = mark_duplicates_cmd(argc, argv);
 	else if (argc >= 2 && is(1, "subsample")) rc = subsample_cmd(argc, argv);
+	else if (argc >= 2 && is(1, "merge")) rc = merge_cmd(argc, argv);
 	else if (argc >= 3 && is(1, "coverage") && is(2, "histogram")) rc = coverage_histogram_cmd(argc, argv);
 	else fprintf(stderr, "%s\n", USAGE_TOP);
 	host::out().flush();

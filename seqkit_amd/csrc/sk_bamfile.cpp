@@ -24,7 +24,9 @@
 #include <cstdlib>
 #include <condition_variable>
 #include <cstring>
+#include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -216,11 +218,12 @@ struct ReadsState : WindowedState {
 
 // Which of the rewrite-window calls is running — the kernel that writes a window's records — and what that kernel takes
 struct WriteOp {
-	enum Kind { kRewrite, kMinimize, kMarkdup, kSubsample } kind = kRewrite;
+	enum Kind { kRewrite, kMinimize, kMarkdup, kSubsample, kMerge } kind = kRewrite;
 	int flags = 0;                               // kRewrite: SK_REWRITE_*; kMinimize: SK_MINIMIZE_*
 	uint8_t fill = 255;                          // kMinimize: the qualities' fill byte
 	const uint32_t *ids = nullptr;               // kMinimize: the read ids (ctx slot kKeepPassWork; nullptr without SK_MINIMIZE_READ_IDS)
 	const uint16_t *md_flags = nullptr;          // kMarkdup: every record's flag (ctx slot kKeepPassWork)
+	const uint8_t *merge_in = nullptr;           // kMerge: every output record's input number (ctx slot kKeepPassWork); nullptr without --suffix
 };
 
 // sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_markdup / sk_bam_file_subsample and sk_bam_file_rewrite_next: every written record's stream and output offsets
@@ -250,7 +253,14 @@ struct Ranges {
 	uint64_t gen = 0;                            // file calls so far: a reads state of an earlier call is stale
 	ReadsState reads;                            // (only one of the two is live: the next file call, windowed or not, ends either)
 	RewriteState rw;
-	static void destroy(void *p) { Ranges *r = (Ranges *)p; r->comp.release(); r->out.release(); delete r; }
+	std::vector<sk_ctx *> helpers;               // sk_bam_file_merge: one context per further input, whose front half keeps that input's stream
+	static void destroy(void *p)
+	{
+		Ranges *r = (Ranges *)p;
+		for (sk_ctx *h : r->helpers) sk_destroy(h);
+		r->comp.release(); r->out.release();
+		delete r;
+	}
 };
 
 // The readers: threads that pread the file's chunks, in order, into a ring of page-locked buffers — chunk k into slot k mod R, once the
@@ -1008,6 +1018,10 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		case WriteOp::kMinimize: e = sk::launch_bam_min_write(s.d_out, s.krec, s.kout, op.ids, first, n, s.wo[w], op.flags, op.fill, s.d_raw, sk::ctx_n_cu(c), st); break;
 		case WriteOp::kMarkdup: e = sk::launch_bam_md_write(s.d_out, s.krec, s.kout, op.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
 		case WriteOp::kSubsample: e = sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kMerge:                                               // (krec: offsets from input 1's stream that reach every input's; without a suffix a record is one copied span)
+			e = op.merge_in ? sk::launch_bam_merge_write(s.d_out, s.krec, s.kout, op.merge_in, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st)
+			                : sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st);
+			break;
 		}
 	}
 	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
@@ -1362,6 +1376,140 @@ extern "C" int sk_bam_file_subsample(sk_ctx *c, const char *path, float fraction
 	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kSubsample}, level, window_bytes, counts[1], counts[2], n_records, raw_bytes, handled, info);
 	if (rc == SK_OK && *handled && n_total) *n_total = (int64_t)counts[0];
 	return rc;
+}
+
+// ---- sam merge (include/seqkit_hip.h: sk_bam_file_merge; the windows come from sk_bam_file_rewrite_next) ---
+// K verified streams at once.  The front half serves one file per ctx and keeps its ranges with it, so every input but the first gets a
+// helper context of its own on the same device (kept with the caller's ctx in Ranges::helpers, freed with it, invisible in the C-ABI)
+// and the unchanged front half runs in each, one after the other: input 1 in the caller's ctx first — that ends an earlier call's windows
+// in flight, which may read the helpers' streams — then the others.  When a front returns its stream is verified, which takes the
+// host's word: nothing of it is still running, and every record pass and every window of this call runs on the caller's streams.  All
+// streams lie in one address space, so a record is addressed by its offset from input 1's stream mod 2^64 and the window writers keep
+// their one base pointer.  The reference names are compared on the host as each front returns.  Then the passes of sk_bammerge.hip:
+// keys per input, the order check, the shared sort over all records, the gather and the scan.  Their working memory (29 B per record and
+// the scratch of the sort and the scan) lies in input 1's compressed file's device buffer, idle by then, where that is large enough,
+// else in ctx slot kKeepPassWork, which always holds the one byte per output record that the windows read with a suffix.  Declined
+// files: the list in include/seqkit_hip.h.
+static std::vector<std::string> front_ref_names(const std::vector<uint8_t> &h)     // (the header is checked by the front: it parses)
+{
+	std::vector<std::string> names;
+	uint64_t o = 8 + (uint64_t)le32(h.data() + 4);
+	const uint32_t n_ref = le32(h.data() + o);
+	o += 4;
+	for (uint32_t r = 0; r < n_ref; r++) {
+		const uint32_t l_name = le32(h.data() + o);
+		std::string name((const char *)h.data() + o + 4, l_name);
+		if (!name.empty() && name.back() == '\0') name.pop_back();          // (as the host reader keeps them)
+		names.push_back(name);
+		o += 4 + (uint64_t)l_name + 4;
+	}
+	return names;
+}
+
+extern "C" int sk_bam_file_merge(sk_ctx *c, const char *const *paths, int n_paths, int suffix, int level, uint64_t window_bytes, int64_t *n_records,
+                                 uint64_t *raw_bytes, int *handled, double info[8])
+{
+	if (!c || !paths || !handled) return SK_ERR_INVALID;
+	*handled = 0;
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (n_records) *n_records = 0;
+	if (raw_bytes) *raw_bytes = 0;
+	if (n_paths < 2) return sk::ctx_fail(c, SK_ERR_INVALID, "n_paths = %d", n_paths);
+	for (int i = 0; i < n_paths; i++) if (!paths[i]) return sk::ctx_fail(c, SK_ERR_INVALID, "paths[%d] is NULL", i);
+	if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+	if (int r = sk::ctx_bind(c)) return r;
+	if (n_paths > 99) BF_LEAVE(21);                                     // (the suffix writer knows one and two digits)
+	const size_t K = (size_t)n_paths;
+	// (the helpers' Cleanups are declared first and so run last: the caller's streams are waited for before a helper's tables are freed)
+	std::unique_ptr<Cleanup[]> cls(new Cleanup[K]);
+	Cleanup cl;
+	std::vector<Front> fin(K);
+	std::vector<std::string> names0;
+	int dev = 0;
+	BF_HIP(hipGetDevice(&dev));
+	for (size_t i = 0; i < K; i++) {
+		fin[i].who = "sk_bam_file_merge";
+		if (i == 0) {
+			if (int r = bam_file_front(c, paths[0], cls[0], fin[0], info)) return r;
+		} else {
+			Ranges *both = (Ranges *)sk::ctx_ext(c);
+			while (both->helpers.size() < i) {
+				sk_ctx *h = nullptr;
+				if (sk_create(dev, &h) != SK_OK || !h) BF_LEAVE(21);
+				both->helpers.push_back(h);
+			}
+			sk_ctx *h = both->helpers[i - 1];
+			if (int r = bam_file_front(h, paths[i], cls[i], fin[i], info)) return sk::ctx_fail(c, r, "input %zu: %s", i + 1, sk_last_error(h));
+		}
+		if (!fin[i].ready) return SK_OK;                                  // (info[5] says at which check)
+		if (i == 0) names0 = front_ref_names(fin[0].header);
+		else if (front_ref_names(fin[i].header) != names0) {
+			if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_merge: declined (bits 0x4): input %zu's reference names differ\n", i + 1);
+			BF_LEAVE(30 + 4);
+		}
+	}
+	// ---- one front over all inputs for the spine: the blocks and records of all of them in a row, input 1's header and stream
+	cl.wait_for = {sk::ctx_stream(c), sk::ctx_stream2(c)};
+	Front all = fin[0];
+	for (size_t i = 1; i < K; i++) {
+		all.nb += fin[i].nb; all.n_records += fin[i].n_records; all.fsize += fin[i].fsize; all.stream_len += fin[i].stream_len; all.n_host += fin[i].n_host;
+		all.rounds = std::max(all.rounds, fin[i].rounds);
+		all.nrec.insert(all.nrec.end(), fin[i].nrec.begin(), fin[i].nrec.end());
+	}
+	all.t_walk = now_ms();
+	const Front &fr = all;
+	const uint64_t N = all.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, all, 0, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const uint8_t *kin = nullptr;
+	uint64_t total = 0;
+	if (N) {
+		uint64_t *key[2] = {nullptr, nullptr};
+		uint32_t *idx[2] = {nullptr, nullptr};
+		size_t sort_bytes = 0, scan_bytes = 0;
+		BF_HIP(sk::bam_sort_pairs(nullptr, &sort_bytes, key, idx, N, 64, nullptr, st));
+		BF_HIP(sk::bam_merge_scan(nullptr, &scan_bytes, nullptr, N, st));
+		const size_t a_key = up(N * 8), a_idx = up(N * 4), a_in = up(N), temp_bytes = std::max(sort_bytes, scan_bytes);
+		const size_t work = 3 * a_key + 3 * a_idx + a_in + up(temp_bytes);
+		const bool in_comp = fin[0].fsize + 64 >= work;
+		int krc = SK_OK;
+		uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepPassWork, a_in + (in_comp ? 0 : work), false, &krc);
+		if (!kb) BF_LEAVE(21);
+		uint8_t *mb = in_comp ? fin[0].d_comp : kb + a_in;
+		if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_merge: %zu inputs, %zu bytes of scratch in %s\n", K, work, in_comp ? "the first compressed file's buffer" : "its own buffer");
+		key[0] = (uint64_t *)mb; key[1] = (uint64_t *)(mb + a_key);
+		idx[0] = (uint32_t *)(mb + 3 * a_key); idx[1] = (uint32_t *)(mb + 3 * a_key + a_idx);
+		sk::MergeCols cols;
+		cols.key = key[0]; cols.addr = (uint64_t *)(mb + 2 * a_key); cols.idx = idx[0];
+		cols.len = (uint32_t *)(mb + 3 * a_key + 2 * a_idx); cols.in = mb + 3 * a_key + 3 * a_idx;
+		void *temp = mb + 3 * a_key + 3 * a_idx + a_in;
+		// ---- keys and checks, input by input: the call is served or left here
+		int64_t b0 = 0;
+		for (size_t i = 0; i < K; i++) {
+			const uint32_t sl = suffix ? (i + 1 >= 10 ? 3u : 2u) : 0u;
+			BF_HIP(sk::launch_bam_merge_keys(fin[i].d_out, fin[i].d_bend, fin[i].d_entry, fin[i].nb, o.d_rb + b0, (uint64_t)(uintptr_t)fin[i].d_out - (uint64_t)(uintptr_t)fin[0].d_out,
+			                                 (uint32_t)(i + 1), sl, cols, o.d_decline, st));
+			b0 += fin[i].nb;
+		}
+		BF_HIP(sk::launch_bam_merge_order(cols, N, o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 a suffixed name above 254 bytes, 2 an unsorted input, 8 an invalid record)
+		// ---- the order: a stable sort of all records by the key, then every output record's address, offset and input number
+		int cur = 0;
+		size_t tb = temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(temp, &tb, key, idx, N, 64, &cur, st));
+		BF_HIP(sk::launch_bam_merge_gather(idx[cur], cols, N, o.s->krec, o.s->kout, kb, st));
+		tb = temp_bytes;
+		BF_HIP(sk::bam_merge_scan(temp, &tb, o.s->kout, N, st));
+		BF_HIP(hipMemcpyAsync(&total, o.s->kout + N, 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+		if (suffix) kin = kb;
+	}
+	WriteOp op;
+	op.kind = WriteOp::kMerge; op.merge_in = kin;
+	return rw_begin(c, cl, all, o, op, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam coverage histogram (include/seqkit_hip.h: sk_bam_file_coverage) ---

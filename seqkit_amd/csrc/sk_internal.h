@@ -268,6 +268,26 @@ hipError_t launch_bam_sub_compact(const uint64_t *krec, const uint32_t *len, con
                                   uint64_t *kept_out, hipStream_t st);
 hipError_t launch_bam_sub_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, uint8_t *out,
                                 int n_cu, hipStream_t st);
+// ---- sam merge: the record passes of sk_bam_file_merge (sk_bammerge.hip) ----
+// The per-record columns in input order (input 1's records first, then input 2's ..): the record's address as an offset from input 1's
+// stream mod 2^64, its key (u32 refID) << 32 | (u32 pos ^ 0x80000000), its index, its output bytes and its input number (1-based).
+struct MergeCols {
+	uint64_t *addr, *key;
+	uint32_t *idx, *len;
+	uint8_t *in;
+};
+// keys: one input's blocks (rb: their first records' GLOBAL indices; delta: this stream's address less input 1's; suffix_len: 0 without
+// --suffix, else the bytes of ".N") into the columns; decline bits 8 (an invalid record) and 1 (a suffixed name above 254 bytes).
+// order: decline bit 2 where a key is below its predecessor's in the same input.  gather: output place p takes record idx[p]'s address,
+// length (into kout) and input number; scan (temp == nullptr: only *temp_bytes): kout[0 .. n) -> exclusive offsets, kout[n] the sum.  write: as launch_bam_sub_write, ".N" behind every record's name; without a
+// suffix launch_bam_sub_write itself writes the windows.
+hipError_t launch_bam_merge_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, uint64_t delta,
+                                 uint32_t input, uint32_t suffix_len, const MergeCols &cols, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_merge_order(const MergeCols &cols, uint64_t n, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_merge_gather(const uint32_t *idx, const MergeCols &cols, uint64_t n, uint64_t *krec, uint64_t *kout, uint8_t *kin, hipStream_t st);
+hipError_t bam_merge_scan(void *temp, size_t *temp_bytes, uint64_t *kout, uint64_t n, hipStream_t st);
+hipError_t launch_bam_merge_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint8_t *kin, int64_t first, int64_t n, uint64_t o0,
+                                  uint8_t *out, int n_cu, hipStream_t st);
 // ---- sam coverage histogram: the record passes of sk_bam_file_coverage (sk_bamcoverage.hip) ----
 // What the two record passes take (all device memory).  base[r] = the global coordinate of reference r's position 0, base[n_ref] the
 // total.  ioff == nullptr: no intervals; else reference r's merged, sorted, disjoint intervals are [ibeg[k], iend[k]) for k in

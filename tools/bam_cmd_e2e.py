@@ -12,7 +12,15 @@ calls alone, e.g. under rocprofv3 --kernel-trace --stats] [--no-gz: without the 
 write that row's file to PATH; with --human the one under the human-sized header]
 [--subsample: only the `sam subsample` rows, see below] [--yardstick-sam=PATH: with --subsample, another build's `sam` (the parent
 commit's) whose `trim qnames` is the yardstick row instead of this build's] [--subsample-file=PATH: only write that row's file to
-PATH, for a profiler run of the command]
+PATH, for a profiler run of the command] [--merge: only the `sam merge` rows, see below] [--merge-files=DIR: only write the undealt file
+and the parts to DIR (in.bam, p2_0.bam .., p8_0.bam ..), for a profiler run of the command]
+
+--merge: the subsample file, and its records dealt alternately (record j of a repeat to part j mod P) into P = 2 and P = 8 position-
+sorted parts.  Mates share a position, so every key occurs in two parts: with ties by input the merge writes the undealt file's records
+in their order.  Rows, all to /dev/null: `sam trim qnames` on the undealt file on the device path (--yardstick-sam: another build's, the
+parent commit's) — it reads and writes the same bytes —, `sam merge` of the 2 and of the 8 parts on the device path and through the
+host reader.  The ratios merge / trim qnames are printed run for run next to the spread of the trim qnames repeats.  With --check the
+inflated output of every merge row on both paths is compared with trim qnames' on the undealt file.
 
 --markdup: the count file (position-sorted, one reference per repeat) with duplicates: every fourth pair lies at the position and has
 the fragment length of the pair before it, and the pairs of every second group of four carry an RX:Z UMI (a duplicate pair its
@@ -66,6 +74,8 @@ coverage = "--coverage" in sys.argv
 human = "--human" in sys.argv
 coverage_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--coverage-file=")), None)
 subsample_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--subsample-file=")), None)
+merge = "--merge" in sys.argv
+merge_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--merge-files=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 millions = int(argv[0]) if len(argv) > 0 else 20
@@ -322,6 +332,89 @@ def subsample_rows():
     os.rmdir(d)
 
 
+def write_part_files(dirname, parts):
+    """the count file's records dealt alternately into `parts` files: record j of every repeat goes to part j mod parts; the paths"""
+    u = np.frombuffer(unit, dtype=np.uint8)
+    paths = []
+    for p in range(parts):
+        idx = range(p, len(starts), parts)
+        pu = np.concatenate([u[starts[j]:ends[j]] for j in idx])
+        lens = np.array([ends[j] - starts[j] for j in idx], dtype=np.int64)
+        pe = np.cumsum(lens)
+        ps = pe - lens
+
+        def blob(t, pu=pu, ps=ps, pe=pe):
+            v = pu.copy()
+            tb = np.frombuffer(struct.pack("<i", t), dtype=np.uint8)
+            for k in range(4):
+                v[ps + 4 + k] = tb[k]
+                v[ps + 24 + k] = tb[k]
+            raw, out_, lo, prev = v.tobytes(), [], 0, 0
+            for e in pe:                                                     # (blocks_of's rule: a block is flushed rather than a record split)
+                if e - lo > 0xff00:
+                    out_.append(bgzf(raw[lo:prev]))
+                    lo = prev
+                prev = int(e)
+            out_.append(bgzf(raw[lo:]))
+            return b"".join(out_)
+        path = os.path.join(dirname, f"p{parts}_{p}.bam")
+        with open(path, "wb") as f:
+            f.write(header(reps))
+            with ThreadPoolExecutor(16) as ex:
+                for b in ex.map(blob, range(reps)):
+                    f.write(b)
+            f.write(bgzf(b""))
+        paths.append(path)
+    return paths
+
+
+def merge_rows():
+    t0 = time.perf_counter()
+    write_count_file(bam)
+    parts = {P: write_part_files(d, P) for P in (2, 8)}
+    print(f"merge files: {n} BAM records on {reps} references, sorted, {os.path.getsize(bam) / 1e6:.0f} MB, and dealt alternately into 2 parts ("
+          + ", ".join(f"{os.path.getsize(p) / 1e6:.0f}" for p in parts[2]) + " MB) and 8 parts (" + ", ".join(f"{os.path.getsize(p) / 1e6:.0f}" for p in parts[8])
+          + f" MB), written in {time.perf_counter() - t0:.1f} s; {runs} runs per row, alternating", flush=True)
+    trim_sam = yardstick_sam or SAM
+    trim_label = "sam trim qnames   device" + (" (yardstick build)" if yardstick_sam else "")
+    rows = {}
+    for k in range(runs):
+        for label, cmd, env in ((trim_label, [trim_sam, "trim", "qnames", bam], None),
+                                ("sam merge 2      device", [SAM, "merge"] + parts[2], None),
+                                ("sam merge 2      host  ", [SAM, "merge"] + parts[2], {"SEQKIT_HOST_INFLATE": "1"}),
+                                ("sam merge 8      device", [SAM, "merge"] + parts[8], None),
+                                ("sam merge 8      host  ", [SAM, "merge"] + parts[8], {"SEQKIT_HOST_INFLATE": "1"})):
+            dt, cpu, rc, _, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+            lines = err.decode(errors="replace").split("\n")
+            served = [ln for ln in lines if ln.startswith("sam ")]
+            assert rc == 0 and served and ("host reader" if env else "device path") in served[0], (label, rc, err[-400:])
+            rows.setdefault(label, []).append((dt, cpu, [ln for ln in lines if ln.startswith("sk_bam_file_merge:")]))
+    for label, r in rows.items():
+        print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r), flush=True)
+    tq = [x[0] for x in rows[trim_label]]
+    for P in (2, 8):
+        dev, host = [x[0] for x in rows[f"sam merge {P}      device"]], [x[0] for x in rows[f"sam merge {P}      host  "]]
+        for ln in rows[f"sam merge {P}      device"][-1][2]:
+            print("  " + ln, flush=True)
+        print(f"merge {P} / trim qnames, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(dev, tq))
+              + f"; medians {float(np.median(dev)) / float(np.median(tq)):.2f}x; trim qnames max - min {max(tq) - min(tq):.2f} s = "
+              f"{(max(tq) - min(tq)) / float(np.median(tq)):.2f} of its median; device / host reader (medians) = {float(np.median(dev)) / float(np.median(host)):.2f}", flush=True)
+    if markdup_check:
+        dt, cpu, rc, _, err = timed([trim_sam, "trim", "qnames", bam], None, sink=out)
+        want = (rc, inflated_digest(out), err)
+        for P in (2, 8):
+            for env in (None, {"SEQKIT_HOST_INFLATE": "1"}):
+                dt, cpu, rc, _, err = timed([SAM, "merge"] + parts[P], env, sink=out)
+                assert (rc, inflated_digest(out), err) == want, (P, env, rc, err[-400:])
+        print(f"sam merge > file: inflated outputs of 2 and 8 parts on both paths identical to trim qnames' on the undealt file ({want[1]})", flush=True)
+        os.remove(out)
+    os.remove(bam)
+    for ps in parts.values():
+        for p in ps:
+            os.remove(p)
+    os.rmdir(d)
+
+
 HUMAN_REFS, HUMAN_LEN = 25, 124_000_000
 
 
@@ -367,6 +460,16 @@ def coverage_rows():
     os.rmdir(d)
 
 
+if merge_files is not None:
+    write_count_file(os.path.join(merge_files, "in.bam"))
+    for P in (2, 8):
+        write_part_files(merge_files, P)
+    print(f"wrote {merge_files}/in.bam and its 2 and 8 parts: {n} records", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if merge:
+    merge_rows()
+    sys.exit(0)
 if coverage_file is not None:
     write_count_file(coverage_file, HUMAN_REFS if human else None, HUMAN_LEN if human else 1 << 28)
     print(f"wrote {coverage_file}: {n} records, {os.path.getsize(coverage_file) / 1e6:.0f} MB", flush=True)
