@@ -296,19 +296,9 @@ static std::string expand_home(const std::string &path)      // PathArgs::get_pa
 // sk_bam_file_columns returns ("BAM\1" .. the end of the reference list: checked there already).
 static std::vector<std::string> header_names(const uint8_t *h, uint64_t len)
 {
-	auto u32_at = [&](uint64_t o) { return o + 4 <= len ? le32(h + o) : 0u; };
-	std::vector<std::string> names;
-	uint64_t o = 8 + (uint64_t)u32_at(4);
-	const uint32_t n_ref = u32_at(o);
-	o += 4;
-	for (uint32_t r = 0; r < n_ref && o + 4 <= len; r++) {
-		const uint32_t l_name = u32_at(o);
-		std::string name(reinterpret_cast<const char *>(h + o + 4), std::min<uint64_t>(l_name, len - o - 4));
-		if (!name.empty() && name.back() == '\0') name.pop_back();
-		names.push_back(name);
-		o += 4 + (uint64_t)l_name + 4;
-	}
-	return names;
+	bamfmt::RefList refs;
+	(void)refs.parse(h, len, len);
+	return refs.names(h);
 }
 
 // device buffers of one command's file path (sk_malloc_device), freed whichever way it is left
@@ -1786,21 +1776,10 @@ struct CovRefs { std::vector<std::string> names; std::vector<uint32_t> len; };
 bool cov_refs(const uint8_t *h, uint64_t n, CovRefs &out)
 {
 	out.names.clear(); out.len.clear();
-	if (n < 12 || memcmp(h, "BAM\1", 4) != 0) return false;
-	uint64_t o = 8 + (uint64_t)le32(h + 4);
-	if (o + 4 > n) return false;
-	const uint32_t n_ref = le32(h + o);
-	o += 4;
-	for (uint32_t r = 0; r < n_ref; r++) {
-		if (o + 4 > n) return false;
-		const uint64_t l_name = le32(h + o);
-		if (l_name > (1u << 20) || o + 4 + l_name + 4 > n) return false;
-		std::string name(reinterpret_cast<const char *>(h + o + 4), l_name);
-		if (!name.empty() && name.back() == '\0') name.pop_back();
-		out.names.push_back(name);
-		out.len.push_back(le32(h + o + 4 + l_name));
-		o += 4 + l_name + 4;
-	}
+	bamfmt::RefList refs;
+	if (refs.parse(h, n, n) != bamfmt::RefList::kOk) return false;
+	out.names = refs.names(h);
+	for (const bamfmt::RefList::Ref &r : refs.refs) out.len.push_back(r.l_ref);
 	return true;
 }
 

@@ -1,0 +1,526 @@
+// sk_bamfile_out.cpp — the BAM-writing file calls (include/seqkit_hip.h: sk_bam_file_rewrite, _minimize, _markdup, _subsample, _merge and
+// sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "sk_bamfile.h"
+
+using namespace bamfile;
+
+// ---- BAM out (include/seqkit_hip.h: sk_bam_file_rewrite, sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample; sk_bam_file_rewrite_next) ---
+// The front half above, then the call's own passes, among them a sizing pass (per block: output bytes, decline bits) and its scan; the
+// decision to serve the file is taken there, before any window exists.  Then every record's stream and output offsets, the windows, and
+// the header's members on their way.  A window is rewritten into one device buffer, cut into blocks of at most 0xff00 bytes, deflated where it lies and packed into
+// complete members; only the members' bytes are copied back.  Every allocation that fails leaves the file to the caller's reader
+// (info[5] = -21).
+
+// the header (first) or window w of the plan (the next non-empty one) into packed buffer b: rewrite, cut, deflate, pack, and the packed
+// size back; false: nothing left
+static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
+{
+	*rc = SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	int64_t first = 0, n = 0;
+	uint64_t raw_len = 0;
+	hipError_t e = hipSuccess;
+	if (!s.header_done) {
+		s.header_done = true;
+		raw_len = s.header.size();
+		e = hipMemcpyAsync(s.d_raw, s.header.data(), (size_t)raw_len, hipMemcpyHostToDevice, st);
+	} else {
+		size_t w;
+		if (!s.next_window(w)) return false;
+		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
+		raw_len = s.wo[w + 1] - s.wo[w];
+		const WriteOp &op = s.write;
+		switch (op.kind) {
+		case WriteOp::kRewrite: e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], op.flags, s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kMinimize: e = sk::launch_bam_min_write(s.d_out, s.krec, s.kout, op.ids, first, n, s.wo[w], op.flags, op.fill, s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kMarkdup: e = sk::launch_bam_md_write(s.d_out, s.krec, s.kout, op.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kSubsample: e = sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
+		case WriteOp::kMerge:                                               // (krec: offsets from input 1's stream that reach every input's; without a suffix a record is one copied span)
+			e = op.merge_in ? sk::launch_bam_merge_write(s.d_out, s.krec, s.kout, op.merge_in, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st)
+			                : sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st);
+			break;
+		}
+	}
+	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
+	if (e == hipSuccess) e = hipStreamWaitEvent(st, s.ev_copy[b], 0);                   // (the copy out of this packed buffer)
+	if (e == hipSuccess) e = sk::launch_bgzf_cut(raw_len, s.d_blocks, nblk, st);
+	if (e == hipSuccess) e = s.level ? sk::launch_bgzf_deflate(s.d_raw, s.d_blocks, nblk, s.d_slots, SK_DEFLATE_SLOT, s.d_tokens, s.d_result, s.d_crc, sk::ctx_n_cu(c), st)
+	                                 : sk::launch_bgzf_crc(s.d_raw, s.d_blocks, nblk, s.d_crc, sk::ctx_n_cu(c), st);
+	if (e == hipSuccess) e = sk::launch_bgzf_pack(s.d_raw, s.d_blocks, nblk, s.d_slots, SK_DEFLATE_SLOT, s.d_result, s.d_crc, s.level ? 0 : 1, s.d_msz,
+	                                              s.d_pack[b], sk::ctx_n_cu(c), st);
+	if (e == hipSuccess) e = hipMemcpyAsync(s.h_size + b, s.d_msz + nblk, 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipEventRecord(s.ev[b], st);
+	if (e != hipSuccess) { *rc = sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_rewrite: window at record %lld: %s", (long long)first, hipGetErrorString(e)); return false; }
+	s.first[b] = first; s.n[b] = n; s.raw[b] = raw_len;
+	return true;
+}
+
+// What sk_bam_file_rewrite, sk_bam_file_minimize, sk_bam_file_markdup and sk_bam_file_subsample open with once the stream is verified: the per-block scratch of
+// their passes with the decline word behind it, the blocks' first record indices on the device, and the rewrite state with room for
+// every record's stream and output offsets (ctx slot kKeepFileCols).  s == nullptr afterwards: that memory cannot be had, and the file
+// is left to the caller's reader (info[5] = -21).
+struct RwOpen {
+	RewriteState *s = nullptr;
+	uint64_t *d_blk = nullptr;                   // blk_cols columns of nb + 1 u64 each
+	uint64_t *d_rb = nullptr;                    // block b's first record: nb entries, and one word more that is the caller's
+	uint32_t *d_decline = nullptr;               // zeroed
+	std::vector<uint64_t> rb;                    // (what d_rb is copied from: it lives until the caller has waited for the stream)
+	double t_size = 0;
+};
+static int rw_open(sk_ctx *c, Cleanup &cl, const Front &fr, int blk_cols, RwOpen &o, double info[8])
+{
+	o.t_size = now_ms();
+	hipStream_t st = sk::ctx_stream(c);
+	const int64_t nb = fr.nb;
+	if (hipMalloc((void **)&o.d_blk, (size_t)(nb + 1) * 8 * (size_t)(blk_cols + 1) + 64) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+	cl.dev.push_back(o.d_blk);
+	o.d_rb = o.d_blk + (size_t)(nb + 1) * (size_t)blk_cols;
+	o.d_decline = (uint32_t *)(o.d_rb + nb + 1);
+	BF_HIP(hipMemsetAsync(o.d_decline, 0, 4, st));
+	if (int r = block_first_records(c, fr, o.rb)) return r;
+	if (nb) BF_HIP(hipMemcpyAsync(o.d_rb, o.rb.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+	int krc = SK_OK;
+	const size_t a_col = up(fr.n_records * 8 + 8);
+	uint8_t *kb = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileCols, 2 * a_col, false, &krc);
+	if (!kb) BF_LEAVE(21);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	R->rw.krec = (uint64_t *)kb; R->rw.kout = (uint64_t *)(kb + a_col);
+	o.s = &R->rw;
+	return SK_OK;
+}
+
+// What they share once the stream and output offsets (s.krec, s.kout) of the N records that go out are there — every record of the file,
+// or for sk_bam_file_subsample the kept ones —: the window plan, the window area, and the header's members on their way.  `write`: the
+// kernel that writes a window; `total`: the records' output bytes.
+static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WriteOp &write, int level, uint64_t window_bytes, uint64_t N,
+                    uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	RewriteState &s = *o.s;
+	int krc = SK_OK;
+	// ---- the windows: at most W rewritten bytes each
+	uint64_t mx[3];                                                     // records, rewritten bytes
+	bool room = true;
+	if (int r = plan_windows(c, cl, window_bytes, s.kout, nullptr, N, total, 0, s, s.wo, nullptr, mx, &room)) return r;
+	if (!room) BF_LEAVE(21);
+	s.header = bamfmt::rewrite_header(fr.header);
+	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
+	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
+	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	const uint64_t pack = max_raw + nblk * 31 + 64;
+	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
+	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
+	if (!dw) BF_LEAVE(21);
+	const size_t p_pack = up(pack + 28);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * p_pack + 64, true, &krc);
+	if (!hw) BF_LEAVE(21);
+	s.d_raw = dw; s.d_blocks = dw + a_raw; s.d_result = (uint32_t *)(dw + a_raw + a_blk); s.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
+	s.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
+	uint8_t *dp = dw + a_raw + a_blk + a_res + a_crc + a_msz;
+	s.d_pack[0] = dp; s.d_pack[1] = dp + a_pack;
+	s.d_slots = level ? dp + 2 * a_pack : nullptr;
+	s.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
+	s.h_pin[0] = hw; s.h_pin[1] = hw + p_pack; s.h_size = (uint64_t *)(hw + 2 * p_pack);
+	for (int b = 0; b < 2; b++)
+		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
+	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
+	s.write = write; s.level = level; s.header_done = false;
+	s.begin(fr.d_out, ((Ranges *)sk::ctx_ext(c))->gen);
+	int rc = SK_OK;
+	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
+	if (rc) return rc;
+	s.live = true;
+	if (n_records) *n_records = (int64_t)N;
+	if (raw_bytes) *raw_bytes = s.header.size() + total;
+	*handled = 1;
+	char tail[128];
+	snprintf(tail, sizeof tail, "; %llu records, %llu rewritten bytes, %lld windows", (unsigned long long)N, (unsigned long long)total, (long long)s.ws.size() - 1);
+	file_call_close(fr, "size + index + plan", o.t_size, tail, info);
+	return SK_OK;
+}
+
+extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int level, uint64_t window_bytes, int64_t *n_records, uint64_t *raw_bytes,
+                                   int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_rewrite", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (op < SK_REWRITE_TRIM_QNAMES || op > SK_REWRITE_TAGS_FROM_QNAME) return sk::ctx_fail(c, SK_ERR_INVALID, "op = %d", op);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 1, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const int64_t nb = fr.nb;
+	// ---- the sizing pass: per block the rewritten bytes (then their exclusive offsets), the decline bits
+	uint64_t *bo = o.d_blk;
+	BF_HIP(sk::launch_bam_rw_size(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, o.d_decline, st));
+	uint64_t total = 0;
+	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
+	BF_LEAVE_DECLINED(o.d_decline, 0);                                  // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
+	// ---- every record's stream and output offsets
+	BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, o.d_rb, o.s->krec, o.s->kout, st));
+	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kRewrite, op}, level, window_bytes, fr.n_records, total, n_records, raw_bytes, handled, info);
+}
+
+// ---- sam minimize (include/seqkit_hip.h: sk_bam_file_minimize; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then with SK_MINIMIZE_READ_IDS the id passes (sk_bamminimize.hip: keys, sort, runs, ids) in the working memory of ctx
+// slot kKeepPassWork — two key and two index buffers for the sort (24 B per record and the sort's own scratch); behind the sort the idle
+// key buffer holds src and the opener counts and the idle index buffer the ids — then the sizing pass with the ids' digits, and from
+// there on what sk_bam_file_rewrite does.  The file is left to the caller's reader (info[5] = -21) when that memory cannot be had or
+// the file has 2^32 records or more (the ids are u32), and with info[5] = -(30 + bits) on an invalid record (8), a CIGAR operation
+// code above 8 (32) or two keys with one hash (64).
+extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint8_t baseq_fill, int level, uint64_t window_bytes, int64_t *n_records,
+                                    uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_minimize", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    const int all = SK_MINIMIZE_READ_IDS | SK_MINIMIZE_BASE_QUALITIES | SK_MINIMIZE_TAGS;
+		    if (!flags || (flags & ~all) || ((flags & SK_MINIMIZE_BASE_QUALITIES) && !(flags & SK_MINIMIZE_TAGS)))
+			    return sk::ctx_fail(c, SK_ERR_INVALID, "flags = %d", flags);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 1, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *bo = o.d_blk, *krec = o.s->krec, *kout = o.s->kout;
+	// ---- the read ids
+	const uint32_t *ids = nullptr;
+	if ((flags & SK_MINIMIZE_READ_IDS) && N) {
+		int bits = 64;                                                  // (a test knob: fewer bits make hash collisions reachable)
+		if (const char *ev = getenv("SK_MINIMIZE_KEY_BITS")) { const int v = atoi(ev); if (v >= 1 && v <= 64) bits = v; }
+		passmem::SortBufs sb;
+		BF_HIP(pass_temp(sb, N, bits, st, [](size_t *) { return hipSuccess; }));
+		uint32_t *agg = nullptr;
+		passmem::Layout L;
+		L.add(sb.key, N * 8); L.add(sb.idx, N * 4); L.add(agg, (N / 1024 + 2) * 4); L.add(sb.temp, sb.temp_bytes);
+		uint8_t *own = nullptr;
+		if (!pass_memory(c, passmem::place(L.total(), 0, 0, true), own)) BF_LEAVE(21);     // (all of it kept: the windows read the ids)
+		L.carve(own);
+		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, bits, sk::IdRule{0, 0u}, krec, sb.key[0], sb.idx[0], o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (the passes below read the names of valid records only)
+		int cur = 0;
+		size_t tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(sb.temp, &tb, sb.key, sb.idx, N, bits, &cur, st));
+		uint32_t *src = (uint32_t *)sb.key[cur ^ 1], *cnt = src + N;
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, sb.key[cur], sb.idx[cur], N, bits, sk::IdRule{0, 0u}, agg, src, cnt, sb.idx[cur ^ 1], o.d_decline, st));
+		ids = sb.idx[cur ^ 1];
+	}
+	// ---- the sizing pass: per block the output bytes (then their exclusive offsets), the decline bits
+	BF_HIP(sk::launch_bam_min_size(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, flags, ids, bo, o.d_decline, st));
+	uint64_t total = 0;
+	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
+	BF_LEAVE_DECLINED(o.d_decline, 0);
+	BF_HIP(sk::launch_bam_min_index(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, flags, ids, bo, krec, kout, st));
+	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMinimize, flags, baseq_fill, ids}, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
+}
+
+// ---- sam mark duplicates (include/seqkit_hip.h: sk_bam_file_markdup; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then the passes of sk_bammarkdup.hip.  Their working memory — two key and two index buffers for the sort (before the
+// sort the second of each holds (tid, pos) and the run flags, and the first index buffer the run indices), five u32 signature columns
+// and the scratch of the sort and the scan: 44 B per record — is needed only until the clusters are found, and lies in the device
+// buffer of the COMPRESSED file, which is idle once the stream is verified (a BAM record takes more compressed bytes than that; where
+// it does not, ctx slot kKeepPassWork serves).  Only the u16 flag column, which the windows read, is kept in that slot: a gigabyte
+// taken and given back for a 20 M-record file cost the command 0.1 s.  The records' bytes and sizes do not change: a record's output
+// offset is its stream offset less the header's, the windows are planned over those, and the write kernel patches the flag.  Declined
+// files: the list in include/seqkit_hip.h.
+extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, int level, uint64_t window_bytes, int64_t *n_records,
+                                   int64_t *n_duplicates, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_markdup", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (n_duplicates) *n_duplicates = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 0, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *d_count = o.d_rb + nb;                                    // (no per-block column, one word: the duplicates)
+	passmem::SortBufs sb;
+	BF_HIP(pass_temp(sb, N ? N : 1, 64, st, [&](size_t *b) { return sk::bam_md_run_scan(nullptr, b, nullptr, nullptr, N ? N : 1, st); }));
+	sk::MdCols cols;
+	cols.krec = o.s->krec; cols.kout = o.s->kout;
+	const uint64_t sig = N * 4 + 4;                                     // (a signature column)
+	passmem::Layout L;
+	L.add(sb.key, N * 8 + 8); L.add(sb.idx, N * 4 + 4);
+	L.add(cols.start, sig); L.add(cols.fl, sig); L.add(cols.lseq, sig); L.add(cols.uoff, sig); L.add(cols.ulen, sig);
+	L.add(sb.temp, sb.temp_bytes);
+	const passmem::Placement pl = passmem::place(N * 2 + 2, L.total(), fr.fsize + 64, getenv("SK_MARKDUP_OWN_MEMORY") != nullptr);   // (the knob: for tests of the other placement)
+	uint8_t *own = nullptr;
+	if (!pass_memory(c, pl, own)) BF_LEAVE(21);
+	pl.trace(fr.who, "", "the compressed file's buffer");
+	L.carve(pl.scratch_at(own, fr.d_comp));
+	cols.tidpos = sb.key[1]; cols.nflag = (uint16_t *)own;
+	// ---- signatures, order, runs: the decision to serve the file
+	BF_HIP(sk::launch_bam_md_sig(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, ignore_umi ? 1 : 0, fr.first, cols, o.d_decline, st));
+	BF_HIP(sk::launch_bam_md_order(cols.tidpos, N, sb.idx[1], o.d_decline, st));
+	uint32_t runs = 0;
+	if (N) {
+		size_t tb = sb.temp_bytes;
+		BF_HIP(sk::bam_md_run_scan(sb.temp, &tb, sb.idx[1], sb.idx[0], N, st));
+		BF_HIP(hipMemcpyAsync(&runs, sb.idx[0] + (N - 1), 4, hipMemcpyDeviceToHost, st));
+	}
+	BF_HIP(hipStreamSynchronize(st));                                  // (runs)
+	BF_LEAVE_DECLINED(o.d_decline, runs >= 0x7fffffffu ? 64u : 0u);
+	// ---- keys, the sort (only the bits the keys use: the all-ones key of the unmapped reads stays the largest), clusters, count
+	int bits = 34;
+	while (bits < 64 && ((uint64_t)1 << (bits - 33)) <= (uint64_t)runs) bits++;
+	uint64_t dups = 0;
+	if (N) {
+		BF_HIP(sk::launch_bam_md_keys(sb.idx[0], cols, N, sb.key[0], sb.idx[0], st));
+		int cur = 0;
+		size_t tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(sb.temp, &tb, sb.key, sb.idx, N, bits, &cur, st));
+		BF_HIP(sk::launch_bam_md_cluster(fr.d_out, cols, sb.key[cur], sb.idx[cur], N, d_count, sk::ctx_n_cu(c), st));
+		BF_HIP(hipMemcpyAsync(&dups, d_count, 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMarkdup, 0, 255, nullptr, cols.nflag}, level, window_bytes, N, fr.stream_len - fr.first, n_records, raw_bytes, handled, info);
+	if (rc == SK_OK && *handled && n_duplicates) *n_duplicates = (int64_t)dups;
+	return rc;
+}
+
+// ---- sam subsample (include/seqkit_hip.h: sk_bam_file_subsample; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then sk_bamminimize.hip's id passes under the rule {the whole name is the key, 0x800 takes no part} — they number the
+// fragments — and the passes of sk_bamsubsample.hip: the keep pass, two scans and the compaction, which leaves the KEPT records' stream
+// and output offsets where sk_bam_file_rewrite leaves every record's.  The working memory (the compressed file's device buffer, idle by
+// then, or where that is too small ctx slot kKeepPassWork): two key and two
+// index buffers for the sort and every record's stream offset, 32 B per record, and the scratch of the sort and the scans; behind the
+// sort the idle key buffer holds src and the opener counts and then the kept lengths and places, the idle index buffer the fragment
+// numbers, and the sorted keys' buffer the output offsets.  Declined files: the list in include/seqkit_hip.h.
+extern "C" int sk_bam_file_subsample(sk_ctx *c, const char *path, float fraction, uint64_t seed, int level, uint64_t window_bytes, int64_t *n_records,
+                                     int64_t *n_total, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_subsample", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (n_total) *n_total = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (!(fraction >= 0.0f && fraction <= 1.0f)) return sk::ctx_fail(c, SK_ERR_INVALID, "fraction = %g", (double)fraction);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 3, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint64_t *d_counts = o.d_blk;                                       // (no per-block column, three words: counted, kept, kept bytes)
+	uint64_t counts[3] = {0, 0, 0};
+	if (N) {
+		const sk::IdRule rule{1, 0x800u};
+		int bits = 63;                                                  // (a test knob: fewer bits make hash collisions reachable; bit `bits` marks a record with 0x800)
+		if (const char *ev = getenv("SK_SUBSAMPLE_KEY_BITS")) { const int v = atoi(ev); if (v >= 1 && v <= 64) bits = std::min(v, 63); }
+		passmem::SortBufs sb;
+		BF_HIP(pass_temp(sb, N, bits + 1, st, [&](size_t *b) { return sk::bam_sub_scans(nullptr, b, nullptr, nullptr, nullptr, N, st); }));
+		uint64_t *krec = nullptr;
+		uint32_t *agg = nullptr;
+		passmem::Layout L;
+		L.add(sb.key, N * 8); L.add(krec, N * 8); L.add(sb.idx, N * 4); L.add(agg, (N / 1024 + 2) * 4); L.add(sb.temp, sb.temp_bytes);
+		// (all of it is idle once the kept records are compacted: as sk_bam_file_markdup's scratch it lies in the device buffer of the
+		// compressed file where that is large enough, and a gigabyte is not taken and given back for a 20 M-record file)
+		const passmem::Placement pl = passmem::place(0, L.total(), fr.fsize + 64, false);
+		uint8_t *own = nullptr;
+		if (!pass_memory(c, pl, own)) BF_LEAVE(21);
+		pl.trace(fr.who, "", "the compressed file's buffer");
+		L.carve(pl.scratch_at(own, fr.d_comp));
+		// ---- the fragment numbers
+		BF_HIP(sk::launch_bam_min_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, bits, rule, krec, sb.key[0], sb.idx[0], o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (8: the passes below read the names and flags of valid records only)
+		int cur = 0;
+		size_t tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(sb.temp, &tb, sb.key, sb.idx, N, bits + 1, &cur, st));
+		uint32_t *src = (uint32_t *)sb.key[cur ^ 1], *cnt = src + N, *ids = sb.idx[cur ^ 1];
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, sb.key[cur], sb.idx[cur], N, bits, rule, agg, src, cnt, ids, o.d_decline, st));
+		// ---- the decisions: the file is served or left here
+		uint32_t *len = src, *pos = cnt;
+		uint64_t *off = sb.key[cur];
+		BF_HIP(sk::launch_bam_sub_keep(fr.d_out, krec, ids, N, seed, sk::subsample_threshold(fraction), len, d_counts, o.d_decline, sk::ctx_n_cu(c), st));
+		BF_HIP(hipMemcpyAsync(counts, d_counts, 24, hipMemcpyDeviceToHost, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 a counted record without 0x1, 64 two names with one hash)
+		// ---- the kept records' stream and output offsets
+		tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sub_scans(sb.temp, &tb, len, pos, off, N, st));
+		BF_HIP(sk::launch_bam_sub_compact(krec, len, pos, off, N, o.s->krec, o.s->kout, st));
+	}
+	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kSubsample}, level, window_bytes, counts[1], counts[2], n_records, raw_bytes, handled, info);
+	if (rc == SK_OK && *handled && n_total) *n_total = (int64_t)counts[0];
+	return rc;
+}
+
+// ---- sam merge (include/seqkit_hip.h: sk_bam_file_merge; the windows come from sk_bam_file_rewrite_next) ---
+// K verified streams at once.  The front half serves one file per ctx and keeps its ranges with it, so every input but the first gets a
+// helper context of its own on the same device (kept with the caller's ctx in Ranges::helpers, freed with it, invisible in the C-ABI)
+// and the unchanged front half runs in each, one after the other: input 1 in the caller's ctx first — that ends an earlier call's windows
+// in flight, which may read the helpers' streams — then the others.  When a front returns its stream is verified, which takes the
+// host's word: nothing of it is still running, and every record pass and every window of this call runs on the caller's streams.  All
+// streams lie in one address space, so a record is addressed by its offset from input 1's stream mod 2^64 and the window writers keep
+// their one base pointer.  The reference names are compared on the host as each front returns.  Then the passes of sk_bammerge.hip:
+// keys per input, the order check, the shared sort over all records, the gather and the scan.  Their working memory (29 B per record and
+// the scratch of the sort and the scan) lies in input 1's compressed file's device buffer, idle by then, where that is large enough,
+// else in ctx slot kKeepPassWork, which always holds the one byte per output record that the windows read with a suffix.  Declined
+// files: the list in include/seqkit_hip.h.
+extern "C" int sk_bam_file_merge(sk_ctx *c, const char *const *paths, int n_paths, int suffix, int level, uint64_t window_bytes, int64_t *n_records,
+                                 uint64_t *raw_bytes, int *handled, double info[8])
+{
+	if (!c || !paths || !handled) return SK_ERR_INVALID;
+	*handled = 0;
+	if (info) for (int i = 0; i < 8; i++) info[i] = 0.0;
+	if (n_records) *n_records = 0;
+	if (raw_bytes) *raw_bytes = 0;
+	if (n_paths < 2) return sk::ctx_fail(c, SK_ERR_INVALID, "n_paths = %d", n_paths);
+	for (int i = 0; i < n_paths; i++) if (!paths[i]) return sk::ctx_fail(c, SK_ERR_INVALID, "paths[%d] is NULL", i);
+	if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+	if (int r = sk::ctx_bind(c)) return r;
+	if (n_paths > 99) BF_LEAVE(21);                                     // (the suffix writer knows one and two digits)
+	const size_t K = (size_t)n_paths;
+	// (the helpers' Cleanups are declared first and so run last: the caller's streams are waited for before a helper's tables are freed)
+	std::unique_ptr<Cleanup[]> cls(new Cleanup[K]);
+	Cleanup cl;
+	std::vector<Front> fin(K);
+	std::vector<std::string> names0;
+	int dev = 0;
+	BF_HIP(hipGetDevice(&dev));
+	for (size_t i = 0; i < K; i++) {
+		fin[i].who = "sk_bam_file_merge";
+		if (i == 0) {
+			if (int r = bam_file_front(c, paths[0], cls[0], fin[0], info)) return r;
+		} else {
+			Ranges *both = (Ranges *)sk::ctx_ext(c);
+			while (both->helpers.size() < i) {
+				sk_ctx *h = nullptr;
+				if (sk_create(dev, &h) != SK_OK || !h) BF_LEAVE(21);
+				both->helpers.push_back(h);
+			}
+			sk_ctx *h = both->helpers[i - 1];
+			if (int r = bam_file_front(h, paths[i], cls[i], fin[i], info)) return sk::ctx_fail(c, r, "input %zu: %s", i + 1, sk_last_error(h));
+		}
+		if (!fin[i].ready) return SK_OK;                                  // (info[5] says at which check)
+		if (i == 0) names0 = fin[0].refs.names(fin[0].header.data());
+		else if (fin[i].refs.names(fin[i].header.data()) != names0) {
+			if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "sk_bam_file_merge: declined (bits 0x4): input %zu's reference names differ\n", i + 1);
+			BF_LEAVE(30 + 4);
+		}
+	}
+	// ---- one front over all inputs for the spine: the blocks and records of all of them in a row, input 1's header and stream
+	cl.wait_for = {sk::ctx_stream(c), sk::ctx_stream2(c)};
+	Front all = fin[0];
+	for (size_t i = 1; i < K; i++) {
+		all.nb += fin[i].nb; all.n_records += fin[i].n_records; all.fsize += fin[i].fsize; all.stream_len += fin[i].stream_len; all.n_host += fin[i].n_host;
+		all.rounds = std::max(all.rounds, fin[i].rounds);
+		all.nrec.insert(all.nrec.end(), fin[i].nrec.begin(), fin[i].nrec.end());
+	}
+	all.t_walk = now_ms();
+	const Front &fr = all;
+	const uint64_t N = all.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, all, 0, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const uint8_t *kin = nullptr;
+	uint64_t total = 0;
+	if (N) {
+		passmem::SortBufs sb;
+		BF_HIP(pass_temp(sb, N, 64, st, [&](size_t *b) { return sk::bam_merge_scan(nullptr, b, nullptr, N, st); }));
+		sk::MergeCols cols;
+		passmem::Layout L;
+		L.add(sb.key, N * 8); L.add(cols.addr, N * 8); L.add(sb.idx, N * 4); L.add(cols.len, N * 4); L.add(cols.in, N); L.add(sb.temp, sb.temp_bytes);
+		const passmem::Placement pl = passmem::place(N, L.total(), fin[0].fsize + 64, false);      // (kept: every output record's input number)
+		uint8_t *kb = nullptr;
+		if (!pass_memory(c, pl, kb)) BF_LEAVE(21);
+		char inputs[32];
+		snprintf(inputs, sizeof inputs, "%zu inputs", K);
+		pl.trace(fr.who, inputs, "the first compressed file's buffer");
+		L.carve(pl.scratch_at(kb, fin[0].d_comp));
+		cols.key = sb.key[0]; cols.idx = sb.idx[0];
+		// ---- keys and checks, input by input: the call is served or left here
+		int64_t b0 = 0;
+		for (size_t i = 0; i < K; i++) {
+			const uint32_t sl = suffix ? (i + 1 >= 10 ? 3u : 2u) : 0u;
+			BF_HIP(sk::launch_bam_merge_keys(fin[i].d_out, fin[i].d_bend, fin[i].d_entry, fin[i].nb, o.d_rb + b0, (uint64_t)(uintptr_t)fin[i].d_out - (uint64_t)(uintptr_t)fin[0].d_out,
+			                                 (uint32_t)(i + 1), sl, cols, o.d_decline, st));
+			b0 += fin[i].nb;
+		}
+		BF_HIP(sk::launch_bam_merge_order(cols, N, o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 a suffixed name above 254 bytes, 2 an unsorted input, 8 an invalid record)
+		// ---- the order: a stable sort of all records by the key, then every output record's address, offset and input number
+		int cur = 0;
+		size_t tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(sb.temp, &tb, sb.key, sb.idx, N, 64, &cur, st));
+		BF_HIP(sk::launch_bam_merge_gather(sb.idx[cur], cols, N, o.s->krec, o.s->kout, kb, st));
+		tb = sb.temp_bytes;
+		BF_HIP(sk::bam_merge_scan(sb.temp, &tb, o.s->kout, N, st));
+		BF_HIP(hipMemcpyAsync(&total, o.s->kout + N, 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+		if (suffix) kin = kb;
+	}
+	WriteOp op;
+	op.kind = WriteOp::kMerge; op.merge_in = kin;
+	return rw_begin(c, cl, all, o, op, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
+}
+
+extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
+{
+	if (!c || !w) return SK_ERR_INVALID;
+	memset(w, 0, sizeof *w);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	if (!R || !R->rw.current(R->gen)) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_rewrite_next: no sk_bam_file_rewrite in progress");
+	if (int r = sk::ctx_bind(c)) return r;
+	RewriteState &s = R->rw;
+	const int b = s.cur;
+	if (b < 0) return SK_OK;                                            // the end
+	BF_HIP(hipEventSynchronize(s.ev[b]));
+	uint64_t bytes = s.h_size[b];
+	int rc = SK_OK;
+	s.cur = rw_issue(c, s, b ^ 1, &rc) ? (b ^ 1) : -1;                    // (the buffer of the window returned last time: the caller is done with it)
+	if (rc) { s.live = false; return rc; }
+	hipStream_t st2 = sk::ctx_stream2(c);
+	if (bytes) BF_HIP(hipMemcpyAsync(s.h_pin[b], s.d_pack[b], (size_t)bytes, hipMemcpyDeviceToHost, st2));
+	BF_HIP(hipEventRecord(s.ev_copy[b], st2));
+	BF_HIP(hipEventSynchronize(s.ev_copy[b]));
+	if (s.cur < 0) { memcpy(s.h_pin[b] + bytes, bamfmt::kBgzfEof, 28); bytes += 28; }   // the last window ends with the EOF block
+	w->first = s.first[b]; w->n = s.n[b];
+	w->bgzf = s.h_pin[b]; w->bytes = bytes; w->raw_bytes = s.raw[b];
+	return SK_OK;
+}

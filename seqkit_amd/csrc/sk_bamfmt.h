@@ -1,8 +1,11 @@
-// sk_bamfmt.h — BAM and BGZF format bits that the library (sk_bamfile.cpp) and the hosts (sam_main.cpp, host_common.cpp) read or write.
+// sk_bamfmt.h — BAM and BGZF format bits that the library (sk_bamfile*.cpp) and the hosts (sam_main.cpp, host_common.cpp) read or write.
 // Plain C++: the hosts are built with g++.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
+#include <string>
 #include <vector>
 
 namespace bamfmt {
@@ -31,5 +34,54 @@ inline std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h)
 	o.insert(o.end(), h.begin() + 8 + (ptrdiff_t)l_text, h.end());
 	return o;
 }
+
+// The reference list of a BAM header (SAMv1 §4.2: magic, l_text, text, n_ref, then per reference l_name, name, l_ref), read from the
+// first `have` bytes of a stream of `total` bytes; no byte at or beyond `have` is read.  kBad: no BAM magic, a name of more than 2^20
+// bytes (the hosts' reader refuses such a header), or a field that ends beyond `total`; kMore: a field ends beyond `have`; kOk: `end` is
+// where the list ends — the first record's offset — and refs holds, per reference, where its name lies in h and the two lengths.
+// n_ref is the header's count as far as it was read, -1 where that exceeds 0x7fffffff.
+struct RefList {
+	enum Status { kOk, kMore, kBad };
+	struct Ref { uint64_t name_off; uint32_t l_name, l_ref; };
+	uint64_t end = 0;
+	int32_t n_ref = -1;
+	std::vector<Ref> refs;
+	Status parse(const uint8_t *h, uint64_t have, uint64_t total)
+	{
+		end = 0; n_ref = -1; refs.clear();
+		Status st = kOk;
+		auto need = [&](uint64_t upto) { if (upto > have) { st = upto > total ? kBad : kMore; return false; } return true; };
+		if (!need(12)) return st;
+		if (memcmp(h, "BAM\1", 4) != 0) return kBad;
+		uint64_t o = 8 + (uint64_t)le32(h + 4);
+		if (!need(o + 4)) return st;
+		const uint32_t n = le32(h + o);
+		n_ref = n <= 0x7fffffffu ? (int32_t)n : -1;
+		o += 4;
+		for (uint32_t r = 0; r < n; r++) {
+			if (!need(o + 4)) return st;
+			const uint32_t l_name = le32(h + o);
+			if (l_name > (1u << 20)) return kBad;
+			if (!need(o + 4 + (uint64_t)l_name + 4)) return st;
+			refs.push_back(Ref{o + 4, l_name, le32(h + o + 4 + l_name)});
+			o += 4 + (uint64_t)l_name + 4;
+		}
+		end = o;
+		return kOk;
+	}
+	// reference r's name as the hosts' reader keeps it: one trailing NUL dropped, other bytes kept
+	std::string name(const uint8_t *h, size_t r) const
+	{
+		std::string s(reinterpret_cast<const char *>(h) + refs[r].name_off, refs[r].l_name);
+		if (!s.empty() && s.back() == '\0') s.pop_back();
+		return s;
+	}
+	std::vector<std::string> names(const uint8_t *h) const
+	{
+		std::vector<std::string> v;
+		for (size_t r = 0; r < refs.size(); r++) v.push_back(name(h, r));
+		return v;
+	}
+};
 
 }  // namespace bamfmt

@@ -573,7 +573,7 @@ extern "C" int sk_count_order_check_dev(sk_ctx *c, const uint16_t *flag, const u
 	return SK_OK;
 }
 
-// ---- launchers of the reads passes and the window plan (sk_bamfile.cpp: sk_bam_file_reads, sk_bam_file_rewrite) ------------------
+// ---- launchers of the reads passes and the window plan (sk_bamfile_reads.cpp: sk_bam_file_reads; sk_bamfile_out.cpp: sk_bam_file_rewrite) ------------------
 namespace sk {
 hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int fmt, int want_unpaired,
                                  uint64_t *bk, uint64_t *bt, uint64_t *bn, uint32_t *decline, hipStream_t st)

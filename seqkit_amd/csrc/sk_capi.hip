@@ -60,7 +60,7 @@ struct sk_ctx {
 	size_t pin_bytes = 0;
 	// buffers that stay with the ctx from one call to the next (sk::ctx_keep; sk_internal.h: sk::KeepSlot)
 	struct Kept { void *p = nullptr; size_t cap = 0; bool pinned = false; } kept[sk::kKeepSlots];
-	void *ext = nullptr;               // an object another translation unit keeps with the ctx (sk_bamfile.cpp: its mapped output range), and how to free it
+	void *ext = nullptr;               // an object another translation unit keeps with the ctx (sk_bamfile.h: Ranges, the file calls' mapped ranges and window state), and how to free it
 	void (*ext_free)(void *) = nullptr;
 	sk::Census *census = nullptr;
 	ncclComm_t comm = nullptr;         // one-process-per-GPU communicator (sk_comm_init_rank)

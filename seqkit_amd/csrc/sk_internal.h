@@ -337,7 +337,7 @@ constexpr int kMaxCensusLen = 31;
 
 }  // namespace sk
 
-// ---- what sk_bamfile.cpp needs of a ctx (sk_capi.hip owns the struct) ----
+// ---- what the file calls (sk_bamfile*.cpp) need of a ctx (sk_capi.hip owns the struct) ----
 struct sk_ctx;
 namespace sk {
 // The buffers that stay with a ctx from call to call (ctx_keep).  The file calls' front half (sk_bamfile.cpp: bam_file_front) keeps the
@@ -347,8 +347,11 @@ enum KeepSlot {
 	kKeepComp = 0, kKeepOut = 1, kKeepPin = 2, kKeepTable = 3, kKeepBlocks = 4, kKeepStatus = 5,   // the front half
 	kKeepCols = 6,                                      // sk_bam_file_columns: the columns, which sk_bam_fragments_bed_dev reads after it
 	kKeepTextPin = 7, kKeepText = 8,                    // sk_bam_fragments_bed_dev: the BED text (sk_bamtext.hip)
-	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bam_file_reads / _rewrite / _minimize / _markdup: per-record columns, windows
-	kKeepPassWork = 12,                                 // the record passes' working memory. sk_bam_file_minimize: the sort's keys and indices, then the read ids; sk_bam_file_subsample: the same and every record's stream offset, until the kept records are compacted; sk_bam_file_markdup: the flag column (and its scratch where the compressed file's buffer is too small); sk_bam_file_coverage: the events, where that buffer is too small
+	kKeepFileCols = 9, kKeepFileWin = 10, kKeepFilePin = 11,    // sk_bamfile_reads.cpp, sk_bamfile_out.cpp: per-record columns, windows
+	// The record passes' working memory (sk_passmem.h: each call lists its regions in a Layout, and a Placement says where they lie).
+	// Here lies what a call's windows read later — minimize's read ids, markdup's flag column, merge's input numbers — and behind it the
+	// passes' scratch of markdup, subsample, merge and coverage where the compressed file's idle buffer is too small for it.
+	kKeepPassWork = 12,
 	kKeepSlots = 13
 };
 hipStream_t ctx_stream(sk_ctx *c);

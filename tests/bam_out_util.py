@@ -1,8 +1,28 @@
 """What the tests of the three BAM-writing commands (`sam trim qnames` and its two siblings, `sam minimize`, `sam mark duplicates`)
 share: the check of a rewrite-window call's windows, and the run of a command over its three paths."""
+import struct
+import zlib
+
 import pytest
 
 from tests import cli_util as cu
+
+
+def zlib_members(data):
+    """every BGZF member of data inflated by zlib itself, its CRC-32 and ISIZE checked; each member is at most 64 KiB"""
+    out, at = [], 0
+    while at < len(data):
+        xlen, bsize = struct.unpack_from("<H", data, at + 10)[0], struct.unpack_from("<H", data, at + 16)[0] + 1
+        assert bsize <= 65536 and data[at:at + 4] == b"\x1f\x8b\x08\x04"
+        d = zlib.decompressobj(-15)
+        raw = d.decompress(data[at + 12 + xlen:at + bsize - 8])
+        assert d.eof and not d.unused_data
+        crc, isize = struct.unpack_from("<II", data, at + bsize - 8)
+        assert zlib.crc32(raw) == crc and len(raw) == isize
+        out.append(raw)
+        at += bsize
+    assert at == len(data)
+    return out
 
 
 def checked_windows(ctx, result, m):

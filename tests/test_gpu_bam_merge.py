@@ -9,26 +9,9 @@ import pytest
 from tests import bam_merge_model as m
 from tests import bam_minimize_model as mm
 from tests import bam_subsample_model as sm
-from tests.bam_out_util import checked_windows
+from tests.bam_out_util import checked_windows, zlib_members
 
 pytestmark = pytest.mark.gpu
-
-
-def zlib_members(data):
-    """every BGZF member of data inflated by zlib itself, its CRC-32 and ISIZE checked; each member is at most 64 KiB"""
-    out, at = [], 0
-    while at < len(data):
-        xlen, bsize = struct.unpack_from("<H", data, at + 10)[0], struct.unpack_from("<H", data, at + 16)[0] + 1
-        assert bsize <= 65536 and data[at:at + 4] == b"\x1f\x8b\x08\x04"
-        d = zlib.decompressobj(-15)
-        raw = d.decompress(data[at + 12 + xlen:at + bsize - 8])
-        assert d.eof and not d.unused_data
-        crc, isize = struct.unpack_from("<II", data, at + bsize - 8)
-        assert zlib.crc32(raw) == crc and len(raw) == isize
-        out.append(raw)
-        at += bsize
-    assert at == len(data)
-    return out
 
 
 def write_all(d, files, **kw):
@@ -259,3 +242,33 @@ def test_the_ctx_is_left_as_found(ctx, inputs, tmp_path):
     res = ctx.bam_file_merge(paths[:3], False, 1, 256)                                # and left with windows unread
     assert res[0] and next(ctx.bam_file_rewrite_windows())["bgzf"]
     assert others() == before
+
+
+def test_merge_scratch_in_the_first_compressed_files_buffer_or_its_own(ctx, tmp_path, monkeypatch, capfd):
+    """the sort's buffers and the columns (29 B per record of all inputs and the sort's own scratch) lie in the idle buffer of input 1's
+    compressed file when they fit, else in memory of their own; the placements arise from the files.  Inputs of 3 000 and 2 500 records,
+    input 1 under a header text of 4 MiB that does not compress: its buffer.  An input 1 of 300 records in front of the 2 500: memory
+    of its own, whatever the sort asks for on top.  (Input 1 under the default header takes 0.30 MB against 0.16 MB of scratch — its
+    records do not compress below that — so that pair alone never reaches the second placement; it is merged and compared all the
+    same.)  The model's output every time, with and without the suffix, whose input numbers stay in the call's own buffer throughout."""
+    import os
+    import random
+    rnd = random.Random(9)
+    text = b"@CO\t" + bytes(rnd.randrange(33, 127) for _ in range(4 << 20)) + b"\n"
+    files = m.served_inputs(2, [3000, 2500], seed=5)
+    few = m.served_inputs(2, [300, 1], seed=6)[0]
+    small, large, tiny, second = tmp_path / "small.bam", tmp_path / "large.bam", tmp_path / "tiny.bam", tmp_path / "second.bam"
+    raw_small, raw_large, raw_second = m.write(small, files[0]), m.write(large, files[0], text=text), m.write(second, files[1])
+    raw_tiny = m.write(tiny, few)
+    assert os.path.getsize(tiny) + 64 < 29 * (300 + 2500)                              # (input 1's buffer against the seven columns alone)
+    monkeypatch.setenv("SK_BAMFILE_TRACE", "1")
+    capfd.readouterr()
+    for first, raw_first, where in ((small, raw_small, None), (tiny, raw_tiny, "its own buffer"), (large, raw_large, "the first compressed file's buffer"),
+                                    (tiny, raw_tiny, "its own buffer")):
+        for suffix in (False, True):
+            check(ctx, [str(first), str(second)], [raw_first, raw_second], suffix)
+            lines = [ln for ln in capfd.readouterr().err.split("\n") if "bytes of scratch in" in ln]
+            assert len(lines) == 1 and lines[0].startswith("sk_bam_file_merge: 2 inputs, ")
+            print(lines[0])
+            if where:
+                assert lines[0].endswith("bytes of scratch in " + where)

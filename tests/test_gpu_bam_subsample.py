@@ -7,26 +7,9 @@ import pytest
 
 from tests import bam_minimize_model as mm
 from tests import bam_subsample_model as m
-from tests.bam_out_util import checked_windows
+from tests.bam_out_util import checked_windows, zlib_members
 
 pytestmark = pytest.mark.gpu
-
-
-def zlib_members(data):
-    """every BGZF member of data inflated by zlib itself, its CRC-32 and ISIZE checked; each member is at most 64 KiB"""
-    out, at = [], 0
-    while at < len(data):
-        xlen, bsize = struct.unpack_from("<H", data, at + 10)[0], struct.unpack_from("<H", data, at + 16)[0] + 1
-        assert bsize <= 65536 and data[at:at + 4] == b"\x1f\x8b\x08\x04"
-        d = zlib.decompressobj(-15)
-        raw = d.decompress(data[at + 12 + xlen:at + bsize - 8])
-        assert d.eof and not d.unused_data
-        crc, isize = struct.unpack_from("<II", data, at + bsize - 8)
-        assert zlib.crc32(raw) == crc and len(raw) == isize
-        out.append(raw)
-        at += bsize
-    assert at == len(data)
-    return out
 
 
 def collect(ctx, path, fraction, seed, level=1, window_bytes=0):
@@ -231,3 +214,42 @@ def test_minimize_read_ids_before_and_after_on_the_same_ctx(ctx, tmp_path):
     raw = m.write(spath, recs)
     check(ctx, spath, raw, "0.5", 9)
     minimize()
+
+
+def test_subsample_scratch_in_the_compressed_files_buffer_or_its_own(ctx, tmp_path, monkeypatch, capfd):
+    """the sort's buffers and the record offsets (32 B per record and the sort's own scratch) lie in the idle buffer of the compressed
+    file when they fit, else in memory of their own; the placements arise from the files.  8 000 served records under a header text of
+    4 MiB that does not compress: the file's buffer.  8 000 records of 39 bytes, which compress to 5 bytes each: memory of its own,
+    whatever the sort asks for on top.  (The served records under the default header take 1.3 MB against 0.26 MB of scratch: their
+    own qualities do not compress, so that file alone never reaches the second placement; it is served and compared all the same.)
+    The model's output every time, also after another file has been read into that buffer."""
+    import os
+    import random
+    rnd = random.Random(9)
+    text = b"@CO\t" + bytes(rnd.randrange(33, 127) for _ in range(4 << 20)) + b"\n"
+    small, large, tiny, other = tmp_path / "small.bam", tmp_path / "large.bam", tmp_path / "tiny.bam", tmp_path / "other.bam"
+    recs = m.served_records(8000, seed=3)
+    raw_small, raw_large = m.write(small, recs), m.write(large, recs, text=text)
+    raw_tiny = m.write(tiny, [m.rm.record(b"s%d" % (i // 2), 0, flag=0x41 if i & 1 else 0x81, seed=i) for i in range(8000)])
+    assert os.path.getsize(tiny) + 64 < 32 * 8000                                      # (the file's buffer against the five columns alone)
+    raw_other = m.write(other, m.served_records(600, seed=7))
+    monkeypatch.setenv("SK_BAMFILE_TRACE", "1")
+    capfd.readouterr()
+
+    def placed():
+        lines = [ln for ln in capfd.readouterr().err.split("\n") if "bytes of scratch in" in ln]
+        assert len(lines) == 1 and lines[0].startswith("sk_bam_file_subsample: ")
+        print(lines[0])
+        return lines[0].split("bytes of scratch in ")[1]
+    check(ctx, small, raw_small, "0.5", 1)
+    placed()
+    check(ctx, tiny, raw_tiny, "0.5", 1)
+    assert placed() == "its own buffer"
+    check(ctx, large, raw_large, "0.5", 1)
+    assert placed() == "the compressed file's buffer"
+    check(ctx, other, raw_other, "0.5", 2)
+    placed()
+    check(ctx, large, raw_large, "0.5", 1, window_bytes=64 << 10)
+    assert placed() == "the compressed file's buffer"
+    check(ctx, tiny, raw_tiny, "0.9", 3)
+    assert placed() == "its own buffer"
