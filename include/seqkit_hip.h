@@ -400,6 +400,35 @@ int sk_bam_file_reads(sk_ctx *ctx, const char *path, int format /* 0 raw, 1 fast
                       int *handled, double info[8]);
 int sk_bam_file_reads_next(sk_ctx *ctx, sk_bam_reads_window *w);
 
+/* ---- `sam to`, the mates paired on the device and the texts in output order (src/sam_to_fastq.rs:100-137) -----------------------
+ * sk_bam_file_pairs: what sk_bam_file_reads does up to the kept records (same files, same records kept with want_unpaired =
+ * !interleaved, same texts, same *handled = 0 cases), then the loop of :113-137 over them on the device.  Per name, in file order, a
+ * first mate (0x40; kind 1) whose name has a pending last mate completes a pair, else it becomes the pending first mate of its name,
+ * REPLACING one that is pending (the record replaced is written nowhere); a last mate (0x80 alone; kind 2) mirrors that.  Stream 1 and
+ * stream 2 hold the first and the last mate of every pair, the pairs in the order of the records that completed them.  The single
+ * stream holds the unpaired records in file order, then the first mates still pending at the end, then the last mates still pending,
+ * each in the order their names became pending (the reference's order there is arbitrary).  interleaved != 0: one stream, stream 1,
+ * with the two mates of pair p adjacent, the first mate first; unpaired records are not kept and pending ones are written nowhere.
+ * counts[8]: pairs, unpaired records kept, first mates pending at the end, last mates pending at the end, paired records replaced
+ * while pending, and the text bytes of stream 1, stream 2 and the single stream.  *handled = 0 also, before any text is written, when two different names have one 64-bit key (info[5] = -94; environment
+ * SK_PAIR_KEY_BITS = 1..64 cuts the key, for tests), when 2^32 records or more are kept, and when the working memory cannot be had:
+ * per kept record 33 B of columns, 12 B of permutation and offsets and 38 B of scratch (the scratch in the compressed file's device
+ * buffer where it fits; SK_PAIRS_OWN_MEMORY: never there), and the scratch of the sort and the scans.
+ * sk_bam_file_pairs_next: the next window; w->n == 0 at the end.  A window is a range of one stream's records: the windows of stream
+ * 1 come first, then stream 2's, then the single stream's, and each stream's windows' bytes back to back are that output.  window_bytes
+ * (0: 64 MiB) bounds a window's text (a single record may go beyond it).  The HOST text (the ctx's, page-locked) holds until the next
+ * call on the ctx; the device writes and copies the following window while the caller writes this one.  Calling it after another
+ * sk_bam_file_* call, or without sk_bam_file_pairs: SK_ERR_INVALID.                                                             */
+typedef struct sk_bam_pairs_window {
+	int32_t stream;                /* 0 stream 1 (interleaved: both mates), 1 stream 2, 2 the single stream */
+	int64_t first, n;              /* the stream's records first .. first + n - 1; n == 0: the end */
+	const uint8_t *text;           /* HOST, page-locked: their texts back to back */
+	uint64_t bytes;
+} sk_bam_pairs_window;
+int sk_bam_file_pairs(sk_ctx *ctx, const char *path, int format /* 0 raw, 1 fasta, 2 fastq */, uint8_t min_baseq, int interleaved,
+                      uint64_t window_bytes /* 0 = default */, uint64_t counts[8], int *handled, double info[8]);
+int sk_bam_file_pairs_next(sk_ctx *ctx, sk_bam_pairs_window *w);
+
 /* ---- BAM out for `sam trim qnames`, `sam tags from qname`, `sam qname from tags` (src/sam_trim_qnames.rs:20-30,
  * src/sam_tags_from_qname.rs:33-52, src/sam_qname_from_tags.rs:32-41) ------------------------------------------------------
  * sk_bam_file_rewrite: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0

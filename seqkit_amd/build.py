@@ -17,7 +17,7 @@ LIBDIR = os.path.join(ROOT, "lib")
 BINDIR = os.path.join(ROOT, "bin")
 LIB_PATH = os.path.join(LIBDIR, "libseqkit_hip.so")
 
-HIP_SOURCES = ["sk_kernels.hip", "sk_census.hip", "sk_inflate.hip", "sk_deflate.hip", "sk_bamtext.hip", "sk_bamwrite.hip", "sk_bamminimize.hip", "sk_bammarkdup.hip", "sk_bamsubsample.hip", "sk_bammerge.hip", "sk_bamcoverage.hip", "sk_capi.hip", "sk_bamfile.cpp", "sk_bamfile_reads.cpp", "sk_bamfile_out.cpp", "sk_bamfile_coverage.cpp", "sk_lut.cpp"]
+HIP_SOURCES = ["sk_kernels.hip", "sk_census.hip", "sk_inflate.hip", "sk_deflate.hip", "sk_bamtext.hip", "sk_bamwrite.hip", "sk_bamminimize.hip", "sk_bammarkdup.hip", "sk_bamsubsample.hip", "sk_bammerge.hip", "sk_bamcoverage.hip", "sk_bampair.hip", "sk_capi.hip", "sk_bamfile.cpp", "sk_bamfile_reads.cpp", "sk_bamfile_out.cpp", "sk_bamfile_coverage.cpp", "sk_lut.cpp"]
 HIP_DEPS = HIP_SOURCES + ["sk_internal.h", "sk_lut.h", "sk_bamblock.h", "sk_bamfmt.h", "sk_bamfile.h", "sk_passmem.h", os.path.join(REPO, "include", "seqkit_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
@@ -81,7 +81,7 @@ def build_hosts(force: bool = False) -> list[str]:
         if not all(os.path.exists(os.path.join(CSRC, s)) for s in srcs):
             continue
         target = os.path.join(BINDIR, name)
-        deps = srcs + ["host_common.h", "sk_bamfmt.h", os.path.join(REPO, "include", "seqkit_hip.h"), LIB_PATH]
+        deps = srcs + ["host_common.h", "sam_pairing.h", "sk_bamfmt.h", os.path.join(REPO, "include", "seqkit_hip.h"), LIB_PATH]
         if force or _stale(target, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I", os.path.join(REPO, "include"),
                    "-o", target] + srcs + ["-L", LIBDIR, "-lseqkit_hip", "-Wl,-rpath,$ORIGIN/../lib"] + libs

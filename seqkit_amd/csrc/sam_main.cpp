@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "host_common.h"
+#include "sam_pairing.h"
 #include "sk_bamfmt.h"
 
 using bamfmt::le32;
@@ -806,120 +807,44 @@ struct PendingReads {
 static ReadSink g_sinks[3];
 static void close_sinks() { for (auto &s : g_sinks) if (s.gz) s.gz->close(); }
 
-// PendingReads over the device path's records: a flat open-addressing table keyed by the device's 64-bit qname key (names compared
-// byte for byte on a key match), the pending names and texts in an arena that is compacted when most of it is dead.  Same semantics:
-// a second insert under a name replaces the text and keeps its order; after a removal a new insert takes a new order number.
-struct PendingTexts {
-	struct Slot { uint64_t key, order, at; uint32_t name_len, text_len; bool used; };
-	std::vector<Slot> slots = std::vector<Slot>(1024);
-	size_t count = 0;
-	uint64_t next = 0, live = 0;
-	std::vector<char> arena;                                        // name then text, per entry
-	size_t mask() const { return slots.size() - 1; }
-	int64_t find(uint64_t key, const uint8_t *name, uint32_t len) const
-	{
-		for (size_t i = key & mask();; i = (i + 1) & mask()) {
-			const Slot &e = slots[i];
-			if (!e.used) return -1;
-			if (e.key == key && e.name_len == len && memcmp(arena.data() + e.at, name, len) == 0) return (int64_t)i;
-		}
-	}
-	const char *text(const Slot &e) const { return arena.data() + e.at + e.name_len; }
-	void put(Slot &e, const uint8_t *name, uint32_t len, const uint8_t *t, uint32_t tl)
-	{
-		e.at = arena.size(); e.name_len = len; e.text_len = tl;
-		arena.insert(arena.end(), name, name + len);
-		arena.insert(arena.end(), t, t + tl);
-		live += (uint64_t)len + tl;
-	}
-	void insert(uint64_t key, const uint8_t *name, uint32_t len, const uint8_t *t, uint32_t tl)
-	{
-		const int64_t f = find(key, name, len);
-		if (f >= 0) { Slot &e = slots[(size_t)f]; live -= (uint64_t)e.name_len + e.text_len; put(e, name, len, t, tl); }
-		else {
-			if ((count + 1) * 2 > slots.size()) grow();
-			size_t i = key & mask();
-			while (slots[i].used) i = (i + 1) & mask();
-			Slot &e = slots[i];
-			e.used = true; e.key = key; e.order = next++;
-			put(e, name, len, t, tl);
-			count++;
-		}
-		if (arena.size() > ((size_t)64 << 20) && arena.size() > 4 * live) compact();
-	}
-	void erase(size_t i)                                            // backward-shift deletion (linear probing)
-	{
-		live -= (uint64_t)slots[i].name_len + slots[i].text_len;
-		slots[i].used = false;
-		count--;
-		for (size_t j = (i + 1) & mask(); slots[j].used; j = (j + 1) & mask()) {
-			const size_t home = slots[j].key & mask();
-			// slot j may move to the hole at i when its home does not lie cyclically in (i, j]
-			if (((j - home) & mask()) >= ((j - i) & mask())) { slots[i] = slots[j]; slots[j].used = false; i = j; }
-		}
-	}
-	void grow()
-	{
-		std::vector<Slot> old(slots.size() * 2);
-		old.swap(slots);
-		for (const Slot &e : old)
-			if (e.used) { size_t i = e.key & mask(); while (slots[i].used) i = (i + 1) & mask(); slots[i] = e; }
-	}
-	void compact()
-	{
-		std::vector<char> a;
-		a.reserve((size_t)live + (1 << 20));
-		for (Slot &e : slots)
-			if (e.used) { const uint64_t at = a.size(); a.insert(a.end(), arena.begin() + (ptrdiff_t)e.at, arena.begin() + (ptrdiff_t)(e.at + e.name_len + e.text_len)); e.at = at; }
-		arena.swap(a);
-	}
-	std::vector<const Slot *> in_order() const
-	{
-		std::vector<const Slot *> v;
-		v.reserve(count);
-		for (const Slot &e : slots) if (e.used) v.push_back(&e);
-		std::sort(v.begin(), v.end(), [](const Slot *a, const Slot *b) { return a->order < b->order; });
-		return v;
-	}
-};
+// Where the mates of `sam to` are paired when the device serves the file: SEQKIT_HOST_PAIRING=1 on the host, SEQKIT_DEVICE_PAIRING=1 on
+// the device, else kDevicePairingDefault (what was measured, and the rule the default follows).
+static const bool kDevicePairingDefault = false;
+static bool device_pairing_wanted()
+{
+	if (getenv("SEQKIT_HOST_PAIRING")) return false;
+	if (getenv("SEQKIT_DEVICE_PAIRING")) return true;
+	return kDevicePairingDefault;
+}
 
-// sam to over the FILE: the device inflates, walks and sizes it, and writes every kept record's text (sk_bam_file_reads); the mate
-// pairing of :114-137 runs here over the windows, in file order.  -1: nothing has been written, and the caller's reader serves the
-// file (one the file path does not take, a device without room, or a record the reference would panic or stop at).  Otherwise the
-// number of records in the file.
+// sam to over the FILE.  The device inflates, walks and sizes it, pairs the mates (:113-137) and writes the texts in the order they
+// leave (sk_bam_file_pairs): this host writes each window to its sink.  SEQKIT_HOST_PAIRING=1, and every file that call declines (two
+// names under one key: info[5] = -94; no room for its working memory: -21), take the path before it: the device writes every kept record's text in file
+// order (sk_bam_file_reads) and the pairing runs here over the windows (sam_pairing.h: pair_on_host).  -1: nothing has been written, and
+// the caller's reader serves the file (one the file path does not take, a device without room, or a record the reference would panic or
+// stop at).  Otherwise the number of records in the file.
 static int64_t to_reads_from_file(const std::string &path, OutFmt format, bool interleaved, ReadSink &out_1, ReadSink &out_2, ReadSink &out_single)
 {
 	sk_ctx *c = host::gpu();
-	int64_t n_kept = 0;
-	uint64_t text_bytes = 0;
 	int handled = 0;
 	double info[8];
 	const int fmt = format == OutFmt::RAW ? 0 : format == OutFmt::FASTA ? 1 : 2;
-	if (sk_bam_file_reads(c, path.c_str(), fmt, 10 /* :103 */, interleaved ? 0 : 1, file_window_bytes(), &n_kept, &text_bytes, &handled, info) != SK_OK || !handled) return -1;
-	PendingTexts reads_1, reads_2;
-	sk_bam_reads_window w;
-	for (;;) {
-		check(sk_bam_file_reads_next(c, &w), "sk_bam_file_reads_next");
-		if (w.n == 0) break;
-		for (int64_t j = 0; j < w.n; j++) {
-			const char *t = reinterpret_cast<const char *>(w.text + w.text_off[j]);
-			const uint32_t tl = (uint32_t)(w.text_off[j + 1] - w.text_off[j]);
-			const uint8_t kind = w.kind[j];
-			if (kind == 0) { out_single.write(t, tl); continue; }                                                // :114-115
-			const uint8_t *nm = w.names + w.name_off[j];
-			const uint32_t nl = w.name_off[j + 1] - w.name_off[j];
-			PendingTexts &mates = kind == 1 ? reads_2 : reads_1, &mine = kind == 1 ? reads_1 : reads_2;      // :116-130
-			const int64_t f = mates.find(w.key[j], nm, nl);
-			if (f >= 0) {
-				const PendingTexts::Slot &e = mates.slots[(size_t)f];
-				if (kind == 1) { out_1.write(t, tl); out_2.write(mates.text(e), e.text_len); }
-				else { out_1.write(mates.text(e), e.text_len); out_2.write(t, tl); }
-				mates.erase((size_t)f);
-			} else mine.insert(w.key[j], nm, nl, reinterpret_cast<const uint8_t *>(t), tl);
+	ReadSink *sinks[3] = {&out_1, &out_2, &out_single};
+	auto write = [&](int stream, const char *p, size_t n) { sinks[stream]->write(p, n); };
+	if (device_pairing_wanted()) {
+		uint64_t counts[8];
+		if (sk_bam_file_pairs(c, path.c_str(), fmt, 10 /* :103 */, interleaved ? 1 : 0, file_window_bytes(), counts, &handled, info) == SK_OK && handled) {
+			if (bamfile_trace()) fprintf(stderr, "sam to pairing: device\n");
+			pairing::write_pair_windows([&](sk_bam_pairs_window *w) { check(sk_bam_file_pairs_next(c, w), "sk_bam_file_pairs_next"); }, write);
+			return (int64_t)info[3];
 		}
+		if (info[5] != -94.0 && info[5] != -21.0) return -1;            // (declined as sk_bam_file_reads would: not inflated a second time)
 	}
-	for (const PendingTexts *m : {&reads_1, &reads_2})                                                          // :133-137
-		for (const PendingTexts::Slot *e : m->in_order()) out_single.write(m->text(*e), e->text_len);
+	int64_t n_kept = 0;
+	uint64_t text_bytes = 0;
+	if (sk_bam_file_reads(c, path.c_str(), fmt, 10 /* :103 */, interleaved ? 0 : 1, file_window_bytes(), &n_kept, &text_bytes, &handled, info) != SK_OK || !handled) return -1;
+	if (bamfile_trace()) fprintf(stderr, "sam to pairing: host\n");
+	pairing::pair_on_host([&](sk_bam_reads_window *w) { check(sk_bam_file_reads_next(c, w), "sk_bam_file_reads_next"); }, write);
 	return (int64_t)info[3];
 }
 

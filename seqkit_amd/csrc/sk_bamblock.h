@@ -1,7 +1,8 @@
 // sk_bamblock.h — what the per-block passes over a verified BAM stream share (sk_inflate.hip: bam_gather_kernel; sk_bamtext.hip: the
 // reads passes; sk_bamwrite.hip: the rewrite passes; sk_bamminimize.hip: the minimize passes).  Such a pass is a wave per BGZF block:
 // lane 0 follows the chain of records from the block's entry to its end and leaves every record's offset in LDS, then the 64 lanes
-// take consecutive records.  Also the name hash (reads, minimize) and the span copy of the window writers (rewrite, pack, minimize).
+// take consecutive records.  Also the name hash (reads, minimize), the byte composition of `sam to`'s texts (sk_bamtext.hip,
+// sk_bampair.hip) and the span copy of the window writers (rewrite, pack, minimize).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,6 +69,33 @@ __device__ __forceinline__ unsigned long long qname_key(const uint8_t *p, uint32
 	for (uint32_t k = 0; k < n; k++) h = (h ^ p[k]) * 0x100000001b3ull;
 	h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
 	return h;
+}
+
+// byte p of a kept record's text in `sam to` (sk_bamtext.hip, sk_bampair.hip: write_read, src/sam_to_fastq.rs:138-149; SEQ as sequence(), :31-59)
+__device__ __forceinline__ uint32_t reads_byte(uint32_t p, int fmt, const uint8_t *name, uint32_t L, const uint8_t *seq4, const uint8_t *qual, uint32_t S,
+                                               bool rev, uint32_t min_baseq)
+{
+	if (fmt != 0) {
+		if (p == 0u) return fmt == 2 ? '@' : '>';
+		if (p <= L) return name[p - 1u];
+		if (p == L + 1u) return '\n';
+		p -= L + 2u;
+	}
+	if (p < S) {
+		const uint32_t s = rev ? S - 1u - p : p;
+		if (qual[s] < min_baseq) return 'N';
+		const uint32_t code = (seq4[s >> 1] >> ((s & 1u) ? 0 : 4)) & 15u;
+		// 1 2 4 8 -> A C G T (reverse strand: T G C A), anything else N
+		const uint32_t fw = code == 1u ? 'A' : code == 2u ? 'C' : code == 4u ? 'G' : code == 8u ? 'T' : 'N';
+		if (!rev) return fw;
+		return fw == 'A' ? 'T' : fw == 'C' ? 'G' : fw == 'G' ? 'C' : fw == 'T' ? 'A' : 'N';
+	}
+	if (p == S || fmt != 2) return '\n';
+	if (p == S + 1u) return '+';
+	if (p == S + 2u) return '\n';
+	p -= S + 3u;
+	if (p < S) return (uint8_t)(33u + qual[p]);
+	return '\n';
 }
 
 // out[o0 .. o0 + len) by `nl` lanes from lane `lane` on: the bytes in [ro0, ro0 + rl0), [ro1, ro1 + rl1) and [ro2, ro2 + rl2) (relative

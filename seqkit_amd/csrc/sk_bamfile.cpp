@@ -160,13 +160,14 @@ int bamfile::bam_file_front(sk_ctx *c, const char *path, Cleanup &cl, Front &fr,
 	// an earlier sk_bam_file_reads may have left a window in flight on the ctx stream: its text kernel reads the inflated stream and its
 	// copies write the page-locked window buffers.  It ends before this call remaps the ranges or takes the kept buffers again.
 	// (the same for an sk_bam_file_rewrite, _minimize or _markdup, whose window copies run on the second stream)
-	if (both->reads.busy() || both->rw.busy()) {
+	if (both->reads.busy() || both->rw.busy() || both->pairs.busy()) {
 		BF_HIP(hipStreamSynchronize(sk::ctx_stream(c)));
 		BF_HIP(hipStreamSynchronize(sk::ctx_stream2(c)));
 	}
 	both->gen++;                                                        // (what an earlier windowed call left is no longer read)
 	both->reads.stop();
 	both->rw.stop();
+	both->pairs.stop();
 	cl.fd = open(path, O_RDONLY);
 	if (cl.fd < 0) BF_LEAVE(1);                                        // (the caller's reader says so in the reference's words)
 	struct stat sb;

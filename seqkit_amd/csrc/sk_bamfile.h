@@ -153,6 +153,23 @@ struct ReadsState : WindowedState {
 	size_t at_toff = 0, at_noff = 0, at_names = 0, at_kind = 0, at_key = 0;   // a window buffer's layout (text at 0)
 };
 
+// sk_bam_file_pairs / sk_bam_file_pairs_next (`sam to`, the texts in output order): the kept records' stream offsets (device, ctx slot
+// kKeepFileCols), every stream's permutation rank -> record and stream offsets (device, the kept head of ctx slot kKeepPassWork; stream s
+// from entry base[s] + s on), the windows of all streams in the order they are returned — stream 1's, stream 2's, the single stream's —
+// and two text buffers on each side (ctx slots kKeepFileWin / kKeepFilePin).  (ws / next_window of the base are not used: a window here
+// is a rank range of ONE stream.)
+struct PairsState : WindowedState {
+	int fmt = 0;
+	uint8_t min_baseq = 10;
+	const uint64_t *krec = nullptr, *soff = nullptr;
+	const uint32_t *perm = nullptr;
+	uint64_t base[3] = {0, 0, 0};
+	struct Window { int stream; uint64_t first, n, bytes; };
+	std::vector<Window> plan;
+	uint8_t *d_win[2] = {nullptr, nullptr}, *h_win[2] = {nullptr, nullptr};
+	Window in[2] = {};                           // the window in buffer b
+};
+
 // Which of the rewrite-window calls is running — the kernel that writes a window's records — and what that kernel takes
 struct WriteOp {
 	enum Kind { kRewrite, kMinimize, kMarkdup, kSubsample, kMerge } kind = kRewrite;
@@ -188,8 +205,9 @@ struct Ranges {
 	OutRange comp, out;
 	std::vector<uint8_t> header;                 // sk_bam_file_columns: the last file's header bytes (cols->header)
 	uint64_t gen = 0;                            // file calls so far: a reads state of an earlier call is stale
-	ReadsState reads;                            // (only one of the two is live: the next file call, windowed or not, ends either)
+	ReadsState reads;                            // (only one of the three is live: the next file call, windowed or not, ends each)
 	RewriteState rw;
+	PairsState pairs;
 	std::vector<sk_ctx *> helpers;               // sk_bam_file_merge: one context per further input, whose front half keeps that input's stream
 	static void destroy(void *p)
 	{

@@ -390,33 +390,6 @@ struct ReadsText {
 	uint32_t *noff;
 };
 
-// byte p of a record's text (write_read, src/sam_to_fastq.rs:138-149; SEQ as sequence(), :31-59)
-__device__ __forceinline__ uint32_t reads_byte(uint32_t p, int fmt, const uint8_t *name, uint32_t L, const uint8_t *seq4, const uint8_t *qual, uint32_t S,
-                                               bool rev, uint32_t min_baseq)
-{
-	if (fmt != 0) {
-		if (p == 0u) return fmt == 2 ? '@' : '>';
-		if (p <= L) return name[p - 1u];
-		if (p == L + 1u) return '\n';
-		p -= L + 2u;
-	}
-	if (p < S) {
-		const uint32_t s = rev ? S - 1u - p : p;
-		if (qual[s] < min_baseq) return 'N';
-		const uint32_t code = (seq4[s >> 1] >> ((s & 1u) ? 0 : 4)) & 15u;
-		// 1 2 4 8 -> A C G T (reverse strand: T G C A), anything else N
-		const uint32_t fw = code == 1u ? 'A' : code == 2u ? 'C' : code == 4u ? 'G' : code == 8u ? 'T' : 'N';
-		if (!rev) return fw;
-		return fw == 'A' ? 'T' : fw == 'C' ? 'G' : fw == 'G' ? 'C' : fw == 'T' ? 'A' : 'N';
-	}
-	if (p == S || fmt != 2) return '\n';
-	if (p == S + 1u) return '+';
-	if (p == S + 2u) return '\n';
-	p -= S + 3u;
-	if (p < S) return (uint8_t)(33u + qual[p]);
-	return '\n';
-}
-
 constexpr int kTextThreads = 256;
 __global__ __launch_bounds__(kTextThreads) void bam_reads_text_kernel(const ReadsText a)
 {

@@ -288,6 +288,38 @@ hipError_t launch_bam_merge_gather(const uint32_t *idx, const MergeCols &cols, u
 hipError_t bam_merge_scan(void *temp, size_t *temp_bytes, uint64_t *kout, uint64_t n, hipStream_t st);
 hipError_t launch_bam_merge_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint8_t *kin, int64_t first, int64_t n, uint64_t o0,
                                   uint8_t *out, int n_cu, hipStream_t st);
+// ---- sam to: the mate pairing of sk_bam_file_pairs and its windows' text (sk_bampair.hip) ----
+// Over the K kept records of launch_bam_reads_index (file order; kind 0 unpaired, 1 first, 2 last mate).  A record's fate: where its text
+// goes; aux: for a record of a pair the kept index of the record that COMPLETED the pair, for a leftover its order record.  Its class: what
+// it counts as in the scan of the ranks (one class at most).
+constexpr int kPairBlock = 256;                  // the workgroup of every pairing kernel: one sorted position or kept record per lane
+constexpr uint8_t kPairSingle = 0, kPairStream1 = 1, kPairStream2 = 2, kPairLeft1 = 3, kPairLeft2 = 4, kPairNowhere = 5;
+constexpr uint8_t kPairClsNone = 0, kPairClsSingle = 1, kPairClsCompleter = 2, kPairClsOrder1 = 3, kPairClsOrder2 = 4;
+struct PairRanks { uint32_t single, pair, order1, order2; };
+// scan_bytes: the scratch every scan below takes over n elements.  scan_paired: ipos[k] = the paired records among 0 .. k.  compact: the
+// paired records' (key cut to key_bits, index) at ipos - 1, every record's initial fate, aux and class.  [bam_sort_pairs.]  heads: lz[p] = p
+// where sorted position p begins a run of one key or follows a record of its own kind, else 0; decline bit 64: two names under one key.
+// scan_max (in place): lz[p] = the last such position.  holds, scan_max: hs[p] = where the stretch of held records around p begins.
+// fates: fate, aux, class.  scan_ranks: per class the records among 0 .. k.  place: stream s's n[s] records into perm / slen from entry
+// base[s] + s on (slen: n[s] + 1 entries, the last one 0); interleaved: stream 0 holds both mates of pair p at 2 p, 2 p + 1, streams 1 and 2
+// nothing.  scan_offsets (in place): the text lengths to stream offsets.  text: ranks first .. first + n - 1 of one stream into text.
+hipError_t bam_pair_scan_bytes(uint64_t n, size_t *temp_bytes, hipStream_t st);
+hipError_t bam_pair_scan_paired(void *temp, size_t temp_bytes, const uint8_t *kkind, uint32_t *ipos, uint64_t n, hipStream_t st);
+hipError_t bam_pair_scan_max(void *temp, size_t temp_bytes, uint32_t *v, uint64_t n, hipStream_t st);
+hipError_t bam_pair_scan_ranks(void *temp, size_t temp_bytes, const uint8_t *cls, PairRanks *ranks, uint64_t n, hipStream_t st);
+hipError_t bam_pair_scan_offsets(void *temp, size_t temp_bytes, uint64_t *lens, uint64_t n, hipStream_t st);
+hipError_t launch_bam_pair_compact(const uint8_t *kkind, const uint64_t *kkey, const uint32_t *ipos, uint64_t K, int key_bits, uint64_t *key, uint32_t *idx,
+                                   uint8_t *fate, uint32_t *aux, uint8_t *cls, hipStream_t st);
+hipError_t launch_bam_pair_heads(const uint8_t *stream, const uint64_t *krec, const uint8_t *kkind, const uint64_t *key, const uint32_t *idx, uint64_t P,
+                                 uint32_t *lz, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_pair_holds(const uint64_t *key, const uint32_t *lz, uint64_t P, uint32_t *hs, hipStream_t st);
+hipError_t launch_bam_pair_fates(const uint64_t *key, const uint32_t *idx, const uint8_t *kkind, const uint32_t *lz, const uint32_t *hs, uint64_t P,
+                                 uint8_t *fate, uint32_t *aux, uint8_t *cls, hipStream_t st);
+hipError_t launch_bam_pair_place(const uint8_t *fate, const uint32_t *aux, const PairRanks *ranks, const uint64_t *ktoff, uint64_t K, uint64_t T,
+                                 const uint64_t n[3], const uint64_t base[3], uint32_t n_single, uint32_t n_left1, int interleaved, uint32_t *perm,
+                                 uint64_t *slen, hipStream_t st);
+hipError_t launch_bam_pair_text(const uint8_t *stream, const uint64_t *krec, const uint32_t *perm, const uint64_t *soff, int64_t first, int64_t n, int fmt,
+                                uint8_t min_baseq, uint8_t *text, int n_cu, hipStream_t st);
 // ---- sam coverage histogram: the record passes of sk_bam_file_coverage (sk_bamcoverage.hip) ----
 // What the two record passes take (all device memory).  base[r] = the global coordinate of reference r's position 0, base[n_ref] the
 // total.  ioff == nullptr: no intervals; else reference r's merged, sorted, disjoint intervals are [ibeg[k], iend[k]) for k in

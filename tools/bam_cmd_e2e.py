@@ -13,7 +13,14 @@ write that row's file to PATH; with --human the one under the human-sized header
 [--subsample: only the `sam subsample` rows, see below] [--yardstick-sam=PATH: with --subsample, another build's `sam` (the parent
 commit's) whose `trim qnames` is the yardstick row instead of this build's] [--subsample-file=PATH: only write that row's file to
 PATH, for a profiler run of the command] [--merge: only the `sam merge` rows, see below] [--merge-files=DIR: only write the undealt file
-and the parts to DIR (in.bam, p2_0.bam .., p8_0.bam ..), for a profiler run of the command]
+and the parts to DIR (in.bam, p2_0.bam .., p8_0.bam ..), for a profiler run of the command] [--pairing: only the `sam to` pairing rows,
+see below] [--pairing-file=PATH: only write that row's file to PATH, for a profiler run of the command]
+
+--pairing: the fragments file (name-sorted in effect: mates adjacent).  Rows: `sam to interleaved fastq` to /dev/null and, without
+--no-gz, `sam to fastq <prefix>` to files, each with the mates paired on the device (SEQKIT_DEVICE_PAIRING=1), paired on the host over the device's
+texts (SEQKIT_HOST_PAIRING=1) and, with --yardstick-sam, by another build's `sam` (the parent commit's), alternating.  Wall and CPU-seconds
+of every run, each row's spread (max - min), and default / yardstick run for run.  The .gz files of the first run of every row are
+compared decompressed.  Then sk_bam_file_pairs' library-call time and its windows drained, next to sk_bam_file_reads'.
 
 --merge: the subsample file, and its records dealt alternately (record j of a repeat to part j mod P) into P = 2 and P = 8 position-
 sorted parts.  Mates share a position, so every key occurs in two parts: with ties by input the merge writes the undealt file's records
@@ -75,6 +82,8 @@ human = "--human" in sys.argv
 coverage_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--coverage-file=")), None)
 subsample_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--subsample-file=")), None)
 merge = "--merge" in sys.argv
+pairing = "--pairing" in sys.argv
+pairing_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--pairing-file=")), None)
 merge_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--merge-files=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -240,6 +249,38 @@ def compare(label, args):
 
 
 n = reps * 2 * PAIRS
+
+
+def pairing_rows():
+    variants = [("device pairing", SAM, {"SEQKIT_DEVICE_PAIRING": "1"}), ("host pairing  ", SAM, {"SEQKIT_HOST_PAIRING": "1"})]
+    if yardstick_sam:
+        variants.append(("yardstick     ", yardstick_sam, None))
+    modes = [("sam to interleaved fastq >/dev/null", ["to", "interleaved", "fastq", bam], None)]
+    if not no_gz:
+        modes.append(("sam to fastq <prefix>", ["to", "fastq", bam, os.path.join(d, "o")], os.path.join(d, "o")))
+    for label, args, prefix in modes:
+        rows, seen = {}, set()
+        for k in range(runs):
+            for name, binary, env in variants:
+                dt, cpu, rc, _, err = timed([binary] + args, env, sink=os.devnull)
+                assert rc == 0, (label, name, rc, err[-400:])
+                rows.setdefault(name, []).append((dt, cpu))
+                if prefix:
+                    h = gz_digest(prefix)
+                    if k == 0:
+                        seen.add(h)
+        assert len(seen) <= 1, f"{label}: outputs differ: {seen}"
+        for name, r in rows.items():
+            w = [x[0] for x in r]
+            print(f"{label:36s} {name} wall median {float(np.median(w)):5.2f} s, max - min {max(w) - min(w):.2f} s, CPU median "
+                  f"{float(np.median([x[1] for x in r])):5.2f} s   " + " ".join(f"{dt:.2f}/{cpu:.1f}" for dt, cpu in r), flush=True)
+        if yardstick_sam:
+            a, b = [x[0] for x in rows["device pairing"]], [x[0] for x in rows["yardstick     "]]
+            print(f"{label:36s} device pairing / yardstick, run for run: " + " ".join(f"{x / y:.2f}x" for x, y in zip(a, b))
+                  + f"; medians {float(np.median(a)) / float(np.median(b)):.2f}x; median difference {float(np.median(b)) - float(np.median(a)):+.2f} s "
+                  f"against the yardstick's max - min {max(b) - min(b):.2f} s" + ("; decompressed outputs identical" if prefix else ""), flush=True)
+    tr = subprocess.run([SAM, "to", "interleaved", "fastq", bam], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, env=dict(os.environ, SK_BAMFILE_TRACE="1")).stderr
+    print("trace of the default: " + str([ln for ln in tr.decode(errors="replace").split("\n") if ln.startswith("sam ")]), flush=True)
 
 
 def write_count_file(path, n_ref=None, l_ref=1 << 28):
@@ -498,7 +539,14 @@ with open(bam, "wb") as f:
         f.write(body)
     f.write(bgzf(b""))
 print(f"fragments file: {n} BAM records, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; {runs} runs per path", flush=True)
-if not lib_only:
+if pairing_file is not None:
+    os.replace(bam, pairing_file)
+    print(f"wrote {pairing_file}", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if pairing and not lib_only:
+    pairing_rows()
+if not lib_only and not pairing:
     compare("sam fragments", ["fragments", bam])
     compare_to("sam to interleaved fastq", ["to", "interleaved", "fastq", bam])
     compare_to("sam to interleaved fastq >/dev/null", ["to", "interleaved", "fastq", bam], sink=os.devnull)
@@ -538,8 +586,24 @@ with seqkit_amd.Context(0) as ctx:
     assert h
     print(f"library call, {n} records: sk_bam_file_reads (fastq) {1e3 * (t1 - t0):.0f} ms, {kept} kept, {tb / 1e9:.2f} GB of text; "
           f"{nw} windows drained in {1e3 * (t2 - t1):.0f} ms", flush=True)
+    # sk_bam_file_pairs (fastq, interleaved and not) and its windows: the device side of `sam to fastq` with the mates paired there
+    for inter in (True, False):
+        t0 = time.perf_counter()
+        h, counts, _ = ctx.bam_file_pairs(bam, "fastq", 10, inter)
+        t1 = time.perf_counter()
+        pw = capi._PairsWindow()
+        nw = 0
+        while True:
+            ctx._check(ctx._lib.sk_bam_file_pairs_next(ctx._h, capi.C.byref(pw)), "sk_bam_file_pairs_next")
+            if pw.n == 0:
+                break
+            nw += 1
+        t2 = time.perf_counter()
+        assert h
+        print(f"library call, {n} records: sk_bam_file_pairs (fastq{', interleaved' if inter else ''}) {1e3 * (t1 - t0):.0f} ms, {counts[0]} pairs, "
+              f"{sum(counts[5:]) / 1e9:.2f} GB of text; {nw} windows drained in {1e3 * (t2 - t1):.0f} ms", flush=True)
 os.remove(bam)
-if lib_only:
+if lib_only or pairing:
     os.rmdir(d)
     sys.exit(0)
 
