@@ -280,7 +280,8 @@ int sk_allreduce_u64_dev(sk_ctx *ctx, uint64_t *buf, size_t count);
  * src/sam_fragment_lengths.rs:29-43 (hist[0..max_frag], *hist_total = records histogrammed).  Inputs
  * are the BAM fixed-core fields as SoA columns (flag@14, refID@0, next_refID@20, tlen@28 of the 32-byte
  * core).  Results are ADDED to the caller's arrays.  The --reads=N early stop (:42) is order dependent
- * and stays on the host.  counters or hist may be NULL to skip that half.                             */
+ * and stays on the host.  counters or hist may be NULL to skip that half.  The --on-target fragments
+ * (S2, :72-106) do not depend on record order: sk_on_target_add counts them, and these counters too. */
 int sk_bam_flag_tlen(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, const int32_t *mtid,
                      const int32_t *tlen, int64_t n, int32_t max_frag,
                      uint64_t counters[3], uint64_t *hist, uint64_t *hist_total);
@@ -643,6 +644,32 @@ int sk_count_get(sk_ctx *ctx, uint32_t *region_frags /* n_regions */);
  * aligned.                                                                                                                      */
 int sk_count_order_check_dev(sk_ctx *ctx, const uint16_t *flag, const uint8_t *mapq, const int32_t *tid, const int32_t *pos, int64_t n,
                              uint8_t min_mapq, int32_t n_ref, int64_t *first_stop, int *code);
+
+/* ---- S2: `sam statistics --on-target=BED` ------------------------------------------------------------------------
+ * src/sam_statistics.rs:63-106.  sk_on_target_set_regions loads the target regions grouped by BAM reference: regions of
+ * reference c are entries chr_off[c] .. chr_off[c+1]-1 of rstart/rend, 1-based inclusive in 64 bits as :44-47 keep them
+ * (start = BED column 2 + 1, end = BED column 3; end < start is taken as it is), in any order inside a group: they are
+ * sorted by start here (:51-53) and the running maximum of their ends is put beside them.  n_entries == 0 and references
+ * without a region are valid.  The six counters are cleared.  sk_on_target_add runs, for every record, S1 (:64-69, the
+ * predicates of sk_bam_flag_tlen) and S2: for a record that is neither secondary, supplementary nor unmapped — paired
+ * (0x1): dropped when the mate is unmapped (0x8), tid != next_refID, pos > next_pos, pos == next_pos without 0x40, or
+ * |tlen| > max_frag_len (:76-84), else start = pos + 1, end = start + |tlen| (:86-87); unpaired: start = pos + 1, end =
+ * cigar end_pos + 1 (:90-91); all in 64 bits.  Every such record is a fragment (:94), and an on-target one when a region
+ * of its reference has start <= r.end && end >= r.start.  The reference's walk over the sorted regions (:97-106) stops at
+ * the first hit and at the first region that starts behind `end`; with k = the regions with r.start <= end that is
+ * k > 0 && max(r.end of regions 0 .. k-1) >= start: one binary search, whatever the order of the records.  A fragment
+ * whose tid is not in [0, n_chr) — where the reference panics (:97) — is counted in out[5] and not looked up.
+ * Columns: flag, refID, next_refID, pos, next_pos, tlen of the BAM core and cigar end_pos (SK_COL_END); host columns of
+ * any alignment for sk_on_target_add, device columns of any alignment (16-byte aligned ones are read with wide loads)
+ * for the _dev form, which is asynchronous on the ctx stream.  Calls accumulate.  sk_on_target_get (synchronous):
+ * out = total_reads, aligned_reads, duplicate_reads, total_fragments, on_target_fragments, bad_tid_fragments.          */
+int sk_on_target_set_regions(sk_ctx *ctx, int n_chr, const int32_t *chr_off, const int64_t *rstart, const int64_t *rend,
+                             int64_t n_entries);
+int sk_on_target_add(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *pos,
+                     const int32_t *mpos, const int32_t *tlen, const int32_t *end_pos, int64_t n, int64_t max_frag_len);
+int sk_on_target_add_dev(sk_ctx *ctx, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *pos,
+                         const int32_t *mpos, const int32_t *tlen, const int32_t *end_pos, int64_t n, int64_t max_frag_len);
+int sk_on_target_get(sk_ctx *ctx, uint64_t out[6]);
 
 /* ---- `fasta gc content` ------------------------------------------------------------------------------------------
  * src/fasta_gc_content.rs:41-46.  sk_gc_set_genome copies the concatenated sequences to the device once (it stays

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
     "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_merge", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
+    "sk_on_target_set_regions", "sk_on_target_add", "sk_on_target_add_dev", "sk_on_target_get",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
     "sk_timer_start", "sk_timer_stop",
 ]
@@ -269,6 +270,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_count_add": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_uint8, C.c_uint32, i32, i32]),
         "sk_count_add_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_uint8, C.c_uint32, i32, i32]),
         "sk_count_get": (i32, [vp, vp]),
+        "sk_on_target_set_regions": (i32, [vp, i32, vp, vp, vp, i64]),
+        "sk_on_target_add": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
+        "sk_on_target_add_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
+        "sk_on_target_get": (i32, [vp, vp]),
         "sk_gc_set_genome": (i32, [vp, vp, i64]),
         "sk_gc_count": (i32, [vp, vp, vp, i64, vp, vp]),
         "sk_census_reset": (i32, [vp]),
@@ -817,6 +822,35 @@ class Context:
         out = np.zeros(max(self._n_regions, 1), dtype=np.uint32)
         self._check(self._lib.sk_count_get(self._h, _ptr(out)), "sk_count_get")
         return out[:self._n_regions]
+
+    # ---- S2: sam statistics --on-target -------------------------------------------------------
+    def on_target_set_regions(self, chr_off, rstart, rend) -> None:
+        """Target regions grouped by BAM reference (entries chr_off[c]..chr_off[c+1]-1 belong to reference c), 1-based inclusive,
+        any order inside a group; clears the six counters."""
+        chr_off = np.ascontiguousarray(chr_off, dtype=np.int32)
+        rstart = np.ascontiguousarray(rstart, dtype=np.int64)
+        rend = np.ascontiguousarray(rend, dtype=np.int64)
+        if len(rend) != len(rstart):
+            raise ValueError("rstart and rend must have one length")
+        self._check(self._lib.sk_on_target_set_regions(self._h, len(chr_off) - 1, _ptr(chr_off), _ptr(rstart), _ptr(rend), len(rstart)),
+                    "sk_on_target_set_regions")
+
+    def on_target_add(self, flag, tid, mtid, pos, mpos, tlen, end_pos, max_frag_len: int = 5000) -> None:
+        n = len(flag)
+        cols = [_vec(flag, np.uint16, n, "flag")]
+        for name, col in (("tid", tid), ("mtid", mtid), ("pos", pos), ("mpos", mpos), ("tlen", tlen), ("end_pos", end_pos)):
+            cols.append(_vec(col, np.int32, n, name))
+        self._check(self._lib.sk_on_target_add(self._h, *[_ptr(c) for c in cols], n, max_frag_len), "sk_on_target_add")
+
+    def on_target_add_dev(self, flag: int, tid: int, mtid: int, pos: int, mpos: int, tlen: int, end_pos: int, n: int,
+                          max_frag_len: int = 5000) -> None:
+        self._check(self._lib.sk_on_target_add_dev(self._h, flag, tid, mtid, pos, mpos, tlen, end_pos, n, max_frag_len), "sk_on_target_add_dev")
+
+    def on_target_get(self) -> np.ndarray:
+        """u64[6]: total_reads, aligned_reads, duplicate_reads, total_fragments, on_target_fragments, bad_tid_fragments."""
+        out = np.zeros(6, dtype=np.uint64)
+        self._check(self._lib.sk_on_target_get(self._h, _ptr(out)), "sk_on_target_get")
+        return out
 
     # ---- fasta gc content -------------------------------------------------------------------
     def gc_set_genome(self, genome) -> None:

@@ -9,10 +9,11 @@
 //
 // The reference reads BAM through rust-htslib; this host walks the BGZF/BAM container itself (SAMv1 §4.2: BGZF is a
 // series of gzip members; after the header every record is block_size:u32 + a 32-byte fixed core) and hands the core
-// columns flag / refID / next_refID / tlen to the device as SoA batches.  Order-dependent pieces stay here, as
-// SURVEY.md §8(e) lists them: the --reads=N early stop and the --on-target sweep (S2, not part of the device path).  A regular
+// columns flag / refID / next_refID / tlen to the device as SoA batches.  The one order-dependent piece stays here, as
+// SURVEY.md §8(e) lists it: the --reads=N early stop.  A regular
 // file is first offered to the device whole (sk_bam_file_reduce, sk_bam_file_columns): it inflates and walks it; `sam fragments`
-// and `sam count` then run their order checks and their text on the device too, and whatever is irregular falls back to the reader
+// and `sam count` then run their order checks and their text on the device too, `sam statistics --on-target` its fragment and
+// region test (S2: it does not depend on record order), and whatever is irregular falls back to the reader
 // here before anything has been written.  `sam to` takes the file the same way: the device writes every record's text, window by
 // window, and the mate pairing stays here.  The commands that write BAM to stdout (trim qnames, tags from qname, qname from tags, minimize,
 // mark duplicates, subsample, merge) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
@@ -342,6 +343,69 @@ static uint64_t file_window_bytes()
 // ---- sam statistics ----------------------------------------------------------------------------------------------
 struct Region { int64_t start, end; };
 
+// The target regions of every BAM reference (src/sam_statistics.rs:26-54), 1-based inclusive, sorted by start.  *overflow, where given:
+// a BED start of INT64_MAX, whose + 1 (:45) does not fit.
+static std::vector<std::vector<Region>> read_targets(const std::string &targets_path, const std::vector<std::string> &names, bool *overflow = nullptr)
+{
+	std::vector<std::vector<Region>> target_regions(names.size());
+	fputs("Reading target regions into memory...\n", stderr);
+	host::LineReader bed(targets_path);
+	std::string line;
+	for (;;) {
+		const bool ok = bed.read_line(line);
+		if (bed.bad_utf8()) error("I/O error while reading from file.");
+		if (!ok) break;
+		const size_t off = host::trim_start_off(line), end = host::trim_end_len(line);
+		if (end <= off || line[0] == '#') continue;                                                // :37
+		const std::vector<std::string> cols = split_tabs(line.substr(off, end - off));
+		if (cols.size() < 3) error("Invalid line in BED file %s:\n%s", targets_path.c_str(), line.c_str());
+		int tid = -1;
+		for (size_t k = 0; k < names.size(); k++) if (names[k] == cols[0]) { tid = (int)k; break; }
+		if (tid < 0) error("Chromosome %s is listed in target region BED file, but is not found in BAM file.", cols[0].c_str());
+		uint64_t s, e;
+		if (!host::parse_uint(cols[1].c_str(), INT64_MAX, s) || !host::parse_uint(cols[2].c_str(), INT64_MAX, e)) panic("called `Result::unwrap()` on an `Err` value: ParseIntError (BED)");
+		if (overflow && s == (uint64_t)INT64_MAX) *overflow = true;
+		target_regions[tid].push_back({(int64_t)(s + 1), (int64_t)e});                             // :44-47
+	}
+	for (auto &v : target_regions) std::sort(v.begin(), v.end(), [](const Region &a, const Region &b) { return a.start < b.start; });   // :51-53
+	return target_regions;
+}
+
+// sam statistics --on-target over the FILE: the device inflates and walks it (sk_bam_file_columns) and counts S1 and S2 of every record
+// in one call (sk_on_target_add_dev): whether a fragment overlaps a region does not depend on the records before it.
+// -1: nothing has been written to stdout, and the caller's reader serves the file — one the file path does not take, a header without
+// references (the reference's target_regions.is_empty()), a BED start whose + 1 overflows, or a fragment whose tid has no reference (the
+// reader panics where the reference does).  The regions, once read here, are the caller's too (*have_regions): the BED is read and
+// announced once.  Otherwise the number of records; counters = total, aligned, duplicate reads, total and on-target fragments.
+static int64_t on_target_from_file(const std::string &path, const std::string &targets_path, int64_t max_frag_len,
+                                   std::vector<std::vector<Region>> &target_regions, bool *have_regions, uint64_t counters[5])
+{
+	sk_ctx *c = host::gpu();
+	sk_bam_columns cols;
+	int handled = 0;
+	const uint32_t want = SK_COL_FLAG | SK_COL_TID | SK_COL_MTID | SK_COL_POS | SK_COL_MPOS | SK_COL_TLEN | SK_COL_END;
+	if (sk_bam_file_columns(c, path.c_str(), want, &cols, &handled, nullptr) != SK_OK || !handled) return -1;
+	const std::vector<std::string> names = header_names(cols.header, cols.header_len);
+	if (names.empty()) return -1;
+	bool overflow = false;
+	target_regions = read_targets(targets_path, names, &overflow);
+	*have_regions = true;
+	if (overflow) return -1;
+	std::vector<int32_t> chr_off(names.size() + 1, 0);
+	std::vector<int64_t> rs, re;
+	for (size_t k = 0; k < names.size(); k++) {
+		for (const Region &r : target_regions[k]) { rs.push_back(r.start); re.push_back(r.end); }
+		if (rs.size() > 0x7fffffffu) return -1;
+		chr_off[k + 1] = (int32_t)rs.size();
+	}
+	if (sk_on_target_set_regions(c, (int)names.size(), chr_off.data(), rs.data(), re.data(), (int64_t)rs.size()) != SK_OK) return -1;
+	if (sk_on_target_add_dev(c, cols.flag, cols.tid, cols.mtid, cols.pos, cols.mpos, cols.tlen, cols.end_pos, cols.n, max_frag_len) != SK_OK) return -1;
+	uint64_t got[6];
+	if (sk_on_target_get(c, got) != SK_OK || got[5] != 0) return -1;
+	memcpy(counters, got, 5 * sizeof(uint64_t));
+	return cols.n;
+}
+
 static int statistics(int argc, char **argv)
 {
 	std::vector<host::Opt> opts = {{"--on-target", true, false, ""}};
@@ -361,10 +425,16 @@ static int statistics(int argc, char **argv)
 		         host::fmt_pct((double)counters[2] / (double)counters[1] * 100.0).c_str());
 		host::out().write(buf, strlen(buf));
 	};
+	auto print_on_target = [](uint64_t on_target_fragments, uint64_t total_fragments) {                // :114
+		char buf[256];
+		snprintf(buf, sizeof buf, "On-target: %s%%\n", host::fmt_pct((double)on_target_fragments / (double)total_fragments * 100.0).c_str());
+		host::out().write(buf, strlen(buf));
+	};
 	// S1 over the FILE (round 6): the compressed bytes cross PCIe, the device inflates the BGZF blocks, walks the records and counts
 	// (include/seqkit_hip.h: sk_bam_file_reduce).  It serves well-formed regular files only and says so (handled): everything else —
 	// stdin, plain gzip, a file cut short, a record chain that does not verify — is read record by record below, which reports it as
-	// the reference does.  (--on-target needs pos / cigar of every record in order: the host's sweep, below.)
+	// the reference does.  With --on-target the file goes the same way as columns (on_target_from_file): S2 needs pos and the cigar's
+	// end of every record, but not their order.
 	if (targets_path.empty() && file_path_wanted(bam_path)) {
 		int handled = 0;
 		uint64_t fc[3] = {0, 0, 0};
@@ -376,31 +446,18 @@ static int statistics(int argc, char **argv)
 		if (bamfile_trace()) fprintf(stderr, "sam statistics: waited %.1f ms for the device contexts, sk_bam_file_reduce %.1f ms\n", t1 - t0, now_ms() - t1);
 		if (handled) { print_counters(fc); return 0; }
 	}
-	BamStream bam(bam_path);
-
 	std::vector<std::vector<Region>> target_regions;                                                   // :26-54
+	bool have_regions = false;
 	if (!targets_path.empty()) {
-		fputs("Reading target regions into memory...\n", stderr);
-		target_regions.resize(bam.names.size());
-		host::LineReader bed(targets_path);
-		std::string line;
-		for (;;) {
-			const bool ok = bed.read_line(line);
-			if (bed.bad_utf8()) error("I/O error while reading from file.");
-			if (!ok) break;
-			const size_t off = host::trim_start_off(line), end = host::trim_end_len(line);
-			if (end <= off || line[0] == '#') continue;                                                // :37
-			const std::vector<std::string> cols = split_tabs(line.substr(off, end - off));
-			if (cols.size() < 3) error("Invalid line in BED file %s:\n%s", targets_path.c_str(), line.c_str());
-			int tid = -1;
-			for (size_t k = 0; k < bam.names.size(); k++) if (bam.names[k] == cols[0]) { tid = (int)k; break; }
-			if (tid < 0) error("Chromosome %s is listed in target region BED file, but is not found in BAM file.", cols[0].c_str());
-			uint64_t s, e;
-			if (!host::parse_uint(cols[1].c_str(), INT64_MAX, s) || !host::parse_uint(cols[2].c_str(), INT64_MAX, e)) panic("called `Result::unwrap()` on an `Err` value: ParseIntError (BED)");
-			target_regions[tid].push_back({(int64_t)s + 1, (int64_t)e});                               // :44-47
+		uint64_t fc[5] = {0, 0, 0, 0, 0};
+		if (device_path("sam statistics", bam_path, [&] { return on_target_from_file(bam_path, targets_path, max_frag_len, target_regions, &have_regions, fc); }) >= 0) {
+			print_counters(fc);
+			print_on_target(fc[4], fc[3]);
+			return 0;
 		}
-		for (auto &v : target_regions) std::sort(v.begin(), v.end(), [](const Region &a, const Region &b) { return a.start < b.start; });   // :51-53
 	}
+	BamStream bam(bam_path);
+	if (!targets_path.empty() && !have_regions) target_regions = read_targets(targets_path, bam.names);
 	const bool on_target = !target_regions.empty();
 
 	uint64_t counters[3] = {0, 0, 0};
@@ -410,7 +467,7 @@ static int statistics(int argc, char **argv)
 		// S1 on the device: src/sam_statistics.rs:63-69
 		check(sk_bam_flag_tlen(host::gpu(), col.flag.data(), nullptr, nullptr, nullptr, n, 0, counters, nullptr, nullptr), "sk_bam_flag_tlen");
 		if (!on_target) continue;
-		// S2 (--on-target) stays on the host: src/sam_statistics.rs:72-106
+		// S2 (--on-target) of a file the device path does not take, as the reference states it: src/sam_statistics.rs:72-106
 		for (int64_t i = 0; i < n; i++) {
 			const uint16_t f = col.flag[i];
 			if ((f & 0x100) || (f & 0x800)) continue;
@@ -439,11 +496,7 @@ static int statistics(int argc, char **argv)
 	}
 	bam.raise_deferred();
 	print_counters(counters);                                                                          // :109-115
-	char buf[256];
-	if (on_target) {
-		snprintf(buf, sizeof buf, "On-target: %s%%\n", host::fmt_pct((double)on_target_fragments / (double)total_fragments * 100.0).c_str());
-		host::out().write(buf, strlen(buf));
-	}
+	if (on_target) print_on_target(on_target_fragments, total_fragments);
 	return 0;
 }
 

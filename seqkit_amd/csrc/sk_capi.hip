@@ -74,6 +74,12 @@ struct sk_ctx {
 	uint8_t *d_cnt = nullptr;          // one allocation: chr_off, rstart, rend, rpmax, ridx, counts
 	int32_t *d_chr_off = nullptr, *d_ridx = nullptr;
 	uint32_t *d_rstart = nullptr, *d_rend = nullptr, *d_rpmax = nullptr, *d_region_frags = nullptr;
+	// `sam statistics --on-target` region tables and counters
+	int ot_n_chr = 0;
+	uint8_t *d_ot = nullptr;           // one allocation: chr_off, rstart, rpmax, the six counters
+	int32_t *d_ot_chr_off = nullptr;
+	int64_t *d_ot_rstart = nullptr, *d_ot_rpmax = nullptr;
+	unsigned long long *d_ot_counters = nullptr;
 };
 
 static thread_local std::string g_create_err;
@@ -250,6 +256,7 @@ void sk_destroy(sk_ctx *c)
 	if (c->census) sk::census_destroy(c->census);
 	if (c->comm) (void)sk_comm_destroy(c);
 	if (c->d_cnt) (void)hipFree(c->d_cnt);
+	if (c->d_ot) (void)hipFree(c->d_ot);
 	if (c->d_genome) (void)hipFree(c->d_genome);
 	if (c->ev0) (void)hipEventDestroy(c->ev0);
 	if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1701,6 +1708,116 @@ int sk_count_get(sk_ctx *c, uint32_t *region_frags)
 	if (int r = bind(c)) return r;
 	SK_HIP(c, hipStreamSynchronize(c->stream));
 	if (c->cnt_n_regions) SK_HIP(c, hipMemcpy(region_frags, c->d_region_frags, (size_t)c->cnt_n_regions * 4, hipMemcpyDeviceToHost));
+	return SK_OK;
+}
+
+// ---- S2: sam statistics --on-target ---------------------------------------------------------------------------------
+int sk_on_target_set_regions(sk_ctx *c, int n_chr, const int32_t *chr_off, const int64_t *rstart, const int64_t *rend, int64_t n_entries)
+{
+	if (!c) return SK_ERR_INVALID;
+	if (n_chr < 0 || n_entries < 0 || n_entries > 0x7fffffff || !chr_off || (n_entries > 0 && (!rstart || !rend)))
+		return fail(c, SK_ERR_INVALID, "sk_on_target_set_regions: bad arguments");
+	if (chr_off[0] != 0 || chr_off[n_chr] != n_entries) return fail(c, SK_ERR_INVALID, "chr_off must run from 0 to n_entries");
+	for (int k = 0; k < n_chr; k++) if (chr_off[k] > chr_off[k + 1]) return fail(c, SK_ERR_INVALID, "chr_off must not decrease");
+	if (int r = bind(c)) return r;
+	// sort each reference's regions by start (src/sam_statistics.rs:51-53) and take the running maximum of their ends
+	std::vector<int32_t> order((size_t)n_entries);
+	for (int64_t i = 0; i < n_entries; i++) order[(size_t)i] = (int32_t)i;
+	for (int k = 0; k < n_chr; k++)
+		std::sort(order.begin() + chr_off[k], order.begin() + chr_off[k + 1], [&](int32_t x, int32_t y) { return rstart[x] < rstart[y]; });
+	std::vector<int64_t> s((size_t)n_entries), pm((size_t)n_entries);
+	for (int k = 0; k < n_chr; k++) {
+		int64_t run = INT64_MIN;
+		for (int32_t i = chr_off[k]; i < chr_off[k + 1]; i++) {
+			const int32_t o = order[(size_t)i];
+			s[(size_t)i] = rstart[o];
+			run = std::max(run, rend[o]);
+			pm[(size_t)i] = run;
+		}
+	}
+	SK_HIP(c, hipStreamSynchronize(c->stream));
+	if (c->d_ot) { SK_HIP(c, hipFree(c->d_ot)); c->d_ot = nullptr; }
+	const size_t b_off = up256((size_t)(n_chr + 1) * 4), b_reg = up256((size_t)n_entries * 8 + 8), b_cnt = up256(6 * 8);
+	hipError_t he = hipMalloc((void **)&c->d_ot, b_off + 2 * b_reg + b_cnt);
+	if (he != hipSuccess) { (void)hipGetLastError(); c->d_ot = nullptr; return fail(c, SK_ERR_NOMEM, "target region tables: %s", hipGetErrorString(he)); }
+	uint8_t *p = c->d_ot;
+	c->d_ot_chr_off = (int32_t *)p; p += b_off;
+	c->d_ot_rstart = (int64_t *)p; p += b_reg;
+	c->d_ot_rpmax = (int64_t *)p; p += b_reg;
+	c->d_ot_counters = (unsigned long long *)p;
+	SK_HIP(c, hipMemcpyAsync(c->d_ot_chr_off, chr_off, (size_t)(n_chr + 1) * 4, hipMemcpyHostToDevice, c->stream));
+	if (n_entries) {
+		SK_HIP(c, hipMemcpyAsync(c->d_ot_rstart, s.data(), (size_t)n_entries * 8, hipMemcpyHostToDevice, c->stream));
+		SK_HIP(c, hipMemcpyAsync(c->d_ot_rpmax, pm.data(), (size_t)n_entries * 8, hipMemcpyHostToDevice, c->stream));
+	}
+	SK_HIP(c, hipMemsetAsync(c->d_ot_counters, 0, b_cnt, c->stream));
+	SK_HIP(c, hipStreamSynchronize(c->stream));              // the staging vectors go out of scope
+	c->ot_n_chr = n_chr;
+	return SK_OK;
+}
+
+static int on_target_args(sk_ctx *c, sk::TargetArgs &a, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *pos,
+                          const int32_t *mpos, const int32_t *tlen, const int32_t *end_pos, int64_t n, int64_t max_frag_len)
+{
+	if (!c->d_ot) return fail(c, SK_ERR_INVALID, "sk_on_target_set_regions has not been called");
+	if (n < 0) return fail(c, SK_ERR_INVALID, "n = %lld", (long long)n);
+	if (n > 0 && (!flag || !tid || !mtid || !pos || !mpos || !tlen || !end_pos)) return fail(c, SK_ERR_INVALID, "NULL column");
+	a.flag = flag; a.tid = tid; a.mtid = mtid; a.pos = pos; a.mpos = mpos; a.tlen = tlen; a.end_pos = end_pos;
+	a.n = n; a.max_frag_len = max_frag_len;
+	a.n_chr = c->ot_n_chr; a.chr_off = c->d_ot_chr_off; a.rstart = c->d_ot_rstart; a.rpmax = c->d_ot_rpmax; a.out = c->d_ot_counters;
+	return SK_OK;
+}
+
+int sk_on_target_add_dev(sk_ctx *c, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *pos, const int32_t *mpos,
+                         const int32_t *tlen, const int32_t *end_pos, int64_t n, int64_t max_frag_len)
+{
+	if (!c) return SK_ERR_INVALID;
+	sk::TargetArgs a;
+	if (int r = on_target_args(c, a, flag, tid, mtid, pos, mpos, tlen, end_pos, n, max_frag_len)) return r;
+	if (n == 0) return SK_OK;
+	if (int r = bind(c)) return r;
+	SK_HIP(c, sk::launch_bam_target(a, c->n_cu, c->stream));
+	return SK_OK;
+}
+
+int sk_on_target_add(sk_ctx *c, const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *pos, const int32_t *mpos,
+                     const int32_t *tlen, const int32_t *end_pos, int64_t n, int64_t max_frag_len)
+{
+	if (!c) return SK_ERR_INVALID;
+	sk::TargetArgs a;
+	if (int r = on_target_args(c, a, flag, tid, mtid, pos, mpos, tlen, end_pos, n, max_frag_len)) return r;
+	if (n == 0) return SK_OK;
+	if (int r = bind(c)) return r;
+	int64_t chunk = (int64_t)pipe_chunk((size_t)2 << 20);
+	if (chunk > n) chunk = n;
+	const size_t b2 = up256((size_t)chunk * 2), b4 = up256((size_t)chunk * 4);
+	ChunkPipe pipe(c);
+	if (int r = pipe.begin(b2 + 6 * b4)) return r;
+	const int32_t *hcol[6] = {tid, mtid, pos, mpos, tlen, end_pos};
+	for (int64_t o = 0; o < n; o += chunk, pipe.next()) {
+		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
+		hipStream_t st = pipe.st();
+		uint8_t *p = pipe.ws();
+		uint16_t *dflag = (uint16_t *)p; p += b2;
+		int32_t *dcol[6];
+		for (int k = 0; k < 6; k++) { dcol[k] = (int32_t *)p; p += b4; }
+		SK_HIP(c, hipMemcpyAsync(dflag, flag + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
+		for (int k = 0; k < 6; k++) SK_HIP(c, hipMemcpyAsync(dcol[k], hcol[k] + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
+		a.flag = dflag; a.tid = dcol[0]; a.mtid = dcol[1]; a.pos = dcol[2]; a.mpos = dcol[3]; a.tlen = dcol[4]; a.end_pos = dcol[5];
+		a.n = nr;
+		SK_HIP(c, sk::launch_bam_target(a, c->n_cu, st));
+	}
+	return pipe.end();
+}
+
+int sk_on_target_get(sk_ctx *c, uint64_t out[6])
+{
+	if (!c) return SK_ERR_INVALID;
+	if (!c->d_ot) return fail(c, SK_ERR_INVALID, "sk_on_target_set_regions has not been called");
+	if (!out) return fail(c, SK_ERR_INVALID, "out is NULL");
+	if (int r = bind(c)) return r;
+	SK_HIP(c, hipStreamSynchronize(c->stream));
+	SK_HIP(c, hipMemcpy(out, c->d_ot_counters, 6 * 8, hipMemcpyDeviceToHost));
 	return SK_OK;
 }
 

@@ -149,6 +149,19 @@ struct CountArgs {
 };
 hipError_t launch_bam_count(const CountArgs &a, int n_cu, hipStream_t st);
 
+// `sam statistics --on-target` (sk_bamtarget.hip): record columns + the region tables of sk_on_target_set_regions
+struct TargetArgs {
+	const uint16_t *flag;
+	const int32_t *tid, *mtid, *pos, *mpos, *tlen, *end_pos;
+	int64_t n;
+	int64_t max_frag_len;
+	int n_chr;
+	const int32_t *chr_off;        // n_chr + 1 offsets into the sorted region arrays
+	const int64_t *rstart, *rpmax; // 1-based inclusive starts, ascending per chromosome; the running maximum of the ends
+	unsigned long long *out;       // u64[6]: total, aligned, duplicate reads; total, on-target fragments; fragments with a tid outside [0, n_chr)
+};
+hipError_t launch_bam_target(const TargetArgs &a, int n_cu, hipStream_t st);
+
 hipError_t launch_gc_count(const uint8_t *genome, const int64_t *seg_start, const int32_t *seg_len, const int32_t *seg_region, int64_t nseg,
                            unsigned long long *out, int n_cu, hipStream_t st);
 

@@ -14,7 +14,16 @@ write that row's file to PATH; with --human the one under the human-sized header
 commit's) whose `trim qnames` is the yardstick row instead of this build's] [--subsample-file=PATH: only write that row's file to
 PATH, for a profiler run of the command] [--merge: only the `sam merge` rows, see below] [--merge-files=DIR: only write the undealt file
 and the parts to DIR (in.bam, p2_0.bam .., p8_0.bam ..), for a profiler run of the command] [--pairing: only the `sam to` pairing rows,
-see below] [--pairing-file=PATH: only write that row's file to PATH, for a profiler run of the command]
+see below] [--pairing-file=PATH: only write that row's file to PATH, for a profiler run of the command] [--on-target: only the `sam
+statistics --on-target` rows, see below] [--on-target-files=DIR: only write that row's file and BED to DIR (in.bam, t.bed), for a profiler
+run of the command]
+
+--on-target: the subsample file (position-sorted, 200 references) and a BED of 4 000 regions over its references, a fifth of them short
+ones under a long one.  Rows, all to /dev/null: `sam count --single-end <file> <bed>` on the device path (--yardstick-sam: another
+build's, the parent commit's) — it makes the same columns call (with mapq besides) and runs the heavier kernel: an order check, the
+search, a walk over the regions and an atomic per hit —, `sam statistics --on-target=<bed>` on the device path and through the host
+reader.  Wall and CPU-seconds of every run, and statistics / count run for run next to the spread (max - min) of the count repeats.
+The stdout and stderr of both paths are compared on every run.
 
 --pairing: the fragments file (name-sorted in effect: mates adjacent).  Rows: `sam to interleaved fastq` to /dev/null and, without
 --no-gz, `sam to fastq <prefix>` to files, each with the mates paired on the device (SEQKIT_DEVICE_PAIRING=1), paired on the host over the device's
@@ -84,6 +93,8 @@ subsample_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith(
 merge = "--merge" in sys.argv
 pairing = "--pairing" in sys.argv
 pairing_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--pairing-file=")), None)
+on_target = "--on-target" in sys.argv
+on_target_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--on-target-files=")), None)
 merge_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--merge-files=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -456,6 +467,65 @@ def merge_rows():
     os.rmdir(d)
 
 
+def write_target_bed(path, regions=4000):
+    """regions over the count file's references (positions 0 .. PAIRS + a fragment): four in five 50-3 000 long anywhere, one in five a
+    short one under a long one that begins before it"""
+    brng = np.random.default_rng(7)
+    with open(path, "w") as f:
+        f.write("# targets\n")
+        for k in range(regions // 5):
+            c = int(brng.integers(1, reps + 1))
+            for _ in range(3):
+                s0 = int(brng.integers(0, PAIRS))
+                f.write(f"chr{c}\t{s0}\t{s0 + int(brng.integers(50, 3000))}\n")
+            s0 = int(brng.integers(0, PAIRS - 6000))
+            f.write(f"chr{c}\t{s0}\t{s0 + 6000}\n")
+            s1 = s0 + int(brng.integers(100, 5000))
+            f.write(f"chr{c}\t{s1}\t{s1 + 20}\n")
+
+
+def on_target_rows():
+    t0 = time.perf_counter()
+    write_count_file(bam)
+    write_target_bed(bed)
+    print(f"on-target file: {n} BAM records on {reps} references, sorted, {os.path.getsize(bam) / 1e6:.0f} MB, written in {time.perf_counter() - t0:.1f} s; "
+          f"BED of {sum(1 for ln in open(bed) if not ln.startswith('#'))} regions; {runs} runs per row, alternating", flush=True)
+    count_sam = yardstick_sam or SAM
+    count_label = "sam count --single-end          device" + (" (yardstick build)" if yardstick_sam else "")
+    rows, seen = {}, set()
+    for k in range(runs):
+        for label, cmd, env in ((count_label, [count_sam, "count", "--single-end", bam, bed], None),
+                                ("sam statistics --on-target      device", [SAM, "statistics", f"--on-target={bed}", bam], None),
+                                ("sam statistics --on-target      host  ", [SAM, "statistics", f"--on-target={bed}", bam], {"SEQKIT_HOST_INFLATE": "1"})):
+            stat = label.startswith("sam statistics")
+            dt, cpu, rc, h, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=None if stat else os.devnull)
+            lines = err.decode(errors="replace").split("\n")
+            served = [ln for ln in lines if ln.startswith("sam ")]
+            assert rc == 0 and len(served) == 1 and ("host reader" if env else "device path") in served[0], (label, rc, err[-400:])
+            if stat:
+                seen.add((rc, h, "\n".join(ln for ln in lines if not ln.startswith(("sam ", "sk_bam_file_")))))     # (without the trace's own lines)
+            rows.setdefault(label, []).append((dt, cpu))
+            if stat and not env:
+                stages = [ln for ln in lines if ln.startswith("sk_bam_file_columns:")]
+    assert len(seen) == 1, f"sam statistics --on-target: outputs differ: {seen}"
+    for label, r in rows.items():
+        w = [x[0] for x in r]
+        print(f"{label} : " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu in r) + f"  (median {float(np.median(w)):.2f} s, max - min {max(w) - min(w):.2f} s)", flush=True)
+    print("sam statistics --on-target: stdout and stderr identical on both paths in every run (stdout sha256 " + next(iter(seen))[1] + "): "
+          + open(out).read().replace("\n", " | "), flush=True)
+    for ln in stages:
+        print("  " + ln, flush=True)
+    st = [x[0] for x in rows["sam statistics --on-target      device"]]
+    ct = [x[0] for x in rows[count_label]]
+    host = [x[0] for x in rows["sam statistics --on-target      host  "]]
+    print("statistics --on-target / count --single-end, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(st, ct))
+          + f"; medians {float(np.median(st)) / float(np.median(ct)):.2f}x; median difference {float(np.median(st)) - float(np.median(ct)):+.2f} s against count's max - min "
+          f"{max(ct) - min(ct):.2f} s; device / host reader (medians) = {float(np.median(st)) / float(np.median(host)):.2f}", flush=True)
+    for f_ in (bam, bed, out):
+        os.remove(f_)
+    os.rmdir(d)
+
+
 HUMAN_REFS, HUMAN_LEN = 25, 124_000_000
 
 
@@ -510,6 +580,15 @@ if merge_files is not None:
     sys.exit(0)
 if merge:
     merge_rows()
+    sys.exit(0)
+if on_target_files is not None:
+    write_count_file(os.path.join(on_target_files, "in.bam"))
+    write_target_bed(os.path.join(on_target_files, "t.bed"))
+    print(f"wrote {on_target_files}/in.bam ({n} records) and t.bed", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if on_target:
+    on_target_rows()
     sys.exit(0)
 if coverage_file is not None:
     write_count_file(coverage_file, HUMAN_REFS if human else None, HUMAN_LEN if human else 1 << 28)
