@@ -119,7 +119,10 @@ int sk_barcode_table_info(sk_ctx *ctx, int *kind, int64_t *keys, int64_t *bytes)
 
 /* ---- T1: 3' running-sum quality trim --------------------------------------------------------------
  * src/fasta_trim_by_quality.rs:28-42.  qual rows are the quality line after trim_end(); writes
- * lowest_k[r] in [0, len[r]] (0 means the reference emits "N\n+\n!\n", :44-45).                      */
+ * lowest_k[r] in [0, len[r]] (0 means the reference emits "N\n+\n!\n", :44-45).
+ * _dev: qual must be 16-byte aligned (SK_ERR_INVALID otherwise, nothing is launched) and readable to the next
+ * dword behind its last byte; len and lowest_k are u16 columns at their natural alignment; exactly 2 n bytes of
+ * lowest_k are written.                                                                               */
 int sk_trim_by_quality(sk_ctx *ctx, const uint8_t *qual, const uint16_t *len, int stride, int64_t n,
                        uint8_t min_baseq, uint16_t *lowest_k);
 int sk_trim_by_quality_dev(sk_ctx *ctx, const uint8_t *qual, const uint16_t *len, int stride, int64_t n,
@@ -127,7 +130,10 @@ int sk_trim_by_quality_dev(sk_ctx *ctx, const uint8_t *qual, const uint16_t *len
 
 /* ---- M1: mask bases whose Phred+33 quality is below min_baseq ------------------------------------
  * src/fasta_mask_by_quality.rs:40-43 (byte form, i.e. ASCII lines; the host keeps non-ASCII lines).
- * out_seq may equal seq (in place).                                                                  */
+ * out_seq may equal seq (in place).
+ * _dev: seq, qual and out_seq must each be 16-byte aligned (SK_ERR_INVALID otherwise, nothing is launched); seq and
+ * qual must be readable to the next dword behind their last byte; exactly n * stride bytes of out_seq are
+ * written, whatever n * stride is a multiple of.                                                     */
 int sk_mask_by_quality(sk_ctx *ctx, uint8_t *seq /* in/out */, const uint8_t *qual, const uint16_t *len,
                        int stride, int64_t n, uint8_t min_baseq);
 int sk_mask_by_quality_dev(sk_ctx *ctx, const uint8_t *seq, const uint8_t *qual, int stride, int64_t n,
@@ -141,7 +147,14 @@ int sk_mask_by_quality_dev(sk_ctx *ctx, const uint8_t *seq, const uint8_t *qual,
  *   demultiplex : bc != NULL           -> assign (+ optional lowest_diff/first_idx/last_idx, counters)
  *   trim        : mate.lowest_k != NULL
  *   mask        : mate.out_seq  != NULL (may alias mate.seq)
- * The same struct serves the host and the _dev entry point.                                          */
+ * The same struct serves the host and the _dev entry point.
+ * _dev (sk_fused_pass_dev and every batch of sk_fused_pass_many_dev): qual of a mate with work, and seq and out_seq
+ * of a mate that is masked, must be 16-byte aligned; bc and assign 16-byte, lowest_diff 4-byte, first_idx / last_idx
+ * 8-byte aligned; len, lowest_k and counts at their natural alignment (2, 2 and 8 bytes).  A pointer short of its
+ * rule: SK_ERR_INVALID, and nothing is launched — for the many-batch call no batch is.  seq, qual and bc must be
+ * readable to the next dword behind their last byte (any allocation of a whole number of dwords provides that).
+ * Outputs are written to exactly their size: n * stride bytes of out_seq (a row's bytes past len[r] unspecified),
+ * 2 n of lowest_k, 4 n of assign, n of lowest_diff, 2 n of first_idx / last_idx, 8 (S + 3) of counts.          */
 typedef struct {
 	const uint8_t  *seq;        /* n x stride  (needed only for mask)           */
 	const uint8_t  *qual;       /* n x stride                                   */
@@ -176,19 +189,19 @@ int sk_fused_pass_dev(sk_ctx *ctx, const sk_fused_args *args);
  * work per read: reads are independent, so are batches).  Asynchronous like the _dev calls; sk_sync() waits.  The two
  * conveniences below build the argument blocks. */
 int sk_fused_pass_many_dev(sk_ctx *ctx, const sk_fused_args *batches, int n_batches);
-typedef struct sk_demux_batch {
-	const uint8_t *bc;          /* n x bc_stride */
+typedef struct sk_demux_batch {     /* device pointers, aligned as sk_fused_args' _dev rules say, batch by batch */
+	const uint8_t *bc;          /* n x bc_stride; 16-byte aligned, readable to the next dword behind its last byte */
 	int64_t n;
-	int32_t *assign;            /* n */
-	uint8_t *lowest_diff;       /* n or NULL */
-	int16_t *first_idx, *last_idx;
+	int32_t *assign;            /* n; 16-byte aligned */
+	uint8_t *lowest_diff;       /* n or NULL; 4-byte aligned */
+	int16_t *first_idx, *last_idx;      /* n or NULL; 8-byte aligned */
 } sk_demux_batch;
 int sk_demux_assign_many_dev(sk_ctx *ctx, const sk_demux_batch *batches, int n_batches, int bc_stride);
-typedef struct sk_trim_batch {
-	const uint8_t *qual;        /* n x stride */
+typedef struct sk_trim_batch {      /* device pointers */
+	const uint8_t *qual;        /* n x stride; 16-byte aligned, readable to the next dword behind its last byte */
 	const uint16_t *len;        /* n or NULL */
 	int64_t n;
-	uint16_t *lowest_k;         /* n */
+	uint16_t *lowest_k;         /* n: exactly 2 n bytes are written */
 } sk_trim_batch;
 int sk_trim_by_quality_many_dev(sk_ctx *ctx, const sk_trim_batch *batches, int n_batches, int stride, uint8_t min_baseq);
 

@@ -924,10 +924,9 @@ class Context:
         return [(bytes(e["barcode"]), int(e["count"]), int(e["first_row"])) for e in out[:k]], int(total[0])
 
     # ---- device entry points (raw addresses) ---------------------------------------------
-    def fused_pass_dev(self, n: int, stride: int, min_baseq: int, mates, bc: int = 0, bc_stride: int = 0,
-                       assign: int = 0, lowest_diff: int = 0, first_idx: int = 0, last_idx: int = 0,
-                       counts: int = 0) -> None:
-        """mates: list of dicts with device addresses {seq, qual, len, out_seq, lowest_k} (0 = NULL)."""
+    @staticmethod
+    def _fused_args(n: int, stride: int, min_baseq: int, mates, bc: int = 0, bc_stride: int = 0, assign: int = 0, lowest_diff: int = 0,
+                    first_idx: int = 0, last_idx: int = 0, counts: int = 0) -> _FusedArgs:
         a = _FusedArgs()
         a.n, a.n_mates, a.stride, a.min_baseq = n, len(mates), stride, min_baseq
         for i, m in enumerate(mates):
@@ -943,7 +942,19 @@ class Context:
         a.first_idx = first_idx or None
         a.last_idx = last_idx or None
         a.counts = counts or None
+        return a
+
+    def fused_pass_dev(self, n: int, stride: int, min_baseq: int, mates, bc: int = 0, bc_stride: int = 0,
+                       assign: int = 0, lowest_diff: int = 0, first_idx: int = 0, last_idx: int = 0,
+                       counts: int = 0) -> None:
+        """mates: list of dicts with device addresses {seq, qual, len, out_seq, lowest_k} (0 = NULL)."""
+        a = self._fused_args(n, stride, min_baseq, mates, bc, bc_stride, assign, lowest_diff, first_idx, last_idx, counts)
         self._check(self._lib.sk_fused_pass_dev(self._h, C.byref(a)), "sk_fused_pass_dev")
+
+    def fused_pass_many_dev(self, batches) -> None:
+        """batches: a list of dicts of fused_pass_dev's arguments by name (n, stride, min_baseq, mates, bc, ...): sk_fused_pass_many_dev"""
+        arr = (_FusedArgs * len(batches))(*[self._fused_args(**b) for b in batches])
+        self._check(self._lib.sk_fused_pass_many_dev(self._h, arr, len(batches)), "sk_fused_pass_many_dev")
 
     def fused_pass_blocked_dev(self, lay: BlockedLayout, inp: int, out: int, n: int, min_baseq: int, counts: int = 0) -> None:
         self._check(self._lib.sk_fused_pass_blocked_dev(self._h, C.byref(lay), inp, out, n, min_baseq, counts or None),
