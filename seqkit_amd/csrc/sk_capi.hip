@@ -17,6 +17,7 @@
 
 #include "../../include/seqkit_hip.h"
 #include "sk_internal.h"
+#include "sk_hoststage.h"
 
 struct sk_ctx {
 	int device = 0;
@@ -48,16 +49,14 @@ struct sk_ctx {
 	// workspace for the host-pointer entry points
 	uint8_t *ws = nullptr;
 	size_t ws_bytes = 0;
-	// sk_fused_pass_many_dev: the batch descriptors of a many-batch launch travel through a ring of pinned / device slots
-	sk::ManyBatch *many_pin = nullptr, *many_dev = nullptr;
+	// sk_fused_pass_many_dev: the batch descriptors of a many-batch launch travel through a ring of pinned slots
+	sk::ManyBatch *many_pin = nullptr;
 	hipEvent_t many_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	int many_next = 0;
 	// the sheet / pitch / output set for which launch_tile_pass last said "no one-launch form": the next many-batch call of that shape goes
 	// straight to its batches' own launches (the refused attempt cost an event and the descriptors: 3 us a call)
 	const void *many_no_tab = nullptr;
 	int many_no_stride = 0, many_no_detail = -1;
-	uint8_t *pin = nullptr;            // a pinned landing area (sk_bgzf_deflate: the compressed slots come back here)
-	size_t pin_bytes = 0;
 	// buffers that stay with the ctx from one call to the next (sk::ctx_keep; sk_internal.h: sk::KeepSlot)
 	struct Kept { void *p = nullptr; size_t cap = 0; bool pinned = false; } kept[sk::kKeepSlots];
 	void *ext = nullptr;               // an object another translation unit keeps with the ctx (sk_bamfile.h: Ranges, the file calls' mapped ranges and window state), and how to free it
@@ -121,8 +120,6 @@ static int ensure_ws(sk_ctx *c, size_t bytes)
 	return SK_OK;
 }
 
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 namespace sk {
 hipStream_t ctx_stream(sk_ctx *c) { return c->stream; }
 hipStream_t ctx_stream2(sk_ctx *c) { return c->stream2; }
@@ -160,23 +157,41 @@ int ctx_fail(sk_ctx *c, int code, const char *fmt, ...)
 // stream (k & 1) and half (k & 1) of the workspace, so the H2D copies of chunk k+1 run under the kernel and the D2H
 // copies of chunk k, and a half is reused only by the next chunk of the SAME stream (in order: no hazard).  Copies are
 // true DMA when the caller's buffers are pinned (sk_malloc_pinned); pageable buffers work too, staged by the runtime.
+// What a chunk stages is stated once per call, as a hoststage::Stage (sk_hoststage.h): begin() sizes the workspace from it, stage_in()
+// carves the lane's half and queues the H2D copies of rows [r0, r0 + nr), stage_out() queues the D2H copies behind the launch.
+using namespace hoststage;
 struct ChunkPipe {
 	sk_ctx *c;
-	size_t half = 0;
+	Stage &s;
+	int64_t n = 0, r0 = 0, nr = 0;                             // the batch's rows; the chunk at hand is [r0, r0 + nr)
 	int k = 0;
-	explicit ChunkPipe(sk_ctx *ctx) : c(ctx) {}
-	int begin(size_t bytes_per_chunk, size_t shared_tail = 0)      // shared_tail: bytes after the two halves used by every chunk (accumulators)
+	ChunkPipe(sk_ctx *ctx, Stage &stage) : c(ctx), s(stage) {}
+	int begin(int64_t rows, int64_t chunk, size_t shared_tail = 0)
 	{
-		half = up256(bytes_per_chunk);
-		if (int r = ensure_ws(c, 2 * half + shared_tail)) return r;
+		s.plan(chunk, shared_tail);
+		n = rows; nr = s.rows_at(0, n);
+		if (int r = ensure_ws(c, s.total())) return r;
 		SK_HIP(c, hipEventRecord(c->ev_pipe, c->stream));          // the second lane starts after whatever the ctx stream holds
 		SK_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_pipe, 0));
 		return SK_OK;
 	}
+	bool more() const { return r0 < n; }
+	void next() { k++; r0 += s.chunk(); nr = s.rows_at(r0, n); }
 	hipStream_t st() const { return (k & 1) ? c->stream2 : c->stream; }
-	uint8_t *ws() const { return c->ws + (size_t)(k & 1) * half; }
-	uint8_t *tail() const { return c->ws + 2 * half; }
-	void next() { k++; }
+	uint8_t *ws() const { return c->ws + (size_t)(k & 1) * s.half(); }
+	uint8_t *tail() const { return c->ws + s.tail_at(); }      // behind the two halves, used by every chunk (accumulators)
+	int copies(Dir dir) const
+	{
+		hipError_t e = hipSuccess;
+		s.each_copy(dir, r0, nr, [&](size_t at, uint8_t *host, size_t bytes) {
+			if (e != hipSuccess) return;
+			e = dir == kIn ? hipMemcpyAsync(ws() + at, host, bytes, hipMemcpyHostToDevice, st()) : hipMemcpyAsync(host, ws() + at, bytes, hipMemcpyDeviceToHost, st());
+		});
+		if (e != hipSuccess) return fail(c, SK_ERR_HIP, "hipMemcpyAsync (%s): %s", dir == kIn ? "host to device" : "device to host", hipGetErrorString(e));
+		return SK_OK;
+	}
+	int stage_in() const { s.carve(ws()); return copies(kIn); }
+	int stage_out() const { return copies(kOut); }
 	int end()
 	{
 		SK_HIP(c, hipStreamSynchronize(c->stream2));
@@ -193,6 +208,26 @@ static size_t pipe_chunk(size_t dflt)
 	return dflt;
 }
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// Each reference's regions in the order of their starts (stable, as `sam count` sorts them; src/sam_statistics.rs:51-53 sorts unstably,
+// and this is one of the orders that may give): order[i] is the caller's entry at place i, s[i] its start, pm[i] the running maximum
+// of the ends up to it (from `lowest` on).
+template <class T>
+static std::vector<int32_t> regions_by_start(int n_chr, const int32_t *chr_off, const T *rstart, const T *rend, T lowest, std::vector<T> &s, std::vector<T> &pm)
+{
+	std::vector<int32_t> order((size_t)chr_off[n_chr]);
+	s.resize(order.size()); pm.resize(order.size());
+	for (size_t i = 0; i < order.size(); i++) order[i] = (int32_t)i;
+	for (int k = 0; k < n_chr; k++) {
+		std::stable_sort(order.begin() + chr_off[k], order.begin() + chr_off[k + 1], [&](int32_t x, int32_t y) { return rstart[x] < rstart[y]; });
+		T run = lowest;
+		for (int32_t i = chr_off[k]; i < chr_off[k + 1]; i++) {
+			s[(size_t)i] = rstart[order[(size_t)i]];
+			pm[(size_t)i] = run = std::max(run, rend[order[(size_t)i]]);
+		}
+	}
+	return order;
+}
 
 extern "C" {
 
@@ -247,11 +282,9 @@ void sk_destroy(sk_ctx *c)
 	if (c->d_counts_wide) (void)hipFree(c->d_counts_wide);
 	if (c->d_count_rep) (void)hipFree(c->d_count_rep);
 	if (c->ws) (void)hipFree(c->ws);
-	if (c->pin) (void)hipHostFree(c->pin);
 	for (auto &k : c->kept) if (k.p) { if (k.pinned) (void)hipHostFree(k.p); else (void)hipFree(k.p); }
 	if (c->ext && c->ext_free) c->ext_free(c->ext);
 	if (c->many_pin) (void)hipHostFree(c->many_pin);
-	if (c->many_dev) (void)hipFree(c->many_dev);
 	for (hipEvent_t e : c->many_ev) if (e) (void)hipEventDestroy(e);
 	if (c->census) sk::census_destroy(c->census);
 	if (c->comm) (void)sk_comm_destroy(c);
@@ -901,12 +934,11 @@ int sk_fused_pass_many_dev(sk_ctx *c, const sk_fused_args *batches, int n_batche
 			if (int r = prepare_demux(c, &batches[0])) return r;
 			if (!c->many_pin) {
 				SK_HIP(c, hipHostMalloc((void **)&c->many_pin, kManySlots * kManyMax * sizeof(sk::ManyBatch), hipHostMallocDefault));
-				SK_HIP(c, hipMalloc((void **)&c->many_dev, kManySlots * kManyMax * sizeof(sk::ManyBatch)));
 				for (int k = 0; k < kManySlots; k++) SK_HIP(c, hipEventCreateWithFlags(&c->many_ev[k], hipEventDisableTiming));
 			}
 			const int slot = c->many_next++ % kManySlots;
 			SK_HIP(c, hipEventSynchronize(c->many_ev[slot]));                // (the launch that read this slot eight calls ago: long done)
-			sk::ManyBatch *hb = c->many_pin + (size_t)slot * kManyMax, *db = c->many_dev + (size_t)slot * kManyMax;
+			sk::ManyBatch *hb = c->many_pin + (size_t)slot * kManyMax;
 			int64_t q0 = 0;
 			int nb = 0;
 			for (int i = 0; i < n_batches; i++) {
@@ -926,7 +958,6 @@ int sk_fused_pass_many_dev(sk_ctx *c, const sk_fused_args *batches, int n_batche
 			if (nb > 0) {
 				// (the kernel reads the descriptors where they lie, in pinned host memory: a wave reads one when its cursor moves to the next
 				// batch — a copy of 200 bytes in front of the launch was 10 us on the stream, a tenth of what four batches take)
-				(void)db;
 				sk_fused_args first = batches[0];
 				for (int i = 0; i < n_batches; i++) if (batches[i].n > 0) { first = batches[i]; break; }
 				sk::TileArgs t = tile_args_of(c, &first);
@@ -1016,77 +1047,36 @@ int sk_fused_pass(sk_ctx *c, const sk_fused_args *a)
 	if (a->n == 0) return SK_OK;
 	if (int r = prepare_demux(c, a)) return r;
 	const int64_t stride = a->stride;
-	// bytes of workspace per row
-	size_t per_row = 0;
+	sk_fused_args d = *a;                                      // the chunk on the device: every pointer below is set by stage_in()
+	d.counts = nullptr;
+	Stage cols;
 	for (int m = 0; m < a->n_mates; m++) {
 		const sk_mate &mt = a->mate[m];
+		sk_mate &dm = d.mate[m];
+		dm = sk_mate{nullptr, nullptr, nullptr, nullptr, nullptr};
 		if (!mt.out_seq && !mt.lowest_k) continue;
-		per_row += (size_t)stride;                         // qual
-		if (mt.out_seq) per_row += 2 * (size_t)stride;     // seq + out
-		if (mt.len) per_row += 2;
-		if (mt.lowest_k) per_row += 2;
+		cols.add(dm.qual, stride, kIn, mt.qual);
+		if (mt.out_seq) { cols.add(dm.seq, stride, kIn, mt.seq); cols.add(dm.out_seq, stride, kOut, mt.out_seq); }
+		if (mt.len) cols.add(dm.len, 2, kIn, mt.len);
+		if (mt.lowest_k) cols.add(dm.lowest_k, 2, kOut, mt.lowest_k);
 	}
-	if (a->bc) per_row += (size_t)a->bc_stride + 4 + 1 + 2 + 2;
-	int64_t chunk = (int64_t)(pipe_chunk(kPipeChunkBytes) / (per_row ? per_row : 1));
-	chunk &= ~(int64_t)63;
-	if (chunk < 64) chunk = 64;
-	if (chunk > a->n) chunk = (a->n + 63) & ~(int64_t)63;
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin((size_t)chunk * per_row + 64 * 256)) return r;
-
-	for (int64_t r0 = 0; r0 < a->n; r0 += chunk, pipe.next()) {
-		const int64_t nr = (a->n - r0) < chunk ? (a->n - r0) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *p = pipe.ws();
-		auto carve = [&](size_t bytes) { uint8_t *q = p; p += up256(bytes); return q; };
-		sk_fused_args d = *a;
-		d.n = nr; d.counts = nullptr;
-		for (int m = 0; m < a->n_mates; m++) {
-			const sk_mate &mt = a->mate[m];
-			sk_mate &dm = d.mate[m];
-			dm = sk_mate{nullptr, nullptr, nullptr, nullptr, nullptr};
-			if (!mt.out_seq && !mt.lowest_k) continue;
-			uint8_t *dq = carve((size_t)nr * stride);
-			SK_HIP(c, hipMemcpyAsync(dq, mt.qual + r0 * stride, (size_t)nr * stride, hipMemcpyHostToDevice, st));
-			dm.qual = dq;
-			if (mt.out_seq) {
-				uint8_t *ds = carve((size_t)nr * stride);
-				SK_HIP(c, hipMemcpyAsync(ds, mt.seq + r0 * stride, (size_t)nr * stride, hipMemcpyHostToDevice, st));
-				dm.seq = ds;
-				dm.out_seq = carve((size_t)nr * stride);
-			}
-			if (mt.len) {
-				uint16_t *dl = (uint16_t *)carve((size_t)nr * 2);
-				SK_HIP(c, hipMemcpyAsync(dl, mt.len + r0, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-				dm.len = dl;
-			}
-			if (mt.lowest_k) dm.lowest_k = (uint16_t *)carve((size_t)nr * 2);
-		}
-		if (a->bc) {
-			uint8_t *db = carve((size_t)nr * a->bc_stride);
-			SK_HIP(c, hipMemcpyAsync(db, a->bc + r0 * a->bc_stride, (size_t)nr * a->bc_stride, hipMemcpyHostToDevice, st));
-			d.bc = db;
-			d.assign = (int32_t *)carve((size_t)nr * 4);
-			d.lowest_diff = a->lowest_diff ? carve((size_t)nr) : nullptr;
-			d.first_idx = a->first_idx ? (int16_t *)carve((size_t)nr * 2) : nullptr;
-			d.last_idx = a->last_idx ? (int16_t *)carve((size_t)nr * 2) : nullptr;
-		}
+	if (a->bc) {                                               // (the budget counts the three detail columns whether they are asked for or not)
+		cols.add(d.bc, a->bc_stride, kIn, a->bc);
+		cols.add(d.assign, 4, kOut, a->assign);
+		cols.add(d.lowest_diff, 1, kOut, a->lowest_diff);
+		cols.add(d.first_idx, 2, kOut, a->first_idx);
+		cols.add(d.last_idx, 2, kOut, a->last_idx);
+	}
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(a->n, cols.rows_for_bytes(pipe_chunk(kPipeChunkBytes), 64, a->n))) return r;
+	for (; pipe.more(); pipe.next()) {
+		d.n = pipe.nr;
+		if (int r = pipe.stage_in()) return r;
 		sk::TileArgs t = tile_args_of(c, &d);
 		if (t.table.count_rep && (pipe.k & 1)) t.table.count_rep += c->count_rep_set;     // the second lane's set of counter copies
 		if (t.bc && t.counts_wide) c->wide_dirty = true;
-		SK_HIP(c, sk::launch_tile_pass(t, c->n_cu, st));
-		for (int m = 0; m < a->n_mates; m++) {
-			const sk_mate &mt = a->mate[m];
-			const sk_mate &dm = d.mate[m];
-			if (mt.out_seq) SK_HIP(c, hipMemcpyAsync(mt.out_seq + r0 * stride, dm.out_seq, (size_t)nr * stride, hipMemcpyDeviceToHost, st));
-			if (mt.lowest_k) SK_HIP(c, hipMemcpyAsync(mt.lowest_k + r0, dm.lowest_k, (size_t)nr * 2, hipMemcpyDeviceToHost, st));
-		}
-		if (a->bc) {
-			SK_HIP(c, hipMemcpyAsync(a->assign + r0, d.assign, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
-			if (a->lowest_diff) SK_HIP(c, hipMemcpyAsync(a->lowest_diff + r0, d.lowest_diff, (size_t)nr, hipMemcpyDeviceToHost, st));
-			if (a->first_idx) SK_HIP(c, hipMemcpyAsync(a->first_idx + r0, d.first_idx, (size_t)nr * 2, hipMemcpyDeviceToHost, st));
-			if (a->last_idx) SK_HIP(c, hipMemcpyAsync(a->last_idx + r0, d.last_idx, (size_t)nr * 2, hipMemcpyDeviceToHost, st));
-		}
+		SK_HIP(c, sk::launch_tile_pass(t, c->n_cu, pipe.st()));
+		if (int r = pipe.stage_out()) return r;
 	}
 	return pipe.end();
 }
@@ -1312,19 +1302,16 @@ int sk_mask_by_quality(sk_ctx *c, uint8_t *seq, const uint8_t *qual, const uint1
 	(void)len;   // pad bytes of the output are unspecified: the whole matrix is one byte stream
 	if (int r = bind(c)) return r;
 	const int64_t total = n * (int64_t)stride;
-	int64_t chunk = (int64_t)pipe_chunk((size_t)16 << 20);
-	if (chunk > total) chunk = (total + 15) & ~(int64_t)15;
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin((size_t)up256((size_t)chunk) * 3)) return r;
+	uint8_t *ds, *dq, *dout;
+	Stage cols;
+	cols.add(ds, 1, kIn, seq); cols.add(dq, 1, kIn, qual); cols.add(dout, 1, kOut, seq);
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(total, rows_per_chunk(pipe_chunk((size_t)16 << 20), 16, total))) return r;
 	sk::QualConsts qc = sk::make_qual_consts(min_baseq);
-	for (int64_t o = 0; o < total; o += chunk, pipe.next()) {
-		const int64_t nb = (total - o) < chunk ? (total - o) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *ds = pipe.ws(), *dq = ds + up256((size_t)chunk), *dout = ds + 2 * up256((size_t)chunk);
-		SK_HIP(c, hipMemcpyAsync(ds, seq + o, (size_t)nb, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dq, qual + o, (size_t)nb, hipMemcpyHostToDevice, st));
-		SK_HIP(c, sk::launch_mask_flat(ds, dq, dout, nb, qc, c->n_cu, st));
-		SK_HIP(c, hipMemcpyAsync(seq + o, dout, (size_t)nb, hipMemcpyDeviceToHost, st));
+	for (; pipe.more(); pipe.next()) {
+		if (int r = pipe.stage_in()) return r;
+		SK_HIP(c, sk::launch_mask_flat(ds, dq, dout, pipe.nr, qc, c->n_cu, pipe.st()));
+		if (int r = pipe.stage_out()) return r;
 	}
 	return pipe.end();
 }
@@ -1353,29 +1340,19 @@ int sk_bam_flag_tlen(sk_ctx *c, const uint16_t *flag, const int32_t *tid, const 
 	if (!counters && !hist) return fail(c, SK_ERR_INVALID, "nothing to do");
 	if (int r = bind(c)) return r;
 	const size_t nout = 4 + (hist ? (size_t)max_frag + 1 : 0);
-	int64_t chunk = (int64_t)pipe_chunk((size_t)4 << 20);
-	if (chunk > n) chunk = n;
-	const size_t cols = up256((size_t)chunk * 2) + 3 * up256((size_t)chunk * 4);
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin(cols, up256(nout * 8))) return r;
+	const Dir core = hist ? kIn : kDev;                           // counters alone read the flags only
+	uint16_t *dflag;
+	int32_t *dtid, *dmtid, *dtlen;
+	Stage cols;
+	cols.add(dflag, 2, kIn, flag); cols.add(dtid, 4, core, tid); cols.add(dmtid, 4, core, mtid); cols.add(dtlen, 4, core, tlen);
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(n, rows_per_chunk(pipe_chunk((size_t)4 << 20), 1, n), nout * 8)) return r;
 	unsigned long long *dout = (unsigned long long *)pipe.tail();
 	SK_HIP(c, hipMemsetAsync(dout, 0, nout * 8, c->stream));
 	SK_HIP(c, hipStreamSynchronize(c->stream));                   // both lanes add into dout
-	for (int64_t o = 0; o < n; o += chunk, pipe.next()) {
-		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *p = pipe.ws();
-		uint16_t *dflag = (uint16_t *)p; p += up256((size_t)chunk * 2);
-		int32_t *dtid = (int32_t *)p; p += up256((size_t)chunk * 4);
-		int32_t *dmtid = (int32_t *)p; p += up256((size_t)chunk * 4);
-		int32_t *dtlen = (int32_t *)p;
-		SK_HIP(c, hipMemcpyAsync(dflag, flag + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-		if (hist) {
-			SK_HIP(c, hipMemcpyAsync(dtid, tid + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-			SK_HIP(c, hipMemcpyAsync(dmtid, mtid + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-			SK_HIP(c, hipMemcpyAsync(dtlen, tlen + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-		}
-		SK_HIP(c, sk::launch_bam_flag_tlen(dflag, dtid, dmtid, dtlen, nr, max_frag, dout, counters ? 1 : 0, hist ? 1 : 0, c->n_cu, st));
+	for (; pipe.more(); pipe.next()) {
+		if (int r = pipe.stage_in()) return r;
+		SK_HIP(c, sk::launch_bam_flag_tlen(dflag, dtid, dmtid, dtlen, pipe.nr, max_frag, dout, counters ? 1 : 0, hist ? 1 : 0, c->n_cu, pipe.st()));
 	}
 	if (int r = pipe.end()) return r;
 	std::vector<uint64_t> h(nout);
@@ -1484,24 +1461,28 @@ int sk_bgzf_deflate(sk_ctx *c, const uint8_t *in, size_t in_bytes, const sk_defl
 			return fail(c, SK_ERR_INVALID, "block %lld: %u bytes at %llu of %zu (at most %d a block)", (long long)i, blocks[i].in_len, (unsigned long long)blocks[i].in_off, in_bytes, SK_DEFLATE_MAX_IN);
 	if (int r = bind(c)) return r;
 	const size_t n = (size_t)n_blocks;
-	const size_t b_in = up256(in_bytes + 8), b_blk = up256(n * sizeof(sk_deflate_block)), b_slots = up256(n * (size_t)SK_DEFLATE_SLOT);
-	const size_t b_tok = up256(n * (size_t)SK_DEFLATE_MAX_IN * 4), b_res = up256(n * 8), b_crc = up256(n * 4);
-	if (int r = ensure_ws(c, b_in + b_blk + b_slots + b_tok + b_res + b_crc)) return r;
-	uint8_t *d_in = c->ws, *d_blk = d_in + b_in, *d_slots = d_blk + b_blk, *d_tok = d_slots + b_slots, *d_res = d_tok + b_tok, *d_crc = d_res + b_res;
-	// a pinned landing area for the slots (the ctx keeps it)
-	if (c->pin_bytes < b_slots) {
-		if (c->pin) { SK_HIP(c, hipHostFree(c->pin)); c->pin = nullptr; c->pin_bytes = 0; }
-		SK_HIP(c, hipHostMalloc((void **)&c->pin, b_slots + (b_slots >> 2), hipHostMallocDefault));
-		c->pin_bytes = b_slots + (b_slots >> 2);
-	}
+	const size_t b_slots = n * (size_t)SK_DEFLATE_SLOT;
+	uint8_t *d_in, *d_slots;
+	sk_deflate_block *d_blk;
+	uint32_t *d_tok, *d_res, *d_crc;
+	passmem::Layout ws;
+	ws.add(d_in, in_bytes + 8); ws.add(d_blk, n * sizeof(sk_deflate_block)); ws.add(d_slots, b_slots);
+	ws.add(d_tok, n * (size_t)SK_DEFLATE_MAX_IN * 4); ws.add(d_res, n * 8); ws.add(d_crc, n * 4);
+	if (int r = ensure_ws(c, ws.total())) return r;
+	ws.carve(c->ws);
+	// a pinned landing area for the slots (the ctx keeps it, a quarter larger than the call that made it grow asked for)
+	int krc = SK_OK;
+	const size_t have = sk::ctx_kept_bytes(c, sk::kKeepDeflatePin);
+	uint8_t *pin = (uint8_t *)sk::ctx_keep(c, sk::kKeepDeflatePin, have >= b_slots ? have : passmem::up(b_slots) + (passmem::up(b_slots) >> 2), true, &krc);
+	if (!pin) return krc;
 	SK_HIP(c, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
 	SK_HIP(c, hipMemsetAsync(d_in + in_bytes, 0, 8, c->stream));
 	SK_HIP(c, hipMemcpyAsync(d_blk, blocks, n * sizeof(sk_deflate_block), hipMemcpyHostToDevice, c->stream));
-	SK_HIP(c, sk::launch_bgzf_deflate(d_in, d_blk, n_blocks, d_slots, SK_DEFLATE_SLOT, (uint32_t *)d_tok, (uint32_t *)d_res, (uint32_t *)d_crc, c->n_cu, c->stream));
+	SK_HIP(c, sk::launch_bgzf_deflate(d_in, d_blk, n_blocks, d_slots, SK_DEFLATE_SLOT, d_tok, d_res, d_crc, c->n_cu, c->stream));
 	std::vector<uint32_t> res(2 * n), crc(n);
 	SK_HIP(c, hipMemcpyAsync(res.data(), d_res, n * 8, hipMemcpyDeviceToHost, c->stream));
 	SK_HIP(c, hipMemcpyAsync(crc.data(), d_crc, n * 4, hipMemcpyDeviceToHost, c->stream));
-	SK_HIP(c, hipMemcpyAsync(c->pin, d_slots, n * (size_t)SK_DEFLATE_SLOT, hipMemcpyDeviceToHost, c->stream));
+	SK_HIP(c, hipMemcpyAsync(pin, d_slots, b_slots, hipMemcpyDeviceToHost, c->stream));
 	SK_HIP(c, hipStreamSynchronize(c->stream));
 	static const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
 	size_t at = 0;
@@ -1521,7 +1502,7 @@ int sk_bgzf_deflate(sk_ctx *c, const uint8_t *in, size_t in_bytes, const sk_defl
 			m[21] = (uint8_t)(~len & 0xff); m[22] = (uint8_t)((~len >> 8) & 0xff);
 			memcpy(m + 23, in + blocks[i].in_off, len);
 		} else {
-			memcpy(m + 18, c->pin + i * (size_t)SK_DEFLATE_SLOT, pay);
+			memcpy(m + 18, pin + i * (size_t)SK_DEFLATE_SLOT, pay);
 		}
 		uint8_t *t = m + 18 + clen;
 		for (int k = 0; k < 4; k++) { t[k] = (uint8_t)(crc[i] >> (8 * k)); t[4 + k] = (uint8_t)(len >> (8 * k)); }
@@ -1553,29 +1534,21 @@ int sk_bam_fragments(sk_ctx *c, const uint16_t *flag, const int32_t *tid, const 
 	if (n == 0) return SK_OK;
 	if (!flag || !tid || !mtid || !tlen || !keep_bits) return fail(c, SK_ERR_INVALID, "NULL column or output");
 	if (int r = bind(c)) return r;
-	int64_t chunk = (int64_t)pipe_chunk((size_t)4 << 20);
-	if (chunk > n) chunk = (n + 7) & ~(int64_t)7;
-	const size_t need = up256((size_t)chunk * 2) + 3 * up256((size_t)chunk * 4) + up256((size_t)chunk / 8 + 8);
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin(need, 256)) return r;
+	uint16_t *dflag;
+	int32_t *dtid, *dmtid, *dtlen;
+	uint8_t *dbits;
+	Stage cols;
+	cols.add(dflag, 2, kIn, flag); cols.add(dtid, 4, kIn, tid); cols.add(dmtid, 4, kIn, mtid); cols.add(dtlen, 4, kIn, tlen);
+	cols.add_bits(dbits, 1, kOut, keep_bits);                     // one bit per row: a lane stores the byte of its 8 rows, clipped at the chunk's last
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(n, rows_per_chunk(pipe_chunk((size_t)4 << 20), 8, n), 8)) return r;      // whole bytes of keep_bits per chunk
 	unsigned long long *dkept = (unsigned long long *)pipe.tail();
 	SK_HIP(c, hipMemsetAsync(dkept, 0, 8, c->stream));
 	SK_HIP(c, hipStreamSynchronize(c->stream));                   // both lanes add into dkept
-	for (int64_t o = 0; o < n; o += chunk, pipe.next()) {         // chunk is a multiple of 8 records: byte-aligned in keep_bits
-		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *p = pipe.ws();
-		uint16_t *dflag = (uint16_t *)p; p += up256((size_t)chunk * 2);
-		int32_t *dtid = (int32_t *)p; p += up256((size_t)chunk * 4);
-		int32_t *dmtid = (int32_t *)p; p += up256((size_t)chunk * 4);
-		int32_t *dtlen = (int32_t *)p; p += up256((size_t)chunk * 4);
-		uint8_t *dbits = p;
-		SK_HIP(c, hipMemcpyAsync(dflag, flag + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dtid, tid + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dmtid, mtid + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dtlen, tlen + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-		SK_HIP(c, sk::launch_bam_fragments(dflag, dtid, dmtid, dtlen, nr, min_size, max_size, dbits, dkept, c->n_cu, st));
-		SK_HIP(c, hipMemcpyAsync(keep_bits + o / 8, dbits, (size_t)((nr + 7) / 8), hipMemcpyDeviceToHost, st));
+	for (; pipe.more(); pipe.next()) {
+		if (int r = pipe.stage_in()) return r;
+		SK_HIP(c, sk::launch_bam_fragments(dflag, dtid, dmtid, dtlen, pipe.nr, min_size, max_size, dbits, dkept, c->n_cu, pipe.st()));
+		if (int r = pipe.stage_out()) return r;
 	}
 	if (int r = pipe.end()) return r;
 	uint64_t k = 0;
@@ -1595,36 +1568,23 @@ int sk_count_set_regions(sk_ctx *c, int n_chr, const int32_t *chr_off, const uin
 	if (chr_off[0] != 0 || chr_off[n_chr] != n_regions) return fail(c, SK_ERR_INVALID, "chr_off must run from 0 to n_entries");
 	for (int k = 0; k < n_chr; k++) if (chr_off[k] > chr_off[k + 1]) return fail(c, SK_ERR_INVALID, "chr_off must not decrease");
 	if (int r = bind(c)) return r;
-	// sort each reference's regions by start (stable, like :63) and take the running maximum of their ends
-	std::vector<int32_t> order((size_t)n_regions);
-	for (int64_t i = 0; i < n_regions; i++) order[(size_t)i] = (int32_t)i;
-	for (int k = 0; k < n_chr; k++)
-		std::stable_sort(order.begin() + chr_off[k], order.begin() + chr_off[k + 1], [&](int32_t x, int32_t y) { return rstart[x] < rstart[y]; });
-	std::vector<uint32_t> s((size_t)n_regions), e((size_t)n_regions), pm((size_t)n_regions);
-	std::vector<int32_t> ix((size_t)n_regions);
-	for (int k = 0; k < n_chr; k++) {
-		uint32_t run = 0;
-		for (int32_t i = chr_off[k]; i < chr_off[k + 1]; i++) {
-			const int32_t o = order[(size_t)i];
-			const int32_t orig = ridx ? ridx[o] : o;
-			s[(size_t)i] = rstart[o]; e[(size_t)i] = rend[o]; ix[(size_t)i] = orig;
-			if (orig < 0 || orig >= n_counts) return fail(c, SK_ERR_INVALID, "ridx out of range");
-			run = std::max(run, rend[o]);
-			pm[(size_t)i] = run;
-		}
+	std::vector<uint32_t> s, pm, e((size_t)n_regions);
+	std::vector<int32_t> ix = regions_by_start<uint32_t>(n_chr, chr_off, rstart, rend, 0u, s, pm);
+	for (int64_t i = 0; i < n_regions; i++) {
+		const int32_t o = ix[(size_t)i];
+		e[(size_t)i] = rend[o];
+		ix[(size_t)i] = ridx ? ridx[o] : o;
+		if (ix[(size_t)i] < 0 || ix[(size_t)i] >= n_counts) return fail(c, SK_ERR_INVALID, "ridx out of range");
 	}
 	SK_HIP(c, hipStreamSynchronize(c->stream));
 	if (c->d_cnt) { SK_HIP(c, hipFree(c->d_cnt)); c->d_cnt = nullptr; }
-	const size_t b_off = up256((size_t)(n_chr + 1) * 4), b_reg = up256((size_t)n_regions * 4 + 4), b_cnt = up256((size_t)n_counts * 4 + 4);
-	hipError_t he = hipMalloc((void **)&c->d_cnt, b_off + 4 * b_reg + b_cnt);
+	const size_t b_reg = (size_t)n_regions * 4 + 4, b_cnt = passmem::up((size_t)n_counts * 4 + 4);
+	passmem::Layout tab;
+	tab.add(c->d_chr_off, (size_t)(n_chr + 1) * 4); tab.add(c->d_rstart, b_reg); tab.add(c->d_rend, b_reg); tab.add(c->d_rpmax, b_reg);
+	tab.add(c->d_ridx, b_reg); tab.add(c->d_region_frags, b_cnt);
+	hipError_t he = hipMalloc((void **)&c->d_cnt, tab.total());
 	if (he != hipSuccess) { c->d_cnt = nullptr; return fail(c, SK_ERR_NOMEM, "region tables: %s", hipGetErrorString(he)); }
-	uint8_t *p = c->d_cnt;
-	c->d_chr_off = (int32_t *)p; p += b_off;
-	c->d_rstart = (uint32_t *)p; p += b_reg;
-	c->d_rend = (uint32_t *)p; p += b_reg;
-	c->d_rpmax = (uint32_t *)p; p += b_reg;
-	c->d_ridx = (int32_t *)p; p += b_reg;
-	c->d_region_frags = (uint32_t *)p;
+	tab.carve(c->d_cnt);
 	SK_HIP(c, hipMemcpyAsync(c->d_chr_off, chr_off, (size_t)(n_chr + 1) * 4, hipMemcpyHostToDevice, c->stream));
 	if (n_regions) {
 		SK_HIP(c, hipMemcpyAsync(c->d_rstart, s.data(), (size_t)n_regions * 4, hipMemcpyHostToDevice, c->stream));
@@ -1675,27 +1635,17 @@ int sk_count_add(sk_ctx *c, const uint16_t *flag, const uint8_t *mapq, const int
 	if (int r = count_args(c, a, flag, mapq, tid, mtid, pos, mpos, tlen, end_pos, n, min_mapq, max_frag_len, single_end, center)) return r;
 	if (n == 0) return SK_OK;
 	if (int r = bind(c)) return r;
-	int64_t chunk = (int64_t)pipe_chunk((size_t)2 << 20);
-	if (chunk > n) chunk = n;
-	const size_t b2 = up256((size_t)chunk * 2), b1 = up256((size_t)chunk), b4 = up256((size_t)chunk * 4);
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin(b2 + b1 + 6 * b4)) return r;
-	const int32_t *hcol[6] = {tid, mtid, pos, mpos, tlen, end_pos};
-	for (int64_t o = 0; o < n; o += chunk, pipe.next()) {
-		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *p = pipe.ws();
-		uint16_t *dflag = (uint16_t *)p; p += b2;
-		uint8_t *dmapq = p; p += b1;
-		int32_t *dcol[6];
-		for (int k = 0; k < 6; k++) { dcol[k] = (int32_t *)p; p += b4; }
-		SK_HIP(c, hipMemcpyAsync(dflag, flag + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dmapq, mapq + o, (size_t)nr, hipMemcpyHostToDevice, st));
-		for (int k = 0; k < 6; k++)
-			if (hcol[k]) SK_HIP(c, hipMemcpyAsync(dcol[k], hcol[k] + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-		a.flag = dflag; a.mapq = dmapq; a.tid = dcol[0]; a.mtid = dcol[1]; a.pos = dcol[2]; a.mpos = dcol[3]; a.tlen = dcol[4]; a.end_pos = dcol[5];
-		a.n = nr;
-		SK_HIP(c, sk::launch_bam_count(a, c->n_cu, st));
+	Stage cols;
+	// (a column the caller leaves out — the other mode's — is carved all the same: the kernel is handed no NULL)
+	auto col4 = [&](const int32_t *&dev, const int32_t *host) { cols.add(dev, 4, host ? kIn : kDev, host); };
+	cols.add(a.flag, 2, kIn, flag); cols.add(a.mapq, 1, kIn, mapq);
+	col4(a.tid, tid); col4(a.mtid, mtid); col4(a.pos, pos); col4(a.mpos, mpos); col4(a.tlen, tlen); col4(a.end_pos, end_pos);
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(n, rows_per_chunk(pipe_chunk((size_t)2 << 20), 1, n))) return r;
+	for (; pipe.more(); pipe.next()) {
+		a.n = pipe.nr;
+		if (int r = pipe.stage_in()) return r;
+		SK_HIP(c, sk::launch_bam_count(a, c->n_cu, pipe.st()));
 	}
 	return pipe.end();
 }
@@ -1720,31 +1670,17 @@ int sk_on_target_set_regions(sk_ctx *c, int n_chr, const int32_t *chr_off, const
 	if (chr_off[0] != 0 || chr_off[n_chr] != n_entries) return fail(c, SK_ERR_INVALID, "chr_off must run from 0 to n_entries");
 	for (int k = 0; k < n_chr; k++) if (chr_off[k] > chr_off[k + 1]) return fail(c, SK_ERR_INVALID, "chr_off must not decrease");
 	if (int r = bind(c)) return r;
-	// sort each reference's regions by start (src/sam_statistics.rs:51-53) and take the running maximum of their ends
-	std::vector<int32_t> order((size_t)n_entries);
-	for (int64_t i = 0; i < n_entries; i++) order[(size_t)i] = (int32_t)i;
-	for (int k = 0; k < n_chr; k++)
-		std::sort(order.begin() + chr_off[k], order.begin() + chr_off[k + 1], [&](int32_t x, int32_t y) { return rstart[x] < rstart[y]; });
-	std::vector<int64_t> s((size_t)n_entries), pm((size_t)n_entries);
-	for (int k = 0; k < n_chr; k++) {
-		int64_t run = INT64_MIN;
-		for (int32_t i = chr_off[k]; i < chr_off[k + 1]; i++) {
-			const int32_t o = order[(size_t)i];
-			s[(size_t)i] = rstart[o];
-			run = std::max(run, rend[o]);
-			pm[(size_t)i] = run;
-		}
-	}
+	std::vector<int64_t> s, pm;
+	regions_by_start<int64_t>(n_chr, chr_off, rstart, rend, INT64_MIN, s, pm);
 	SK_HIP(c, hipStreamSynchronize(c->stream));
 	if (c->d_ot) { SK_HIP(c, hipFree(c->d_ot)); c->d_ot = nullptr; }
-	const size_t b_off = up256((size_t)(n_chr + 1) * 4), b_reg = up256((size_t)n_entries * 8 + 8), b_cnt = up256(6 * 8);
-	hipError_t he = hipMalloc((void **)&c->d_ot, b_off + 2 * b_reg + b_cnt);
+	const size_t b_cnt = passmem::up(6 * 8);
+	passmem::Layout tab;
+	tab.add(c->d_ot_chr_off, (size_t)(n_chr + 1) * 4); tab.add(c->d_ot_rstart, (size_t)n_entries * 8 + 8); tab.add(c->d_ot_rpmax, (size_t)n_entries * 8 + 8);
+	tab.add(c->d_ot_counters, b_cnt);
+	hipError_t he = hipMalloc((void **)&c->d_ot, tab.total());
 	if (he != hipSuccess) { (void)hipGetLastError(); c->d_ot = nullptr; return fail(c, SK_ERR_NOMEM, "target region tables: %s", hipGetErrorString(he)); }
-	uint8_t *p = c->d_ot;
-	c->d_ot_chr_off = (int32_t *)p; p += b_off;
-	c->d_ot_rstart = (int64_t *)p; p += b_reg;
-	c->d_ot_rpmax = (int64_t *)p; p += b_reg;
-	c->d_ot_counters = (unsigned long long *)p;
+	tab.carve(c->d_ot);
 	SK_HIP(c, hipMemcpyAsync(c->d_ot_chr_off, chr_off, (size_t)(n_chr + 1) * 4, hipMemcpyHostToDevice, c->stream));
 	if (n_entries) {
 		SK_HIP(c, hipMemcpyAsync(c->d_ot_rstart, s.data(), (size_t)n_entries * 8, hipMemcpyHostToDevice, c->stream));
@@ -1788,24 +1724,15 @@ int sk_on_target_add(sk_ctx *c, const uint16_t *flag, const int32_t *tid, const 
 	if (int r = on_target_args(c, a, flag, tid, mtid, pos, mpos, tlen, end_pos, n, max_frag_len)) return r;
 	if (n == 0) return SK_OK;
 	if (int r = bind(c)) return r;
-	int64_t chunk = (int64_t)pipe_chunk((size_t)2 << 20);
-	if (chunk > n) chunk = n;
-	const size_t b2 = up256((size_t)chunk * 2), b4 = up256((size_t)chunk * 4);
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin(b2 + 6 * b4)) return r;
-	const int32_t *hcol[6] = {tid, mtid, pos, mpos, tlen, end_pos};
-	for (int64_t o = 0; o < n; o += chunk, pipe.next()) {
-		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *p = pipe.ws();
-		uint16_t *dflag = (uint16_t *)p; p += b2;
-		int32_t *dcol[6];
-		for (int k = 0; k < 6; k++) { dcol[k] = (int32_t *)p; p += b4; }
-		SK_HIP(c, hipMemcpyAsync(dflag, flag + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-		for (int k = 0; k < 6; k++) SK_HIP(c, hipMemcpyAsync(dcol[k], hcol[k] + o, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-		a.flag = dflag; a.tid = dcol[0]; a.mtid = dcol[1]; a.pos = dcol[2]; a.mpos = dcol[3]; a.tlen = dcol[4]; a.end_pos = dcol[5];
-		a.n = nr;
-		SK_HIP(c, sk::launch_bam_target(a, c->n_cu, st));
+	Stage cols;
+	cols.add(a.flag, 2, kIn, flag); cols.add(a.tid, 4, kIn, tid); cols.add(a.mtid, 4, kIn, mtid); cols.add(a.pos, 4, kIn, pos);
+	cols.add(a.mpos, 4, kIn, mpos); cols.add(a.tlen, 4, kIn, tlen); cols.add(a.end_pos, 4, kIn, end_pos);
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(n, rows_per_chunk(pipe_chunk((size_t)2 << 20), 1, n))) return r;
+	for (; pipe.more(); pipe.next()) {
+		a.n = pipe.nr;
+		if (int r = pipe.stage_in()) return r;
+		SK_HIP(c, sk::launch_bam_target(a, c->n_cu, pipe.st()));
 	}
 	return pipe.end();
 }
@@ -1859,11 +1786,13 @@ int sk_gc_count(sk_ctx *c, const int64_t *start, const int64_t *len, int64_t n_r
 		}
 	}
 	const size_t ns = sstart.size();
-	const size_t b_out = up256((size_t)n_regions * 16), b_s = up256(ns * 8 + 8), b_l = up256(ns * 4 + 4);
-	if (int r = ensure_ws(c, b_out + b_s + 2 * b_l)) return r;
-	unsigned long long *dout = (unsigned long long *)c->ws;
-	int64_t *dstart = (int64_t *)(c->ws + b_out);
-	int32_t *dlen = (int32_t *)(c->ws + b_out + b_s), *dreg = (int32_t *)(c->ws + b_out + b_s + b_l);
+	unsigned long long *dout;
+	int64_t *dstart;
+	int32_t *dlen, *dreg;
+	passmem::Layout ws;
+	ws.add(dout, (size_t)n_regions * 16); ws.add(dstart, ns * 8 + 8); ws.add(dlen, ns * 4 + 4); ws.add(dreg, ns * 4 + 4);
+	if (int r = ensure_ws(c, ws.total())) return r;
+	ws.carve(c->ws);
 	SK_HIP(c, hipMemsetAsync(dout, 0, (size_t)n_regions * 16, c->stream));
 	if (ns) {
 		SK_HIP(c, hipMemcpyAsync(dstart, sstart.data(), ns * 8, hipMemcpyHostToDevice, c->stream));
@@ -1908,24 +1837,18 @@ int sk_bam_sequence(sk_ctx *c, const uint8_t *seq4, int seq4_stride, const uint8
 	if (int r = bam_sequence_check(c, seq4, seq4_stride, qual, stride, flag, n, out)) return r;
 	if (n == 0) return SK_OK;
 	if (int r = bind(c)) return r;
-	const size_t per_row = (size_t)seq4_stride + 2 * (size_t)stride + 4;
-	int64_t chunk = (int64_t)(pipe_chunk(kPipeChunkBytes) / per_row);
-	if (chunk < 1) chunk = 1;
-	if (chunk > n) chunk = n;
-	const size_t b_seq = up256((size_t)chunk * seq4_stride), b_q = up256((size_t)chunk * stride), b_col = up256((size_t)chunk * 2);
-	ChunkPipe pipe(c);
-	if (int r = pipe.begin(b_seq + 2 * b_q + 2 * b_col)) return r;
-	for (int64_t o = 0; o < n; o += chunk, pipe.next()) {
-		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
-		hipStream_t st = pipe.st();
-		uint8_t *dseq = pipe.ws(), *dq = dseq + b_seq, *dout = dq + b_q;
-		uint16_t *dlen = (uint16_t *)(dout + b_q), *dflag = (uint16_t *)(dout + b_q + b_col);
-		SK_HIP(c, hipMemcpyAsync(dseq, seq4 + o * (int64_t)seq4_stride, (size_t)nr * seq4_stride, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dq, qual + o * (int64_t)stride, (size_t)nr * stride, hipMemcpyHostToDevice, st));
-		if (len) SK_HIP(c, hipMemcpyAsync(dlen, len + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-		SK_HIP(c, hipMemcpyAsync(dflag, flag + o, (size_t)nr * 2, hipMemcpyHostToDevice, st));
-		SK_HIP(c, sk::launch_bam_sequence(dseq, seq4_stride, dq, stride, len ? dlen : nullptr, dflag, nr, min_baseq, dout, c->n_cu, st));
-		SK_HIP(c, hipMemcpyAsync(out + o * (int64_t)stride, dout, (size_t)nr * stride, hipMemcpyDeviceToHost, st));
+	const uint8_t *dseq, *dq;
+	uint8_t *dout;
+	const uint16_t *dlen, *dflag;
+	Stage cols;
+	cols.add(dseq, seq4_stride, kIn, seq4); cols.add(dq, stride, kIn, qual); cols.add(dout, stride, kOut, out);
+	cols.add(dlen, 2, kIn, len); cols.add(dflag, 2, kIn, flag);
+	ChunkPipe pipe(c, cols);
+	if (int r = pipe.begin(n, cols.rows_for_bytes(pipe_chunk(kPipeChunkBytes), 1, n))) return r;
+	for (; pipe.more(); pipe.next()) {
+		if (int r = pipe.stage_in()) return r;
+		SK_HIP(c, sk::launch_bam_sequence(dseq, seq4_stride, dq, stride, dlen, dflag, pipe.nr, min_baseq, dout, c->n_cu, pipe.st()));
+		if (int r = pipe.stage_out()) return r;
 	}
 	return pipe.end();
 }
@@ -1977,16 +1900,19 @@ int sk_census_add(sk_ctx *c, const uint8_t *bc, int bc_stride, int L, int64_t n,
 	if (n == 0) return SK_OK;
 	if (int r = bind(c)) return r;
 	if (int r = census_ready(c)) return r;
-	int64_t chunk = (int64_t)(pipe_chunk((size_t)64 << 20) / (size_t)(bc_stride + 4));
-	if (chunk > n) chunk = n;
-	if (int r = ensure_ws(c, up256((size_t)chunk * bc_stride) + up256((size_t)chunk * 4))) return r;
-	uint8_t *dbc = c->ws;
-	int32_t *dassign = (int32_t *)(c->ws + up256((size_t)chunk * bc_stride));
-	for (int64_t o = 0; o < n; o += chunk) {
-		const int64_t nr = (n - o) < chunk ? (n - o) : chunk;
+	// one stream, one half: inserts of two lanes in flight would change which row is recorded as a key's first
+	uint8_t *dbc;
+	int32_t *dassign;
+	Stage cols;
+	cols.add(dbc, bc_stride, kIn, bc); cols.add(dassign, 4, kIn, assign);
+	cols.plan(cols.rows_for_bytes(pipe_chunk((size_t)64 << 20), 1, n), 0, 1);
+	if (int r = ensure_ws(c, cols.total())) return r;
+	cols.carve(c->ws);
+	for (int64_t o = 0; o < n; o += cols.chunk()) {
+		const int64_t nr = cols.rows_at(o, n);
 		SK_HIP(c, hipMemcpyAsync(dbc, bc + o * (int64_t)bc_stride, (size_t)nr * bc_stride, hipMemcpyHostToDevice, c->stream));
 		if (assign) SK_HIP(c, hipMemcpyAsync(dassign, assign + o, (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
-		SK_HIP(c, sk::census_add(c->census, dbc, bc_stride, L, nr, assign ? dassign : nullptr, row_base + o, c->n_cu, c->stream));
+		SK_HIP(c, sk::census_add(c->census, dbc, bc_stride, L, nr, dassign, row_base + o, c->n_cu, c->stream));
 		SK_HIP(c, hipStreamSynchronize(c->stream));
 	}
 	return SK_OK;

@@ -397,7 +397,8 @@ enum KeepSlot {
 	// Here lies what a call's windows read later — minimize's read ids, markdup's flag column, merge's input numbers — and behind it the
 	// passes' scratch of markdup, subsample, merge and coverage where the compressed file's idle buffer is too small for it.
 	kKeepPassWork = 12,
-	kKeepSlots = 13
+	kKeepDeflatePin = 13,                               // sk_bgzf_deflate: the pinned landing area of the compressed slots (a host may deflate while a file call's state is live)
+	kKeepSlots = 14
 };
 hipStream_t ctx_stream(sk_ctx *c);
 hipStream_t ctx_stream2(sk_ctx *c);

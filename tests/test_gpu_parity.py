@@ -1574,6 +1574,10 @@ def test_host_entry_points_in_many_chunks(ctx, oracle, monkeypatch, chunk_log2):
     counters, hist, total = ctx.bam_flag_tlen(flag, tid, mtid, tlen, 5000)
     ec, eh, et = oracle.bam_flag_tlen(flag, tid, mtid, tlen, 5000)
     assert np.array_equal(counters, ec) and np.array_equal(hist, eh) and total == et
+    # counters alone: tid, mtid, tlen and hist are NULL (the view always passes every column, so through the library itself)
+    alone = np.zeros(3, dtype=np.uint64)
+    ctx._check(ctx._lib.sk_bam_flag_tlen(ctx._h, flag.ctypes.data, None, None, None, len(flag), 5000, alone.ctypes.data, None, None), "sk_bam_flag_tlen")
+    assert np.array_equal(alone, ec)
     keep, kept = ctx.bam_fragments(flag, tid, mtid, tlen, 50, 700)
     ek = oracle.fragments_keep(flag, tid, mtid, tlen, 50, 700)
     assert np.array_equal(keep, ek) and kept == int(ek.sum())
@@ -1591,6 +1595,11 @@ def test_host_entry_points_in_many_chunks(ctx, oracle, monkeypatch, chunk_log2):
     chr_off, gs, ge, gi = grouped_regions(rchr, rstart, rend, n_chr)
     ctx.count_set_regions(chr_off, gs, ge, gi, n_regions=3000)
     ctx.count_add(**dict(cols, end_pos=None))
+    assert code == 0 and np.array_equal(ctx.count_get()[gi], want[gi])
+    # single-end: end_pos given; mtid, mpos and tlen are NULL
+    want, code, _ = oracle.count_batch(**cols, n_chr=n_chr, rchr=rchr, rstart=rstart, rend=rend, single_end=True)
+    ctx.count_set_regions(chr_off, gs, ge, gi, n_regions=3000)
+    ctx.count_add(**dict(cols, mtid=None, mpos=None, tlen=None), single_end=True)
     assert code == 0 and np.array_equal(ctx.count_get()[gi], want[gi])
 
 
