@@ -59,6 +59,8 @@ void sk_destroy(sk_ctx *ctx);
 const char *sk_last_error(const sk_ctx *ctx);            /* ctx may be NULL: last sk_create failure */
 int  sk_sync(sk_ctx *ctx);                               /* wait for everything enqueued on the ctx stream */
 void *sk_stream(sk_ctx *ctx);                            /* the ctx's hipStream_t, for interop */
+int  sk_planned_cus(sk_ctx *ctx);                        /* the CU count the ctx plans its launches with: the device's own,
+                                                          * unless SK_PLAN_CUS (tests only; read once, at creation) names a smaller one */
 
 /* ---- device / pinned memory for hosts that do not link HIP themselves ------------------------ */
 int sk_malloc_device(sk_ctx *ctx, size_t bytes, void **out);

@@ -21,7 +21,7 @@ SK_ASSIGN_AMBIGUOUS = -2
 
 # every symbol include/seqkit_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = [
-    "sk_version", "sk_device_count", "sk_create", "sk_destroy", "sk_last_error", "sk_sync", "sk_stream",
+    "sk_version", "sk_device_count", "sk_create", "sk_destroy", "sk_last_error", "sk_sync", "sk_stream", "sk_planned_cus",
     "sk_malloc_device", "sk_free_device", "sk_malloc_pinned", "sk_free_pinned", "sk_copy_h2d", "sk_copy_d2h",
     "sk_set_barcodes", "sk_set_detail_mode", "sk_barcode_table_info", "sk_demux_assign", "sk_demux_assign_dev", "sk_trim_by_quality", "sk_trim_by_quality_dev",
     "sk_mask_by_quality", "sk_mask_by_quality_dev", "sk_fused_pass", "sk_fused_pass_dev",
@@ -215,7 +215,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     protos = {
         "sk_version": (i32, []), "sk_device_count": (i32, []),
         "sk_create": (i32, [i32, C.POINTER(vp)]), "sk_destroy": (None, [vp]),
-        "sk_last_error": (C.c_char_p, [vp]), "sk_sync": (i32, [vp]), "sk_stream": (vp, [vp]),
+        "sk_last_error": (C.c_char_p, [vp]), "sk_sync": (i32, [vp]), "sk_stream": (vp, [vp]), "sk_planned_cus": (i32, [vp]),
         "sk_malloc_device": (i32, [vp, C.c_size_t, C.POINTER(vp)]), "sk_free_device": (i32, [vp, vp]),
         "sk_malloc_pinned": (i32, [vp, C.c_size_t, C.POINTER(vp)]), "sk_free_pinned": (i32, [vp, vp]),
         "sk_copy_h2d": (i32, [vp, vp, vp, C.c_size_t]), "sk_copy_d2h": (i32, [vp, vp, vp, C.c_size_t]),
@@ -581,6 +581,10 @@ class Context:
 
     def stream(self) -> int:
         return int(self._lib.sk_stream(self._h) or 0)
+
+    def planned_cus(self) -> int:
+        """The CU count this context plans its launches with (SK_PLAN_CUS at creation can only lower it: tests)."""
+        return int(self._lib.sk_planned_cus(self._h))
 
     def malloc_device(self, nbytes: int) -> int:
         p = C.c_void_p()

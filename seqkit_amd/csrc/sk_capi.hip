@@ -256,6 +256,11 @@ int sk_create(int device_id, sk_ctx **out)
 	sk_ctx *c = new sk_ctx();
 	c->device = device_id;
 	c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+	if (const char *ev = getenv("SK_PLAN_CUS")) {      // tests: a smaller planning count, so capped grids loop at test sizes; never a larger one
+		char *end = nullptr;
+		const long v = strtol(ev, &end, 10);
+		if (end != ev && *end == '\0' && v >= 1 && v <= (long)prop.multiProcessorCount) c->n_cu = (int)v;
+	}
 	e = hipSetDevice(device_id);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking);
@@ -310,6 +315,8 @@ int sk_sync(sk_ctx *c)
 }
 
 void *sk_stream(sk_ctx *c) { return c ? (void *)c->stream : nullptr; }
+
+int sk_planned_cus(sk_ctx *c) { return c ? c->n_cu : 0; }
 
 int sk_malloc_device(sk_ctx *c, size_t bytes, void **out)
 {

@@ -60,11 +60,11 @@ def header(text, refs):
     return raw
 
 
-def bgzf(raw, piece=0xFF00):
+def bgzf(raw, piece=0xFF00, level=6):
     out = []
     for o in range(0, len(raw), piece):
         data = raw[o:o + piece]
-        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
         comp = c.compress(data) + c.flush()
         out.append(struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(comp) + 25) + comp
                    + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
@@ -76,10 +76,11 @@ REFS = [(b"chr1", 248956422), (b"chr2", 242193529), (b"chrM", 16569)]
 TEXT = b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % r for r in REFS) + b"@PG\tID:x\n\n\n" + b"\0" * 7
 
 
-def write(path, recs, text=TEXT, refs=REFS, piece=0xFF00):
+def write(path, recs, text=TEXT, refs=REFS, piece=0xFF00, level=6):
+    """piece: the inflated bytes of a BGZF block; level: zlib's (1 writes a large file cheaply, 0 stores)"""
     raw = header(text, refs) + b"".join(recs)
     with open(path, "wb") as f:
-        f.write(bgzf(raw, piece))
+        f.write(bgzf(raw, piece, level))
     return raw
 
 

@@ -37,10 +37,10 @@ def bgzf_member(comp: bytes, data: bytes) -> bytes:
     return hdr + comp + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data) & 0xFFFFFFFF)
 
 
-def write_bam(path, refs, records, truncate=None):
+def write_bam(path, refs, records, truncate=None, piece=60000):
     """refs: [(name, length)], records: dicts with tid,pos,flag,mtid,mpos,tlen,name,cigar[(op,len)],seq_len; optional
     `codes` (one 4-bit BAM base code per base) and `qual` (raw phred per base) give the record real bases; `name` may be
-    bytes."""
+    bytes.  `piece`: the inflated bytes of a BGZF block."""
     raw = b"BAM\1"
     text = b"@HD\tVN:1.6\tSO:coordinate\n"
     raw += struct.pack("<i", len(text)) + text + struct.pack("<i", len(refs))
@@ -65,6 +65,6 @@ def write_bam(path, refs, records, truncate=None):
     if truncate is not None:
         raw = raw[:truncate]
     with open(path, "wb") as f:
-        for i in range(0, len(raw), 60000):
-            f.write(bgzf_block(raw[i:i + 60000]))
+        for i in range(0, len(raw), piece):
+            f.write(bgzf_block(raw[i:i + piece]))
         f.write(bgzf_block(b""))
