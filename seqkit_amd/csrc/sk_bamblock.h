@@ -1,16 +1,22 @@
 // sk_bamblock.h — what the per-block passes over a verified BAM stream share (sk_inflate.hip: bam_gather_kernel; sk_bamtext.hip: the
-// reads passes; sk_bamwrite.hip: the rewrite passes; sk_bamminimize.hip: the minimize passes).  Such a pass is a wave per BGZF block:
-// lane 0 follows the chain of records from the block's entry to its end and leaves every record's offset in LDS, then the 64 lanes
-// take consecutive records.  Also the name hash (reads, minimize), the byte composition of `sam to`'s texts (sk_bamtext.hip,
-// sk_bampair.hip) and the span copy of the window writers (rewrite, pack, minimize).
+// reads passes; sk_bamwrite.hip, sk_bamminimize.hip, sk_bammarkdup.hip, sk_bammerge.hip, sk_bamcoverage.hip: theirs).  Such a pass is a
+// wave per BGZF block: lane 0 follows the chain of records from the block's entry to its end and leaves every record's offset in LDS,
+// then the 64 lanes take consecutive records: block_open is how such a kernel begins (two write it out, where they say why),
+// block_grid its launch, block_close_size how a sizing pass ends.  Also the name hash (reads, minimize), the byte composition of
+// `sam to`'s texts (sk_bamtext.hip, sk_bampair.hip), the span copy (emit) and, around it, the window writer of the BAM-writing calls:
+// bam_write_kernel and launch_bam_write over a command's record descriptor, on the grid rule (group_grid) that every window and
+// text writer is launched by.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sk_internal.h"
+
 namespace sk {
 
 // waves per workgroup, and the records that can begin in one block: each takes at least 36 bytes of its 64 KiB
-constexpr int kBlockWaves = 4, kBlockRecs = 1824;
+constexpr int kBlockWaves = 4, kBlockRecs = 1824, kBlockThreads = kBlockWaves * 64;
+inline unsigned block_grid(int64_t nb) { return (unsigned)((nb + kBlockWaves - 1) / kBlockWaves); }
 
 // four bytes at any alignment, little-endian: two aligned dwords and a byte shift (the buffer is readable to the next dword behind
 // its last byte; the inflated stream is, 64 bytes beyond)
@@ -50,6 +56,42 @@ __device__ __forceinline__ uint32_t wave_record_offsets(const uint8_t *stream, c
 	if (lane == 0) k = block_record_offsets(stream, entry[c], bend[c], off);
 	__builtin_amdgcn_wave_barrier();
 	return (uint32_t)__shfl((int)k, 0);
+}
+
+// How a per-block pass begins: this wave's lane and block c, the block's entry, and the offsets (from entry) of its n records in the
+// wave's own part of the workgroup's LDS.  false: there is no block for this wave, and the kernel returns.  No workgroup barrier may
+// follow in such a kernel: the waves without a block have left, and each wave uses its own LDS.
+struct BlockPass {
+	int lane;
+	int64_t c;
+	unsigned long long entry;
+	uint32_t n;
+	const uint16_t *off;
+};
+__device__ __forceinline__ bool block_open(const uint8_t *stream, const unsigned long long *entry, const unsigned long long *bend, int64_t nb, BlockPass &b)
+{
+	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
+	const int w = threadIdx.x >> 6;
+	b.lane = threadIdx.x & 63;
+	b.c = (int64_t)blockIdx.x * kBlockWaves + w;
+	if (b.c >= nb) return false;
+	b.off = offs[w];
+	b.n = wave_record_offsets(stream, entry, bend, b.c, offs[w], b.lane);
+	b.entry = entry[b.c];
+	return true;
+}
+
+// How a sizing pass ends: the lanes' output bytes summed and their records' decline bits ORed over the wave, then lane 0 stores
+__device__ __forceinline__ void block_close_size(unsigned long long bytes, uint32_t dec, int lane, unsigned long long *block_bytes, uint32_t *decline)
+{
+	for (int s = 32; s > 0; s >>= 1) {
+		bytes += __shfl_xor(bytes, s);
+		dec |= (uint32_t)__shfl_xor((int)dec, s);
+	}
+	if (lane == 0) {
+		*block_bytes = bytes;
+		if (dec) atomicOr(decline, dec);
+	}
 }
 
 // inclusive prefix sum over the wave's 64 lanes
@@ -125,6 +167,39 @@ __device__ __forceinline__ void emit(uint8_t *out, unsigned long long o0, unsign
 			}
 		}
 	}
+}
+
+// ---- a window's records, 16 lanes a record (the window writers here; the text writers of sk_bamtext.hip and sk_bampair.hip) ----
+constexpr int kGroupThreads = 256;               // a workgroup: 16 groups of 16 lanes, a record a group
+// a group per record, at most 16 workgroups a planned CU: the groups stride over the rest
+inline unsigned group_grid(int64_t n, int n_cu)
+{
+	const int64_t want = (n + kGroupThreads / 16 - 1) / (kGroupThreads / 16), cap = (int64_t)(n_cu > 0 ? n_cu : 256) * 16;
+	return (unsigned)(want < cap ? want : cap);
+}
+
+// The window writer of the BAM-writing calls.  What a command makes of a record is its descriptor `rec`, passed by value with the
+// command's device pointers and flags: rec(r, k, put) reads record k at r and calls put(len, <the three spans of emit>, byte) once.
+template <class Rec>
+__global__ __launch_bounds__(kGroupThreads) void bam_write_kernel(const WriteWindow w, const Rec rec)
+{
+	const uint32_t gl = threadIdx.x & 15u;
+	const int64_t gstride = ((int64_t)gridDim.x * kGroupThreads) >> 4;
+	for (int64_t j = ((int64_t)blockIdx.x * kGroupThreads + threadIdx.x) >> 4; j < w.n; j += gstride) {
+		const int64_t k = w.first + j;
+		rec(w.stream + w.krec[k], k, [&](unsigned long long len, uint32_t ro0, uint32_t rl0, const uint8_t *src0, uint32_t ro1, uint32_t rl1,
+		                                 const uint8_t *src1, uint32_t ro2, uint32_t rl2, const uint8_t *src2, const auto &byte) {
+			emit(w.out, w.kout[k] - w.o0, len, ro0, rl0, src0, ro1, rl1, src1, ro2, rl2, src2, byte, gl, 16u);
+		});
+	}
+}
+
+template <class Rec>
+hipError_t launch_bam_write(const WriteWindow &w, const Rec &rec, int n_cu, hipStream_t st)
+{
+	if (w.n <= 0) return hipSuccess;
+	bam_write_kernel<<<group_grid(w.n, n_cu), kGroupThreads, 0, st>>>(w, rec);
+	return hipGetLastError();
 }
 
 }  // namespace sk

@@ -102,15 +102,11 @@ __device__ __forceinline__ void cov_set_bit(u32 *bits, int32_t tid)
 	if (!(bits[tid >> 5] & m)) atomicOr(bits + (tid >> 5), m);
 }
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_cov_mark_kernel(const CovDev d)
+__global__ __launch_bounds__(kBlockThreads) void bam_cov_mark_kernel(const CovDev d)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= d.nb) return;                                                 // (no workgroup barrier below: each wave uses its own LDS)
-	uint16_t *off = offs[w];
-	const u32 n = wave_record_offsets(d.stream, d.entry, d.bend, c, off, lane);
-	const u64 entry = d.entry[c];
+	BlockPass b;
+	if (!block_open(d.stream, d.entry, d.bend, d.nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
 	const CovArgs &a = d.a;
 	u64 runs = 0, counted = 0;
 	bool bad = false;
@@ -144,8 +140,9 @@ __global__ __launch_bounds__(kBlockWaves * 64) void bam_cov_mark_kernel(const Co
 	if (__any((int)bad) && lane == 0) atomicOr(a.decline, 8u);
 }
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_cov_emit_kernel(const CovDev d, u64 *key, u32 *kind)
+__global__ __launch_bounds__(kBlockThreads) void bam_cov_emit_kernel(const CovDev d, u64 *key, u32 *kind)
 {
+	// (block_open written out: with the helper this kernel measured 0.7 % slower, 1.909 against 1.896 ms on 20 M records)
 	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
@@ -236,7 +233,7 @@ CovDev cov_dev(const uint8_t *stream, const uint64_t *bend, const uint64_t *entr
 hipError_t launch_bam_cov_mark(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const CovArgs &a, hipStream_t st)
 {
 	if (nb > 0) {
-		bam_cov_mark_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(cov_dev(stream, bend, entry, nb, a));
+		bam_cov_mark_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(cov_dev(stream, bend, entry, nb, a));
 		if (hipError_t e = hipGetLastError()) return e;
 	}
 	return launch_scan_u64(a.bruns, nb, st);
@@ -246,7 +243,7 @@ hipError_t launch_bam_cov_emit(const uint8_t *stream, const uint64_t *bend, cons
                                uint32_t *kind, hipStream_t st)
 {
 	if (nb <= 0) return hipSuccess;
-	bam_cov_emit_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(cov_dev(stream, bend, entry, nb, a), (u64 *)key, kind);
+	bam_cov_emit_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(cov_dev(stream, bend, entry, nb, a), (u64 *)key, kind);
 	return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "../../include/seqkit_hip.h"
@@ -170,22 +171,16 @@ struct PairsState : WindowedState {
 	Window in[2] = {};                           // the window in buffer b
 };
 
-// Which of the rewrite-window calls is running — the kernel that writes a window's records — and what that kernel takes
-struct WriteOp {
-	enum Kind { kRewrite, kMinimize, kMarkdup, kSubsample, kMerge } kind = kRewrite;
-	int flags = 0;                               // kRewrite: SK_REWRITE_*; kMinimize: SK_MINIMIZE_*
-	uint8_t fill = 255;                          // kMinimize: the qualities' fill byte
-	const uint32_t *ids = nullptr;               // kMinimize: the read ids (ctx slot kKeepPassWork; nullptr without SK_MINIMIZE_READ_IDS)
-	const uint16_t *md_flags = nullptr;          // kMarkdup: every record's flag (ctx slot kKeepPassWork)
-	const uint8_t *merge_in = nullptr;           // kMerge: every output record's input number (ctx slot kKeepPassWork); nullptr without --suffix
-};
+// What writes a window's records for the rewrite-window call that is running: that call's launcher (sk_internal.h: launch_bam_*_write)
+// with the call's own arguments bound.  (Device columns among them lie in ctx slot kKeepPassWork, which lives as long as the windows.)
+typedef std::function<hipError_t(const sk::WriteWindow &w, int n_cu, hipStream_t st)> WindowWriter;
 
 // sk_bam_file_rewrite / sk_bam_file_minimize / sk_bam_file_markdup / sk_bam_file_subsample and sk_bam_file_rewrite_next: every written record's stream and output offsets
 // (device, ctx slot kKeepFileCols), the window plan (output bytes of window w from wo[w] on), the write kernel of the call that runs,
 // one device area for the window being rewritten and compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on
 // each side (ctx slots kKeepFileWin / kKeepFilePin)
 struct RewriteState : WindowedState {
-	WriteOp write;
+	WindowWriter write;
 	int level = 1;
 	uint64_t *krec = nullptr, *kout = nullptr;
 	std::vector<uint64_t> wo;

@@ -37,17 +37,7 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		if (!s.next_window(w)) return false;
 		first = (int64_t)s.ws[w]; n = (int64_t)(s.ws[w + 1] - s.ws[w]);
 		raw_len = s.wo[w + 1] - s.wo[w];
-		const WriteOp &op = s.write;
-		switch (op.kind) {
-		case WriteOp::kRewrite: e = sk::launch_bam_rw_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], op.flags, s.d_raw, sk::ctx_n_cu(c), st); break;
-		case WriteOp::kMinimize: e = sk::launch_bam_min_write(s.d_out, s.krec, s.kout, op.ids, first, n, s.wo[w], op.flags, op.fill, s.d_raw, sk::ctx_n_cu(c), st); break;
-		case WriteOp::kMarkdup: e = sk::launch_bam_md_write(s.d_out, s.krec, s.kout, op.md_flags, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
-		case WriteOp::kSubsample: e = sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st); break;
-		case WriteOp::kMerge:                                               // (krec: offsets from input 1's stream that reach every input's; without a suffix a record is one copied span)
-			e = op.merge_in ? sk::launch_bam_merge_write(s.d_out, s.krec, s.kout, op.merge_in, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st)
-			                : sk::launch_bam_sub_write(s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw, sk::ctx_n_cu(c), st);
-			break;
-		}
+		e = s.write(sk::WriteWindow{s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw}, sk::ctx_n_cu(c), st);
 	}
 	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
 	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
@@ -99,9 +89,9 @@ static int rw_open(sk_ctx *c, Cleanup &cl, const Front &fr, int blk_cols, RwOpen
 }
 
 // What they share once the stream and output offsets (s.krec, s.kout) of the N records that go out are there — every record of the file,
-// or for sk_bam_file_subsample the kept ones —: the window plan, the window area, and the header's members on their way.  `write`: the
-// kernel that writes a window; `total`: the records' output bytes.
-static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WriteOp &write, int level, uint64_t window_bytes, uint64_t N,
+// or for sk_bam_file_subsample the kept ones —: the window plan, the window area, and the header's members on their way.  `write`:
+// what writes a window; `total`: the records' output bytes.
+static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WindowWriter &write, int level, uint64_t window_bytes, uint64_t N,
                     uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
 {
 	RewriteState &s = *o.s;
@@ -175,7 +165,8 @@ extern "C" int sk_bam_file_rewrite(sk_ctx *c, const char *path, int op, int leve
 	BF_LEAVE_DECLINED(o.d_decline, 0);                                  // (1 trim panic, 2 unsupported tag, 4 long name, 8 invalid record, 16 aux: info[5] = -31 .. -61)
 	// ---- every record's stream and output offsets
 	BF_HIP(sk::launch_bam_rw_index(fr.d_out, fr.d_bend, fr.d_entry, nb, op, bo, o.d_rb, o.s->krec, o.s->kout, st));
-	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kRewrite, op}, level, window_bytes, fr.n_records, total, n_records, raw_bytes, handled, info);
+	const WindowWriter write = [op](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_rw_write(w, op, n_cu, s); };
+	return rw_begin(c, cl, fr, o, write, level, window_bytes, fr.n_records, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam minimize (include/seqkit_hip.h: sk_bam_file_minimize; the windows come from sk_bam_file_rewrite_next) ---
@@ -237,7 +228,9 @@ extern "C" int sk_bam_file_minimize(sk_ctx *c, const char *path, int flags, uint
 	BF_HIP(hipMemcpyAsync(&total, bo + nb, 8, hipMemcpyDeviceToHost, st));
 	BF_LEAVE_DECLINED(o.d_decline, 0);
 	BF_HIP(sk::launch_bam_min_index(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, flags, ids, bo, krec, kout, st));
-	return rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMinimize, flags, baseq_fill, ids}, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
+	// (ids: ctx slot kKeepPassWork; nullptr without SK_MINIMIZE_READ_IDS)
+	const WindowWriter write = [=](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_min_write(w, ids, flags, baseq_fill, n_cu, s); };
+	return rw_begin(c, cl, fr, o, write, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
 }
 
 // ---- sam mark duplicates (include/seqkit_hip.h: sk_bam_file_markdup; the windows come from sk_bam_file_rewrite_next) ---
@@ -310,7 +303,9 @@ extern "C" int sk_bam_file_markdup(sk_ctx *c, const char *path, int ignore_umi, 
 		BF_HIP(hipMemcpyAsync(&dups, d_count, 8, hipMemcpyDeviceToHost, st));
 		BF_HIP(hipStreamSynchronize(st));
 	}
-	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kMarkdup, 0, 255, nullptr, cols.nflag}, level, window_bytes, N, fr.stream_len - fr.first, n_records, raw_bytes, handled, info);
+	const uint16_t *nflag = cols.nflag;
+	const WindowWriter write = [nflag](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_md_write(w, nflag, n_cu, s); };
+	const int rc = rw_begin(c, cl, fr, o, write, level, window_bytes, N, fr.stream_len - fr.first, n_records, raw_bytes, handled, info);
 	if (rc == SK_OK && *handled && n_duplicates) *n_duplicates = (int64_t)dups;
 	return rc;
 }
@@ -383,7 +378,7 @@ extern "C" int sk_bam_file_subsample(sk_ctx *c, const char *path, float fraction
 		BF_HIP(sk::bam_sub_scans(sb.temp, &tb, len, pos, off, N, st));
 		BF_HIP(sk::launch_bam_sub_compact(krec, len, pos, off, N, o.s->krec, o.s->kout, st));
 	}
-	const int rc = rw_begin(c, cl, fr, o, WriteOp{WriteOp::kSubsample}, level, window_bytes, counts[1], counts[2], n_records, raw_bytes, handled, info);
+	const int rc = rw_begin(c, cl, fr, o, sk::launch_bam_copy_write, level, window_bytes, counts[1], counts[2], n_records, raw_bytes, handled, info);
 	if (rc == SK_OK && *handled && n_total) *n_total = (int64_t)counts[0];
 	return rc;
 }
@@ -495,9 +490,10 @@ extern "C" int sk_bam_file_merge(sk_ctx *c, const char *const *paths, int n_path
 		BF_HIP(hipStreamSynchronize(st));
 		if (suffix) kin = kb;
 	}
-	WriteOp op;
-	op.kind = WriteOp::kMerge; op.merge_in = kin;
-	return rw_begin(c, cl, all, o, op, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
+	// (krec: offsets from input 1's stream that reach every input's; without a suffix a record is one copied span)
+	WindowWriter write = sk::launch_bam_copy_write;
+	if (kin) write = [kin](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_merge_write(w, kin, n_cu, s); };
+	return rw_begin(c, cl, all, o, write, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
 }
 
 extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)

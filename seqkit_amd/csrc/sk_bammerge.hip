@@ -13,10 +13,10 @@
 // the shared stable radix sort of (key, index) (sk_bamminimize.hip: bam_sort_pairs).
 // bam_merge_gather_kernel — output place p takes the address, length and input number of record idx[p]; bam_merge_scan (rocprim, in
 //   place over n + 1 elements) then turns the lengths into output offsets, the total behind them.
-// bam_merge_write_kernel — with a suffix, a window's records: 16 lanes a record through emit.  The core behind block_size and the name
+// MergeRecord in bam_write_kernel (sk_bamblock.h) — with a suffix, a window's records: 16 lanes a record through emit.  The core behind block_size and the name
 //   without its NUL are one span of the source (bytes 13 ..), refID and pos a second, everything from the CIGAR on a third, all copied
 //   as whole dwords; block_size, l_read_name, '.', the digits, the NUL and the spans' edges go byte by byte.  Without a suffix a record
-//   is one copied span: sk_bamsubsample.hip's write kernel serves as it stands.
+//   is one copied span: sk_bamsubsample.hip's copy writer serves as it stands.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -44,16 +44,13 @@ __device__ __forceinline__ bool merge_valid(const uint8_t *r)
 	return !(bs < 32u || lo < 1u || S > 0x7fffffffu || 4ull * nc + lo + (((u64)S + 1) >> 1) + S > (u64)(bs - 32u));
 }
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_merge_key_kernel(const uint8_t *stream, const u64 *bend, const u64 *entry_of, int64_t nb, const u64 *rb,
+__global__ __launch_bounds__(kBlockThreads) void bam_merge_key_kernel(const uint8_t *stream, const u64 *bend, const u64 *entry_of, int64_t nb, const u64 *rb,
                                                                          u64 delta, u32 input, u32 sl, const MergeCols m, uint32_t *decline)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= nb) return;                                                   // (no workgroup barrier below: each wave uses its own LDS)
-	uint16_t *off = offs[w];
-	const u32 n = wave_record_offsets(stream, entry_of, bend, c, off, lane);
-	const u64 entry = entry_of[c], k0 = rb[c];
+	BlockPass b;
+	if (!block_open(stream, entry_of, bend, nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
+	const u64 k0 = rb[c];
 	u32 dec = 0u;
 	for (u32 j = (u32)lane; j < n; j += 64u) {
 		const uint8_t *r = stream + entry + off[j];
@@ -87,14 +84,12 @@ __global__ __launch_bounds__(kMergeThreads) void bam_merge_gather_kernel(const u
 	kin[p] = m.in[g];
 }
 
-__global__ __launch_bounds__(kMergeThreads) void bam_merge_write_kernel(const uint8_t *stream, const u64 *krec, const u64 *kout, const uint8_t *kin, int64_t first,
-                                                                        int64_t n, u64 o0, uint8_t *out)
-{
-	const u32 gl = threadIdx.x & 15u;
-	const int64_t gstride = ((int64_t)gridDim.x * kMergeThreads) >> 4;
-	for (int64_t j = ((int64_t)blockIdx.x * kMergeThreads + threadIdx.x) >> 4; j < n; j += gstride) {
-		const int64_t k = first + j;
-		const uint8_t *r = stream + krec[k];
+// bam_write_kernel's record: ".N" behind the name, N from the input column
+struct MergeRecord {
+	const uint8_t *kin;
+	template <class Put>
+	__device__ void operator()(const uint8_t *r, int64_t k, const Put &put) const
+	{
 		const u32 input = kin[k], sl = input >= 10u ? 3u : 2u;
 		const u32 bs = bam_le32_bytes(r), lo = r[12];
 		const u32 T = 35u + lo;                                            // where the old name's NUL stood: the suffix begins here
@@ -108,9 +103,9 @@ __global__ __launch_bounds__(kMergeThreads) void bam_merge_write_kernel(const ui
 			if (p > T + sl) return r[p - sl];
 			return '0' + ((sl == 3u && p == T + 1u) ? input / 10u : input % 10u);
 		};
-		emit(out, kout[k] - o0, len, 13u, T - 13u, r + 13, 4u, 8u, r + 4, T + sl + 1u, len - (T + sl + 1u), r + T + 1u, byte, gl, 16u);
+		put(len, 13u, T - 13u, r + 13, 4u, 8u, r + 4, T + sl + 1u, len - (T + sl + 1u), r + T + 1u, byte);
 	}
-}
+};
 
 unsigned merge_grid(uint64_t n) { return (unsigned)((n + kMergeThreads - 1) / kMergeThreads); }
 
@@ -120,7 +115,7 @@ hipError_t launch_bam_merge_keys(const uint8_t *stream, const uint64_t *bend, co
                                  uint32_t input, uint32_t suffix_len, const MergeCols &cols, uint32_t *decline, hipStream_t st)
 {
 	if (nb <= 0) return hipSuccess;
-	bam_merge_key_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(stream, (const u64 *)bend, (const u64 *)entry, nb,
+	bam_merge_key_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(stream, (const u64 *)bend, (const u64 *)entry, nb,
 	                                                                                                     (const u64 *)rb, delta, input, suffix_len, cols, decline);
 	return hipGetLastError();
 }
@@ -146,15 +141,9 @@ hipError_t bam_merge_scan(void *temp, size_t *temp_bytes, uint64_t *kout, uint64
 	return rocprim::exclusive_scan(temp, *temp_bytes, (u64 *)kout, (u64 *)kout, (u64)0, (size_t)n + 1, rocprim::plus<u64>(), st);
 }
 
-hipError_t launch_bam_merge_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint8_t *kin, int64_t first, int64_t n, uint64_t o0,
-                                  uint8_t *out, int n_cu, hipStream_t st)
+hipError_t launch_bam_merge_write(const WriteWindow &w, const uint8_t *kin, int n_cu, hipStream_t st)
 {
-	if (n <= 0) return hipSuccess;
-	int64_t grid = (n + kMergeThreads / 16 - 1) / (kMergeThreads / 16);
-	const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 256) * 16;
-	if (grid > cap) grid = cap;
-	bam_merge_write_kernel<<<(unsigned)grid, kMergeThreads, 0, st>>>(stream, (const u64 *)krec, (const u64 *)kout, kin, first, n, o0, out);
-	return hipGetLastError();
+	return launch_bam_write(w, MergeRecord{kin}, n_cu, st);
 }
 
 }  // namespace sk

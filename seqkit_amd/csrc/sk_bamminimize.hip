@@ -19,7 +19,7 @@
 //
 // The records.  min_plan says what the flags make of one record (the name replaced by the id's digits or kept; `set`: only core, name,
 // CIGAR, bases and qualities stay, the odd base count's pad nibble is cleared, the qualities are copied or filled), and
-// bam_min_size_kernel / bam_min_index_kernel / bam_min_write_kernel follow sk_bamwrite.hip's three passes: per-block sums and decline
+// bam_min_size_kernel / bam_min_index_kernel / MinRecord in bam_write_kernel follow sk_bamwrite.hip's three passes: per-block sums and decline
 // bits (32: a CIGAR operation code above 8, where rust-htslib's cigar() panics), every record's output offset, and a window's bytes —
 // the copied spans (core and kept name; CIGAR and bases; qualities or everything behind the name) as whole dwords through emit, the
 // rest byte by byte.
@@ -41,7 +41,7 @@ namespace {
 typedef uint32_t u32;
 typedef unsigned long long u64;
 
-constexpr int kMinThreads = 256;                  // write kernel: 16 groups of 16 lanes; scan kernels: 4 waves, a tile each
+constexpr int kMinThreads = 256;                  // scan kernels: 4 waves, a tile each
 constexpr u32 kTile = 1024;                       // elements a wave scans: 16 rounds of 64
 constexpr u32 kNoSrc = ~0u;                       // src of a record that takes no part (no record has this index: there are fewer than 2^32)
 
@@ -142,15 +142,12 @@ struct MinArgs {
 	u32 *idx;
 };
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_min_key_kernel(const MinArgs a)
+__global__ __launch_bounds__(kBlockThreads) void bam_min_key_kernel(const MinArgs a)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= a.nb) return;                                                 // (no workgroup barrier below: each wave uses its own LDS)
-	uint16_t *off = offs[w];
-	const u32 n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
-	const u64 entry = a.entry[c], k0 = a.rb[c];
+	BlockPass b;
+	if (!block_open(a.stream, a.entry, a.bend, a.nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
+	const u64 k0 = a.rb[c];
 	u32 dec = 0u;
 	for (u32 j = (u32)lane; j < n; j += 64u) {
 		const uint8_t *r = a.stream + entry + off[j];
@@ -279,15 +276,12 @@ __global__ __launch_bounds__(256) void bam_min_id_kernel(const u32 *src, const u
 }
 
 // ---- size, index, write ----
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_min_size_kernel(const MinArgs a)
+__global__ __launch_bounds__(kBlockThreads) void bam_min_size_kernel(const MinArgs a)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= a.nb) return;
-	uint16_t *off = offs[w];
-	const u32 n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
-	const u64 entry = a.entry[c], k0 = a.rb[c];
+	BlockPass b;
+	if (!block_open(a.stream, a.entry, a.bend, a.nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
+	const u64 k0 = a.rb[c];
 	u64 bytes = 0;
 	u32 dec = 0u;
 	for (u32 j = (u32)lane; j < n; j += 64u) {
@@ -300,25 +294,15 @@ __global__ __launch_bounds__(kBlockWaves * 64) void bam_min_size_kernel(const Mi
 		min_plan(r, a.flags, a.ids ? a.ids[k0 + j] : 0u, pl);
 		bytes += pl.out_len;
 	}
-	for (int s = 32; s > 0; s >>= 1) {
-		bytes += __shfl_xor(bytes, s);
-		dec |= (u32)__shfl_xor((int)dec, s);
-	}
-	if (lane == 0) {
-		a.bo[c] = bytes;
-		if (dec) atomicOr(a.decline, dec);
-	}
+	block_close_size(bytes, dec, lane, a.bo + c, a.decline);
 }
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_min_index_kernel(const MinArgs a)
+__global__ __launch_bounds__(kBlockThreads) void bam_min_index_kernel(const MinArgs a)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= a.nb) return;
-	uint16_t *off = offs[w];
-	const u32 n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
-	const u64 entry = a.entry[c], k0 = a.rb[c];
+	BlockPass b;
+	if (!block_open(a.stream, a.entry, a.bend, a.nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
+	const u64 k0 = a.rb[c];
 	u64 ob = a.bo[c];                                                      // where the block's output begins
 	for (u32 j0 = 0; j0 < n; j0 += 64u) {
 		const u32 j = j0 + (u32)lane;
@@ -330,21 +314,21 @@ __global__ __launch_bounds__(kBlockWaves * 64) void bam_min_index_kernel(const M
 	}
 }
 
-__global__ __launch_bounds__(kMinThreads) void bam_min_write_kernel(const uint8_t *stream, const u64 *krec, const u64 *kout, const u32 *ids, int64_t first,
-                                                                    int64_t n, u64 o0, int flags, u32 fill, uint8_t *out)
-{
-	const u32 gl = threadIdx.x & 15u;
-	const int64_t gstride = ((int64_t)gridDim.x * kMinThreads) >> 4;
-	for (int64_t j = ((int64_t)blockIdx.x * kMinThreads + threadIdx.x) >> 4; j < n; j += gstride) {
-		const int64_t k = first + j;
-		const uint8_t *r = stream + krec[k];
+// bam_write_kernel's record: the three spans of min_plan
+struct MinRecord {
+	const u32 *ids;
+	int flags;
+	u32 fill;
+	template <class Put>
+	__device__ void operator()(const uint8_t *r, int64_t k, const Put &put) const
+	{
 		const u32 id = ids ? ids[k] : 0u;
 		MinPlan pl;
 		min_plan(r, flags, id, pl);
 		auto byte = [&](u32 p) -> u32 { return min_byte(r, pl, flags, fill, id, p); };
-		emit(out, kout[k] - o0, pl.out_len, 13u, pl.s0l, r + 13, pl.T0, pl.s1l, r + pl.tail_s, pl.s2o, pl.s2l, r + pl.tail_s + pl.cs, byte, gl, 16u);
+		put(pl.out_len, 13u, pl.s0l, r + 13, pl.T0, pl.s1l, r + pl.tail_s, pl.s2o, pl.s2l, r + pl.tail_s + pl.cs, byte);
 	}
-}
+};
 
 unsigned tiles_grid(uint64_t n) { return (unsigned)(((n + kTile - 1) / kTile + kMinThreads / 64 - 1) / (kMinThreads / 64)); }
 
@@ -365,7 +349,7 @@ hipError_t launch_bam_min_keys(const uint8_t *stream, const uint64_t *bend, cons
 	a.key_mask = key_bits >= 64 ? ~0ull : (1ull << key_bits) - 1ull;
 	a.rule = rule; a.skip_key = id_skip_bit(rule, key_bits);
 	a.krec = (u64 *)krec; a.key = (u64 *)key; a.idx = idx; a.decline = decline;
-	bam_min_key_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
+	bam_min_key_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(a);
 	return hipGetLastError();
 }
 
@@ -400,7 +384,7 @@ hipError_t launch_bam_min_size(const uint8_t *stream, const uint64_t *bend, cons
 	if (nb > 0) {
 		MinArgs a = min_args(stream, bend, entry, nb, rb, flags);
 		a.ids = ids; a.bo = (u64 *)bo; a.decline = decline;
-		bam_min_size_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
+		bam_min_size_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(a);
 		if (hipError_t e = hipGetLastError()) return e;
 	}
 	return launch_scan_u64(bo, nb, st);
@@ -412,19 +396,13 @@ hipError_t launch_bam_min_index(const uint8_t *stream, const uint64_t *bend, con
 	if (nb <= 0) return hipSuccess;
 	MinArgs a = min_args(stream, bend, entry, nb, rb, flags);
 	a.ids = ids; a.bo = (u64 *)bo; a.krec = (u64 *)krec; a.kout = (u64 *)kout;
-	bam_min_index_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
+	bam_min_index_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(a);
 	return hipGetLastError();
 }
 
-hipError_t launch_bam_min_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint32_t *ids, int64_t first, int64_t n,
-                                uint64_t o0, int flags, uint8_t fill, uint8_t *out, int n_cu, hipStream_t st)
+hipError_t launch_bam_min_write(const WriteWindow &w, const uint32_t *ids, int flags, uint8_t fill, int n_cu, hipStream_t st)
 {
-	if (n <= 0) return hipSuccess;
-	int64_t grid = (n + kMinThreads / 16 - 1) / (kMinThreads / 16);
-	const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 256) * 16;
-	if (grid > cap) grid = cap;
-	bam_min_write_kernel<<<(unsigned)grid, kMinThreads, 0, st>>>(stream, (const u64 *)krec, (const u64 *)kout, ids, first, n, o0, flags, fill, out);
-	return hipGetLastError();
+	return launch_bam_write(w, MinRecord{ids, flags, fill}, n_cu, st);
 }
 
 }  // namespace sk

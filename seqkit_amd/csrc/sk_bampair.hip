@@ -294,10 +294,8 @@ hipError_t launch_bam_pair_text(const uint8_t *stream, const uint64_t *krec, con
 	PairText a;
 	a.stream = stream; a.krec = (const u64 *)krec; a.perm = perm; a.soff = (const u64 *)soff; a.first = first; a.n = n; a.fmt = fmt; a.min_baseq = min_baseq;
 	a.text = text;
-	int64_t grid = (n + kPairThreads / 16 - 1) / (kPairThreads / 16);
-	const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 256) * 16;
-	if (grid > cap) grid = cap;
-	bam_pair_text_kernel<<<(unsigned)grid, kPairThreads, 0, st>>>(a);
+	static_assert(kPairThreads == kGroupThreads, "bam_pair_text_kernel is launched on group_grid");
+	bam_pair_text_kernel<<<group_grid(n, n_cu), kPairThreads, 0, st>>>(a);
 	return hipGetLastError();
 }
 

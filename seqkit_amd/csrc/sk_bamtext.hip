@@ -311,15 +311,11 @@ __device__ __forceinline__ ReadRec reads_rec(const uint8_t *r, int fmt, int want
 	return o;
 }
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_size_kernel(const ReadsArgs a)
+__global__ __launch_bounds__(kBlockThreads) void bam_reads_size_kernel(const ReadsArgs a)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= a.nb) return;                                                 // (no workgroup barrier below: each wave uses its own LDS)
-	uint16_t *off = offs[w];
-	const uint32_t n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
-	const u64 entry = a.entry[c];
+	BlockPass b;
+	if (!block_open(a.stream, a.entry, a.bend, a.nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
 	u64 kept = 0, tb = 0, nb = 0;
 	uint32_t dec = 0u;
 	for (uint32_t j = (uint32_t)lane; j < n; j += 64u) {
@@ -336,15 +332,11 @@ __global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_size_kernel(const 
 	}
 }
 
-__global__ __launch_bounds__(kBlockWaves * 64) void bam_reads_index_kernel(const ReadsArgs a)
+__global__ __launch_bounds__(kBlockThreads) void bam_reads_index_kernel(const ReadsArgs a)
 {
-	__shared__ uint16_t offs[kBlockWaves][kBlockRecs];
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const int64_t c = (int64_t)blockIdx.x * kBlockWaves + w;
-	if (c >= a.nb) return;
-	uint16_t *off = offs[w];
-	const uint32_t n = wave_record_offsets(a.stream, a.entry, a.bend, c, off, lane);
-	const u64 entry = a.entry[c];
+	BlockPass b;
+	if (!block_open(a.stream, a.entry, a.bend, a.nb, b)) return;
+	const auto [lane, c, entry, n, off] = b;
 	u64 kb = a.bk[c], tb = a.bt[c], nb = a.bn[c];                       // where the block's first kept record goes
 	for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
 		const uint32_t j = j0 + (uint32_t)lane;
@@ -390,7 +382,7 @@ struct ReadsText {
 	uint32_t *noff;
 };
 
-constexpr int kTextThreads = 256;
+constexpr int kTextThreads = kGroupThreads;      // (launched on group_grid)
 __global__ __launch_bounds__(kTextThreads) void bam_reads_text_kernel(const ReadsText a)
 {
 	const int gl = threadIdx.x & 15;
@@ -555,7 +547,7 @@ hipError_t launch_bam_reads_size(const uint8_t *stream, const uint64_t *bend, co
 	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.fmt = fmt; a.want_unpaired = want_unpaired;
 	a.bk = (u64 *)bk; a.bt = (u64 *)bt; a.bn = (u64 *)bn; a.decline = decline;
 	if (nb > 0) {
-		bam_reads_size_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
+		bam_reads_size_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(a);
 		if (hipError_t e = hipGetLastError()) return e;
 	}
 	for (u64 *v : {a.bk, a.bt, a.bn}) {
@@ -581,7 +573,7 @@ hipError_t launch_bam_reads_index(const uint8_t *stream, const uint64_t *bend, c
 	a.stream = stream; a.bend = (const u64 *)bend; a.entry = (const u64 *)entry; a.nb = nb; a.fmt = fmt; a.want_unpaired = want_unpaired;
 	a.bk = (u64 *)bk; a.bt = (u64 *)bt; a.bn = (u64 *)bn;
 	a.krec = (u64 *)krec; a.ktoff = (u64 *)ktoff; a.knoff = (u64 *)knoff; a.kkey = (u64 *)kkey; a.kkind = kkind;
-	bam_reads_index_kernel<<<(unsigned)((nb + kBlockWaves - 1) / kBlockWaves), kBlockWaves * 64, 0, st>>>(a);
+	bam_reads_index_kernel<<<block_grid(nb), kBlockThreads, 0, st>>>(a);
 	return hipGetLastError();
 }
 
@@ -602,10 +594,7 @@ hipError_t launch_bam_reads_text(const uint8_t *stream, const uint64_t *krec, co
 	ReadsText a;
 	a.stream = stream; a.krec = (const u64 *)krec; a.ktoff = (const u64 *)ktoff; a.knoff = (const u64 *)knoff; a.first = first; a.n = n;
 	a.t0 = t0; a.n0 = n0; a.fmt = fmt; a.min_baseq = min_baseq; a.text = text; a.toff = (u64 *)toff; a.names = names; a.noff = noff;
-	int64_t grid = (n + kTextThreads / 16 - 1) / (kTextThreads / 16);
-	const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 256) * 16;
-	if (grid > cap) grid = cap;
-	bam_reads_text_kernel<<<(unsigned)grid, kTextThreads, 0, st>>>(a);
+	bam_reads_text_kernel<<<group_grid(n, n_cu), kTextThreads, 0, st>>>(a);
 	return hipGetLastError();
 }
 }  // namespace sk

@@ -205,15 +205,23 @@ hipError_t launch_scan_u64(uint64_t *v, int64_t n, hipStream_t st);     // sk_ba
 hipError_t launch_bam_windows(const uint64_t *off0, const uint64_t *off1, int64_t n, uint64_t W, uint64_t total0, uint64_t total1, uint64_t *ws,
                               uint64_t *w0, uint64_t *w1, int64_t nw, hipStream_t st);
 // ---- BAM out: the per-record rewrite of sk_bam_file_rewrite and the BGZF member packing (sk_bamwrite.hip) ----
+// One window of a BAM-writing call, as every window writer takes it: records first .. first + n - 1 of the written ones (krec: their
+// stream offsets, kout: their output offsets) into out, whose first byte is output offset o0
+struct WriteWindow {
+	const uint8_t *stream;
+	const uint64_t *krec, *kout;
+	int64_t first, n;
+	uint64_t o0;
+	uint8_t *out;
+};
 // size: per block the rewritten bytes of the records that begin in it (then exclusive offsets, bo[nb] the total) and the OR of the
-// records' decline bits; index: every record's stream offset and output offset (rb: the blocks' first record indices); write: records
-// first .. first + n - 1 into out (out offset o0 at 0)
+// records' decline bits; index: every record's stream offset and output offset (rb: the blocks' first record indices); write: the
+// window's records into w.out
 hipError_t launch_bam_rw_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int op, uint64_t *bo, uint32_t *decline,
                               hipStream_t st);
 hipError_t launch_bam_rw_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, int op, const uint64_t *bo,
                                const uint64_t *rb, uint64_t *krec, uint64_t *kout, hipStream_t st);
-hipError_t launch_bam_rw_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, int op,
-                               uint8_t *out, int n_cu, hipStream_t st);
+hipError_t launch_bam_rw_write(const WriteWindow &w, int op, int n_cu, hipStream_t st);
 // ---- sam minimize: the read ids and the per-record rewrite of sk_bam_file_minimize (sk_bamminimize.hip) ----
 // The key rule of the id passes.  whole_name == 0: a record's key is its name up to the first '/' (minimize); else the whole name.
 // skip_flags: a record with one of these flag bits takes no part — it neither opens nor closes an occurrence of its name, and its id is
@@ -234,8 +242,7 @@ hipError_t launch_bam_min_size(const uint8_t *stream, const uint64_t *bend, cons
                                const uint32_t *ids, uint64_t *bo, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_min_index(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int flags,
                                 const uint32_t *ids, const uint64_t *bo, uint64_t *krec, uint64_t *kout, hipStream_t st);
-hipError_t launch_bam_min_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint32_t *ids, int64_t first, int64_t n,
-                                uint64_t o0, int flags, uint8_t fill, uint8_t *out, int n_cu, hipStream_t st);
+hipError_t launch_bam_min_write(const WriteWindow &w, const uint32_t *ids, int flags, uint8_t fill, int n_cu, hipStream_t st);
 // ---- sam mark duplicates: the record passes of sk_bam_file_markdup (sk_bammarkdup.hip) ----
 // The per-record columns, in file order: stream and output offsets, (tid << 32 | (u32) pos), start_pos, fraglen | strand << 16 |
 // mapped << 17 (bit 31 is the cluster pass's), l_seq, the UMI's offset in the record and its length, and the flag to write.
@@ -256,8 +263,7 @@ hipError_t bam_md_run_scan(void *temp, size_t *temp_bytes, const uint32_t *runfl
 hipError_t launch_bam_md_keys(const uint32_t *run, const MdCols &cols, uint64_t n, uint64_t *key, uint32_t *idx, hipStream_t st);
 hipError_t launch_bam_md_cluster(const uint8_t *stream, const MdCols &cols, const uint64_t *key, const uint32_t *idx, uint64_t n, uint64_t *count,
                                  int n_cu, hipStream_t st);
-hipError_t launch_bam_md_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint16_t *nflag, int64_t first, int64_t n,
-                               uint64_t o0, uint8_t *out, int n_cu, hipStream_t st);
+hipError_t launch_bam_md_write(const WriteWindow &w, const uint16_t *nflag, int n_cu, hipStream_t st);
 // ---- sam subsample: the keep pass, the compaction and the window copy of sk_bam_file_subsample (sk_bamsubsample.hip) ----
 // Rule 3 of the command, the one statement of it (sk_subsample_keep, the keep pass): draw d of seed s is splitmix64's d-th output from
 // state s, its top 24 bits m; keep iff m <= T.
@@ -273,14 +279,14 @@ inline uint32_t subsample_threshold(float fraction) { return (uint32_t)((double)
 // keep: per record (krec: its stream offset, ids: its fragment number from the id passes under IdRule{1, 0x800}) len[k] = the record's
 // bytes when it is kept, 0 when it is dropped or has 0x800; counts[0 .. 2] += the counted records, the kept ones, the kept ones' bytes;
 // decline bit 1: a counted record without 0x1.  scans (temp == nullptr: only *temp_bytes): pos[k] = the kept records before k, off[k] =
-// their bytes.  compact: the kept records' stream and output offsets, in order.  write: as launch_bam_rw_write, every record byte for byte.
+// their bytes.  compact: the kept records' stream and output offsets, in order.  copy_write: as launch_bam_rw_write, every record byte for
+// byte (sam merge without --suffix writes its windows with it too).
 hipError_t launch_bam_sub_keep(const uint8_t *stream, const uint64_t *krec, const uint32_t *ids, uint64_t n, uint64_t seed, uint32_t T, uint32_t *len,
                                uint64_t *counts, uint32_t *decline, int n_cu, hipStream_t st);
 hipError_t bam_sub_scans(void *temp, size_t *temp_bytes, const uint32_t *len, uint32_t *pos, uint64_t *off, uint64_t n, hipStream_t st);
 hipError_t launch_bam_sub_compact(const uint64_t *krec, const uint32_t *len, const uint32_t *pos, const uint64_t *off, uint64_t n, uint64_t *kept_rec,
                                   uint64_t *kept_out, hipStream_t st);
-hipError_t launch_bam_sub_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, int64_t first, int64_t n, uint64_t o0, uint8_t *out,
-                                int n_cu, hipStream_t st);
+hipError_t launch_bam_copy_write(const WriteWindow &w, int n_cu, hipStream_t st);
 // ---- sam merge: the record passes of sk_bam_file_merge (sk_bammerge.hip) ----
 // The per-record columns in input order (input 1's records first, then input 2's ..): the record's address as an offset from input 1's
 // stream mod 2^64, its key (u32 refID) << 32 | (u32 pos ^ 0x80000000), its index, its output bytes and its input number (1-based).
@@ -292,15 +298,14 @@ struct MergeCols {
 // keys: one input's blocks (rb: their first records' GLOBAL indices; delta: this stream's address less input 1's; suffix_len: 0 without
 // --suffix, else the bytes of ".N") into the columns; decline bits 8 (an invalid record) and 1 (a suffixed name above 254 bytes).
 // order: decline bit 2 where a key is below its predecessor's in the same input.  gather: output place p takes record idx[p]'s address,
-// length (into kout) and input number; scan (temp == nullptr: only *temp_bytes): kout[0 .. n) -> exclusive offsets, kout[n] the sum.  write: as launch_bam_sub_write, ".N" behind every record's name; without a
-// suffix launch_bam_sub_write itself writes the windows.
+// length (into kout) and input number; scan (temp == nullptr: only *temp_bytes): kout[0 .. n) -> exclusive offsets, kout[n] the sum.  write: as launch_bam_copy_write, ".N" behind every record's name; without a
+// suffix launch_bam_copy_write itself writes the windows.
 hipError_t launch_bam_merge_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, uint64_t delta,
                                  uint32_t input, uint32_t suffix_len, const MergeCols &cols, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_merge_order(const MergeCols &cols, uint64_t n, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_merge_gather(const uint32_t *idx, const MergeCols &cols, uint64_t n, uint64_t *krec, uint64_t *kout, uint8_t *kin, hipStream_t st);
 hipError_t bam_merge_scan(void *temp, size_t *temp_bytes, uint64_t *kout, uint64_t n, hipStream_t st);
-hipError_t launch_bam_merge_write(const uint8_t *stream, const uint64_t *krec, const uint64_t *kout, const uint8_t *kin, int64_t first, int64_t n, uint64_t o0,
-                                  uint8_t *out, int n_cu, hipStream_t st);
+hipError_t launch_bam_merge_write(const WriteWindow &w, const uint8_t *kin, int n_cu, hipStream_t st);
 // ---- sam to: the mate pairing of sk_bam_file_pairs and its windows' text (sk_bampair.hip) ----
 // Over the K kept records of launch_bam_reads_index (file order; kind 0 unpaired, 1 first, 2 last mate).  A record's fate: where its text
 // goes; aux: for a record of a pair the kept index of the record that COMPLETED the pair, for a leftover its order record.  Its class: what

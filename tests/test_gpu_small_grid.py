@@ -45,13 +45,13 @@ pytestmark = pytest.mark.gpu
 # kernel -> units of work ONE launch covers per planned CU in a single trip of its stride loop (read from the named launcher).  Where a
 # launcher asks the occupancy API, the entry is the most it can come to.
 CAPACITY = {
-    "bam_reads_text_kernel": 256,          # launch_bam_reads_text: n_cu * 16 workgroups x 16 groups of 16 lanes, a record a group
-    "bam_pair_text_kernel": 256,           # launch_bam_pair_text: the same shape
-    "bam_rw_write_kernel": 256,            # launch_bam_rw_write: the same shape
-    "bam_min_write_kernel": 256,           # launch_bam_min_write: the same shape
-    "bam_md_write_kernel": 256,            # launch_bam_md_write: the same shape
-    "bam_sub_write_kernel": 256,           # launch_bam_sub_write: the same shape
-    "bam_merge_write_kernel": 256,         # launch_bam_merge_write: the same shape
+    "bam_reads_text_kernel": 256,          # launch_bam_reads_text on group_grid: n_cu * 16 workgroups x 16 groups of 16 lanes, a record a group
+    "bam_pair_text_kernel": 256,           # launch_bam_pair_text on group_grid
+    "bam_rw_write_kernel": 256,            # launch_bam_rw_write: its own kernel, on group_grid
+    "bam_write_kernel<MinRecord>": 256,    # launch_bam_min_write: launch_bam_write, the shared window writer, on group_grid
+    "bam_write_kernel<MdRecord>": 256,     # launch_bam_md_write: launch_bam_write
+    "bam_copy_write_kernel": 256,          # launch_bam_copy_write: its own kernel, on group_grid
+    "bam_write_kernel<MergeRecord>": 256,  # launch_bam_merge_write: launch_bam_write
     "bam_md_cluster_kernel": 2048,         # launch_bam_md_cluster (and bam_md_count_kernel): n_cu * 8 workgroups x 256 sorted positions
     "bam_sub_keep_kernel": 2048,           # launch_bam_sub_keep: n_cu * 8 workgroups x 256 records
     "bam_cov_hist_kernel": 1024,           # launch_bam_cov_hist: n_cu * 4 workgroups x 256 events
@@ -316,7 +316,7 @@ def test_minimize(ctx, small, small_chunks, tmp, cus):
         assert handled, out
         assert out == exp
         return mem
-    out_case(ctx, small, cus, path, "bam_min_write_kernel", len(exp), run)
+    out_case(ctx, small, cus, path, "bam_write_kernel<MinRecord>", len(exp), run)
 
 
 @pytest.mark.parametrize("cus", [1, 3])
@@ -326,7 +326,7 @@ def test_markdup(ctx, small, small_chunks, tmp, cus):
     raw = md_m.write(path, recs, piece=2000)
     if cus == 1:
         trips("bam_md_cluster_kernel", len(recs), 1)
-    out_case(ctx, small, cus, path, "bam_md_write_kernel", len(raw), lambda c, level, window: tg_md.check(c, path, raw, False, level, window))
+    out_case(ctx, small, cus, path, "bam_write_kernel<MdRecord>", len(raw), lambda c, level, window: tg_md.check(c, path, raw, False, level, window))
 
 
 @pytest.mark.parametrize("cus", [1, 3])
@@ -337,7 +337,7 @@ def test_subsample(ctx, small, small_chunks, tmp, cus):
     exp, _, _, kept, total = sub_m.model(raw, 5, sub_m.parse_fraction("0.5"))
     if cus == 1:
         trips("bam_sub_keep_kernel", len(recs), 1)
-    out_case(ctx, small, cus, path, "bam_sub_write_kernel", len(exp), lambda c, level, window: tg_sub.check(c, path, raw, "0.5", 5, level, window))
+    out_case(ctx, small, cus, path, "bam_copy_write_kernel", len(exp), lambda c, level, window: tg_sub.check(c, path, raw, "0.5", 5, level, window))
 
 
 @pytest.mark.parametrize("cus", [1, 3])
@@ -346,7 +346,7 @@ def test_merge(ctx, small, small_chunks, tmp, cus):
     paths, raws = tg_merge.write_all(tmp, files, piece=1000)
     exp, err, code = merge_m.model(raws, True)
     assert (err, code) == (b"", 0)
-    out_case(ctx, small, cus, paths[0], "bam_merge_write_kernel", len(exp), lambda c, level, window: tg_merge.check(c, paths, raws, True, level, window)[:2])
+    out_case(ctx, small, cus, paths[0], "bam_write_kernel<MergeRecord>", len(exp), lambda c, level, window: tg_merge.check(c, paths, raws, True, level, window)[:2])
 
 
 def test_rewrite_level_0_is_the_crc_alone(ctx, small, tmp):
@@ -377,7 +377,7 @@ def test_cli_minimize_read_ids(sam, tmp):
     path = tmp / "cli_minimize.bam"
     recs = min_m.served_records(5000, seed=4)
     raw = min_m.write(path, recs)
-    trips("bam_min_write_kernel", len(recs), 1)
+    trips("bam_write_kernel<MinRecord>", len(recs), 1)
     code, out, err, _ = bu.three(sam, min_m, ["minimize"], path, ["--read-ids"], env={"SK_PLAN_CUS": "1"})
     assert code == 0 and err == b"" and out == min_m.model(raw, "read-ids")[0]
     assert bu.three(sam, min_m, ["minimize"], path, ["--read-ids"])[:3] == (code, out, err)
@@ -387,7 +387,7 @@ def test_cli_mark_duplicates(sam, tmp):
     path = tmp / "cli_markdup.bam"
     recs = md_m.sorted_records(13, 5000, big=1100)
     raw = md_m.write(path, recs)
-    trips("bam_md_write_kernel", len(recs), 1)
+    trips("bam_write_kernel<MdRecord>", len(recs), 1)
     code, out, err, _ = bu.three(sam, md_m, ["mark", "duplicates"], path, env={"SK_PLAN_CUS": "1"})
     exp, stop, msg = md_m.literal(raw)
     assert (code, out, err) == (stop, exp, msg) and stop == 0
