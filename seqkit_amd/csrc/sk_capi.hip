@@ -53,10 +53,6 @@ struct sk_ctx {
 	sk::ManyBatch *many_pin = nullptr;
 	hipEvent_t many_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	int many_next = 0;
-	// the sheet / pitch / output set for which launch_tile_pass last said "no one-launch form": the next many-batch call of that shape goes
-	// straight to its batches' own launches (the refused attempt cost an event and the descriptors: 3 us a call)
-	const void *many_no_tab = nullptr;
-	int many_no_stride = 0, many_no_detail = -1;
 	// buffers that stay with the ctx from one call to the next (sk::ctx_keep; sk_internal.h: sk::KeepSlot)
 	struct Kept { void *p = nullptr; size_t cap = 0; bool pinned = false; } kept[sk::kKeepSlots];
 	void *ext = nullptr;               // an object another translation unit keeps with the ctx (sk_bamfile.h: Ranges, the file calls' mapped ranges and window state), and how to free it
@@ -405,7 +401,6 @@ int sk_set_barcodes(sk_ctx *c, const uint8_t *table, int S, int L, int max_diff)
 	if (c->d_lut) { SK_HIP(c, hipFree(c->d_lut)); c->d_lut = nullptr; }
 	if (c->d_bs) { SK_HIP(c, hipFree(c->d_bs)); c->d_bs = nullptr; }
 	if (c->d_nbr) { SK_HIP(c, hipFree(c->d_nbr)); c->d_nbr = nullptr; }
-	c->many_no_tab = nullptr;
 	c->nbr = sk::LutDev{};
 	c->bs_bytes = c->bs_mm_off = c->G = 0;
 	if (c->d_counts) { SK_HIP(c, hipFree(c->d_counts)); c->d_counts = nullptr; }
@@ -855,22 +850,6 @@ static int check_fused(sk_ctx *c, const sk_fused_args *a, bool dev)
 	return SK_OK;
 }
 
-// demultiplex alone, with the decision only or the detail columns of matched rows only: the neighbourhood table's case.
-// Called with the ctx's device bound (the table is uploaded to the current device).
-static int prepare_demux(sk_ctx *c, const sk_fused_args *a)
-{
-	if (!a->bc) return SK_OK;
-	// (a pass with mates matches in the tile pass itself when the bit-sliced matcher applies — at most 128 samples, the tile's
-	// barcodes in two register chunks: launch_tile_pass's fuse_demux; otherwise its barcode phase is a launch of its own and
-	// takes the table like a demultiplex-alone call)
-	bool any_mate = false;
-	for (int m = 0; m < a->n_mates; m++) any_mate = any_mate || a->mate[m].out_seq || a->mate[m].lowest_k;
-	if (sk::tile_pass_fuses_demux(true, any_mate, a->stride, c->d_bs != nullptr, c->G, c->S, a->bc_stride)) return SK_OK;
-	const bool want_detail = a->lowest_diff || a->first_idx || a->last_idx;
-	if (want_detail && c->detail_mode != SK_DETAIL_MATCHED) return SK_OK;
-	return ensure_neighbour_table(c);
-}
-
 static sk::TileArgs tile_args_of(const sk_ctx *c, const sk_fused_args *a)
 {
 	sk::TileArgs t;
@@ -891,16 +870,34 @@ static sk::TileArgs tile_args_of(const sk_ctx *c, const sk_fused_args *a)
 	return t;
 }
 
+// demultiplex alone, with the decision only or the detail columns of matched rows only: the neighbourhood table's case — unless the
+// pass matches in the tile pass itself (sk_tileplan.h: wants_neighbour_table states both).  Called with the ctx's device bound (the
+// table is uploaded to the current device).
+static int prepare_demux(sk_ctx *c, const sk::tileplan::Knobs &kn, sk::TileArgs &t)
+{
+	if (!t.bc || c->nbr_tried) return SK_OK;       // (tried: the table is there, or the sheet has none)
+	if (!sk::tileplan::wants_neighbour_table(kn, sk::tile_shape(t, c->n_cu))) return SK_OK;
+	if (int r = ensure_neighbour_table(c)) return r;
+	t.table.nbr = c->nbr;
+	return SK_OK;
+}
+static int prepare_demux(sk_ctx *c, const sk::tileplan::Knobs &kn, const sk_fused_args *a)
+{
+	sk::TileArgs t = tile_args_of(c, a);
+	return prepare_demux(c, kn, t);
+}
+
 int sk_fused_pass_dev(sk_ctx *c, const sk_fused_args *a)
 {
 	if (!c) return SK_ERR_INVALID;
 	if (int r = bind(c)) return r;          // first: what follows may upload the sheet's table to the current device
 	if (int r = check_fused(c, a, true)) return r;
 	if (a->n == 0) return SK_OK;
-	if (int r = prepare_demux(c, a)) return r;
+	const sk::tileplan::Knobs kn = sk::tile_knobs();
 	sk::TileArgs t = tile_args_of(c, a);
+	if (int r = prepare_demux(c, kn, t)) return r;
 	if (t.bc && t.counts_wide) c->wide_dirty = true;
-	SK_HIP(c, sk::launch_tile_pass(t, c->n_cu, c->stream));
+	SK_HIP(c, sk::launch_tile_pass(t, kn, c->n_cu, c->stream));
 	return SK_OK;
 }
 
@@ -922,23 +919,32 @@ int sk_fused_pass_many_dev(sk_ctx *c, const sk_fused_args *batches, int n_batche
 	if (n_batches == 0) return SK_OK;
 	if (int r = bind(c)) return r;
 	for (int i = 0; i < n_batches; i++) if (int r = check_fused(c, &batches[i], true)) return r;
+	const sk::tileplan::Knobs kn = sk::tile_knobs();
 	// ONE launch for all of them when they are lookups of one shape: demultiplex alone into the ctx's counters, the same pitch and the
-	// same set of output columns, served by a table in LDS (launch_tile_pass says no for any other shape: the loop below)
+	// same set of output columns, served by a table in LDS (the plan says no for any other shape — sk_tileplan.h: many_ok —: the loop below)
 	{
 		bool same = n_batches >= 2;
 		int64_t rows = 0;
+		const sk_fused_args *first = nullptr;                            // the first batch that has rows
 		for (int i = 0; i < n_batches && same; i++) {
 			const sk_fused_args &a = batches[i], &f = batches[0];
 			bool mates = false;
 			for (int m = 0; m < a.n_mates; m++) mates = mates || a.mate[m].out_seq || a.mate[m].lowest_k;
 			same = !mates && a.bc && !a.counts && a.bc_stride == f.bc_stride && !a.lowest_diff == !f.lowest_diff && !a.first_idx == !f.first_idx && !a.last_idx == !f.last_idx;
 			rows += ((a.n + 255) / 256) * 256;
+			if (!first && a.n > 0) first = &a;
 		}
 		if (const char *ev = getenv("SK_MANY_ONE_LAUNCH")) same = same && atoi(ev) != 0;      // (A/B: the batches' own launches instead)
-		const int want_detail_key = same ? ((batches[0].lowest_diff ? 1 : 0) | (batches[0].first_idx ? 2 : 0) | (batches[0].last_idx ? 4 : 0) | (c->detail_mode << 3)) : 0;
-		if (same && c->many_no_tab && c->many_no_tab == (const void *)c->d_nbr && c->many_no_stride == batches[0].bc_stride && c->many_no_detail == want_detail_key && !getenv("SK_LUT_MANY_GATHER")) same = false;
-		if (same && rows > 0 && rows < ((int64_t)1 << 31) && n_batches <= kManyMax) {
-			if (int r = prepare_demux(c, &batches[0])) return r;
+		sk::TileArgs t;
+		if (same && first && rows < ((int64_t)1 << 31) && n_batches <= kManyMax) {
+			t = tile_args_of(c, first);
+			if (int r = prepare_demux(c, kn, t)) return r;
+			t.n = rows;
+			sk::tileplan::Shape s = sk::tile_shape(t, c->n_cu);
+			s.many = true; s.many_quads = (int)(rows / 256);
+			same = sk::tileplan::demux_plan(kn, s).many_ok;
+		} else same = false;
+		if (same) {
 			if (!c->many_pin) {
 				SK_HIP(c, hipHostMalloc((void **)&c->many_pin, kManySlots * kManyMax * sizeof(sk::ManyBatch), hipHostMallocDefault));
 				for (int k = 0; k < kManySlots; k++) SK_HIP(c, hipEventCreateWithFlags(&c->many_ev[k], hipEventDisableTiming));
@@ -962,22 +968,14 @@ int sk_fused_pass_many_dev(sk_ctx *c, const sk_fused_args *batches, int n_batche
 				q0 += (a.n + 255) / 256;
 				m.q_end = (int32_t)q0;
 			}
-			if (nb > 0) {
-				// (the kernel reads the descriptors where they lie, in pinned host memory: a wave reads one when its cursor moves to the next
-				// batch — a copy of 200 bytes in front of the launch was 10 us on the stream, a tenth of what four batches take)
-				sk_fused_args first = batches[0];
-				for (int i = 0; i < n_batches; i++) if (batches[i].n > 0) { first = batches[i]; break; }
-				sk::TileArgs t = tile_args_of(c, &first);
-				t.n = q0 * 256;
-				t.many = hb; t.n_many = nb; t.many_quads = (int)q0;
-				if (t.counts_wide) c->wide_dirty = true;
-				const hipError_t e = sk::launch_tile_pass(t, c->n_cu, c->stream);
-				SK_HIP(c, hipEventRecord(c->many_ev[slot], c->stream));
-				if (e == hipSuccess) return SK_OK;
-				if (e != hipErrorNotSupported) return fail(c, SK_ERR_HIP, "launch_tile_pass (many batches): %s", hipGetErrorString(e));
-				(void)hipGetLastError();
-				if (t.n >= 1500000) { c->many_no_tab = (const void *)c->d_nbr; c->many_no_stride = batches[0].bc_stride; c->many_no_detail = want_detail_key; }      // (below that the answer may depend on the size)
-			} else return SK_OK;
+			// (the kernel reads the descriptors where they lie, in pinned host memory: a wave reads one when its cursor moves to the next
+			// batch — a copy of 200 bytes in front of the launch was 10 us on the stream, a tenth of what four batches take)
+			t.many = hb; t.n_many = nb; t.many_quads = (int)q0;      // (t.n = q0 * 256, as the plan was asked)
+			if (t.counts_wide) c->wide_dirty = true;
+			const hipError_t e = sk::launch_tile_pass(t, kn, c->n_cu, c->stream);
+			SK_HIP(c, hipEventRecord(c->many_ev[slot], c->stream));
+			if (e != hipSuccess) return fail(c, SK_ERR_HIP, "launch_tile_pass (many batches): %s", hipGetErrorString(e));
+			return SK_OK;
 		}
 	}
 	// batches without a barcode phase (trim / mask alone: nothing but their own outputs is written, no counters) alternate between the
@@ -993,9 +991,9 @@ int sk_fused_pass_many_dev(sk_ctx *c, const sk_fused_args *batches, int n_batche
 		bool mates = false;
 		for (int m = 0; m < batches[i].n_mates; m++) mates = mates || batches[i].mate[m].out_seq || batches[i].mate[m].lowest_k;
 		if (two_mode < 2 || mates || batches[i].counts) { two = false; break; }
-		if (int r = prepare_demux(c, &batches[i])) return r;
-		const sk::TileArgs t = tile_args_of(c, &batches[i]);
-		two = t.counts_wide != nullptr && sk::tile_pass_demux_by_table(t);
+		sk::TileArgs t = tile_args_of(c, &batches[i]);
+		if (int r = prepare_demux(c, kn, t)) return r;
+		two = t.counts_wide != nullptr && sk::tileplan::demux_by_table(kn, sk::tile_shape(t, c->n_cu));
 	}
 	if (two) {
 		SK_HIP(c, hipEventRecord(c->ev_pipe, c->stream));
@@ -1005,10 +1003,10 @@ int sk_fused_pass_many_dev(sk_ctx *c, const sk_fused_args *batches, int n_batche
 	for (int i = 0; i < n_batches; i++) {
 		const sk_fused_args *a = &batches[i];
 		if (a->n == 0) continue;
-		if (int r = prepare_demux(c, a)) return r;
 		sk::TileArgs t = tile_args_of(c, a);
+		if (int r = prepare_demux(c, kn, t)) return r;
 		if (t.bc && t.counts_wide) c->wide_dirty = true;
-		SK_HIP(c, sk::launch_tile_pass(t, c->n_cu, (two && (k & 1)) ? c->stream2 : c->stream));
+		SK_HIP(c, sk::launch_tile_pass(t, kn, c->n_cu, (two && (k & 1)) ? c->stream2 : c->stream));
 		k++;
 	}
 	if (two) {
@@ -1052,7 +1050,8 @@ int sk_fused_pass(sk_ctx *c, const sk_fused_args *a)
 	if (int r = bind(c)) return r;
 	if (int r = check_fused(c, a, false)) return r;
 	if (a->n == 0) return SK_OK;
-	if (int r = prepare_demux(c, a)) return r;
+	const sk::tileplan::Knobs kn = sk::tile_knobs();
+	if (int r = prepare_demux(c, kn, a)) return r;
 	const int64_t stride = a->stride;
 	sk_fused_args d = *a;                                      // the chunk on the device: every pointer below is set by stage_in()
 	d.counts = nullptr;
@@ -1082,7 +1081,7 @@ int sk_fused_pass(sk_ctx *c, const sk_fused_args *a)
 		sk::TileArgs t = tile_args_of(c, &d);
 		if (t.table.count_rep && (pipe.k & 1)) t.table.count_rep += c->count_rep_set;     // the second lane's set of counter copies
 		if (t.bc && t.counts_wide) c->wide_dirty = true;
-		SK_HIP(c, sk::launch_tile_pass(t, c->n_cu, pipe.st()));
+		SK_HIP(c, sk::launch_tile_pass(t, kn, c->n_cu, pipe.st()));
 		if (int r = pipe.stage_out()) return r;
 	}
 	return pipe.end();
@@ -1096,7 +1095,8 @@ int sk_fused_tune_placement_dev(sk_ctx *c, sk_fused_args *a, const sk_fused_cand
 	if (cd->k < 1 || cd->k > SK_MAX_CANDIDATES || sweeps < 0) return fail(c, SK_ERR_INVALID, "k = %d (1..%d), sweeps = %d", cd->k, SK_MAX_CANDIDATES, sweeps);
 	if (int r = bind(c)) return r;
 	if (int r = check_fused(c, a, true)) return r;
-	if (int r = prepare_demux(c, a)) return r;
+	const sk::tileplan::Knobs kn = sk::tile_knobs();
+	if (int r = prepare_demux(c, kn, a)) return r;
 	// the matrices that take part: those the pass uses and that have candidates
 	struct Slot { int mate, what; };                       // what: 0 seq, 1 qual, 2 out_seq
 	std::vector<Slot> slots;
@@ -1131,9 +1131,9 @@ int sk_fused_tune_placement_dev(sk_ctx *c, sk_fused_args *a, const sk_fused_cand
 		apply(t, ch);
 		sk::TileArgs ta = tile_args_of(c, &t);
 		probes++;
-		hipError_t e = sk::launch_tile_pass(ta, c->n_cu, c->stream);                 // warm
+		hipError_t e = sk::launch_tile_pass(ta, kn, c->n_cu, c->stream);             // warm
 		if (e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
-		for (int i = 0; i < 2 && e == hipSuccess; i++) e = sk::launch_tile_pass(ta, c->n_cu, c->stream);
+		for (int i = 0; i < 2 && e == hipSuccess; i++) e = sk::launch_tile_pass(ta, kn, c->n_cu, c->stream);
 		if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
 		if (e == hipSuccess) e = hipEventSynchronize(c->ev1);
 		if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);

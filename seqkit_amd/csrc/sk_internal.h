@@ -4,16 +4,13 @@
 #include <stdint.h>
 
 #include "sk_lut.h"
+#include "sk_tileplan.h"
 
 namespace sk {
 
-constexpr int kWave = 64;             // gfx950 wavefront; one read tile = 64 reads = one wave
-constexpr int kTileRows = 64;
-constexpr int kLdsPad = 16;           // bytes kept free before and after the LDS tile image
-constexpr int kMaxTileStride = 960;   // 64 rows x 960 B + pads + histogram <= 64 KiB of LDS
+// (kWave, kTileRows, kLdsPad, kMaxTileStride, kMaxLdsHist, kSlots and LdsPlan: sk_tileplan.h, with the launch rules that use them)
 constexpr int kMaxOneHotLen = 32;     // barcode length served by the one-hot popcount matcher (W <= 8 dwords)
 constexpr int kKeyBits = 11;          // trim scan packs (U << 11 | j); rows up to 2047 bytes
-constexpr int kMaxLdsHist = 1024;     // per-wave LDS histogram entries (S+3) before falling back to global atomics
 constexpr int kAssignNone = -1;       // SK_ASSIGN_NONE
 constexpr int kAssignAmbiguous = -2;  // SK_ASSIGN_AMBIGUOUS
 
@@ -121,9 +118,16 @@ hipError_t launch_tile_blocked(const BlockedArgs &a, int n_cu, hipStream_t st);
 bool blocked_shape_ok(const BlockedArgs &a);
 
 // launchers (all asynchronous on `st`); return hipError_t of the launch
-hipError_t launch_tile_pass(const TileArgs &a, int n_cu, hipStream_t st);
-// whether launch_tile_pass matches the barcodes inside the tile pass (bit-sliced matcher) instead of with a launch of their own
-bool tile_pass_fuses_demux(bool has_bc, bool any_mate, int stride, bool has_bitsliced, int G, int S, int bc_stride);
+// What launch_tile_pass decides — does the barcode phase ride in the tile pass, does the sheet's table serve a launch of its own, which
+// kernel, what shape — is stated in sk_tileplan.h as functions of these two, so that the C-ABI layer asks the same rules what a call
+// needs (tileplan::wants_neighbour_table, demux_plan().many_ok, demux_by_table) instead of repeating them:
+//   tile_knobs(): the SK_* tuning variables, read from the environment (per call, or once per process: see there).  An entry point
+//                 reads them once, so what it asks the plan and what the launcher then decides rest on the same values;
+//   tile_shape(): the call as the plain facts the rules read.
+// A many-batch TileArgs whose plan has no one-launch form (tileplan::DemuxPlan::many_ok) is refused with hipErrorInvalidValue.
+tileplan::Knobs tile_knobs();
+tileplan::Shape tile_shape(const TileArgs &a, int n_cu);
+hipError_t launch_tile_pass(const TileArgs &a, const tileplan::Knobs &k, int n_cu, hipStream_t st);
 hipError_t launch_mask_flat(const uint8_t *seq, const uint8_t *qual, uint8_t *out, int64_t bytes,
                             const QualConsts &qc, int n_cu, hipStream_t st);
 hipError_t launch_bam_flag_tlen(const uint16_t *flag, const int32_t *tid, const int32_t *mtid, const int32_t *tlen,
@@ -170,7 +174,6 @@ hipError_t launch_bam_sequence(const uint8_t *seq4, int seq4_stride, const uint8
 
 // ---- BGZF inflate and the BAM record walk on the device (sk_inflate.hip) ----
 // blocks: device array of sk_bgzf_block; status: device u32 per block (0 = inflated; 1..8 the decoder gave up; | 0x100 CRC mismatch)
-bool tile_pass_demux_by_table(const TileArgs &b);
 hipError_t launch_bgzf_inflate(const uint8_t *comp, const void *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status, int check_crc, int n_cu, hipStream_t st);
 hipError_t launch_bam_walk(const uint8_t *stream, uint64_t stream_len, const uint64_t *bend, uint64_t *entry, uint64_t *exitp, uint32_t *nrec, int64_t n,
                            uint64_t first, uint32_t *changed, int fix_round /* 0 first walk, 1 fix, 2 guess */, int32_t n_ref, hipStream_t st);

@@ -24,6 +24,8 @@
 #include "sk_internal.h"
 
 #include <cstdlib>
+#include <cstring>
+#include <unistd.h>
 #include <mutex>
 #include <vector>
 
@@ -727,14 +729,6 @@ __device__ __forceinline__ void wave_lds_fence()
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-struct LdsPlan {
-	int table_bytes;     // matcher tables (bit-sliced blob, one-hot codes or raw sheet bytes), rounded to 16
-	int hist_off;        // u32[S+3]
-	int tiles_off;       // first wave's tile slot (includes the front pad)
-	int tile_slot;       // bytes per wave: front pad + 64*row_bytes rounded to 16 + back pad
-	int use_lds_hist;
-};
-
 // copy the matcher tables into the workgroup's LDS and clear its histogram (all threads; ends with a barrier)
 __device__ __forceinline__ void stage_tables(const BarcodeDev &t, const LdsPlan &lp, u32 *hist)
 {
@@ -927,13 +921,6 @@ static hipError_t launch_counts_fold(const TileArgs &b, bool by_table, hipStream
 //   DEMUX : the barcode phase is part of the pass, bit-sliced matcher with G <= 4 (S <= 128) and
 //           64*bc_stride <= 2048; every other demultiplex shape runs as demux_tile_kernel beside this one
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#ifndef SK_SLOTS
-#define SK_SLOTS 2
-#endif
-#ifndef SK_SLOTS1
-#define SK_SLOTS1 4
-#endif
-constexpr int kSlots = SK_SLOTS;                      // 1 KiB chunk loads in flight per wave and stream
 constexpr int kAuxStream = (SK_NT & 1) ? 2 : 0;      // nt on the read-once streams
 #ifdef SK_ST_AUX
 constexpr int kAuxStreamSt = SK_ST_AUX;              // tuning: cache-policy bits of the streaming stores (bit 0 sc0, bit 1 nt, bit 4 sc1)
@@ -1930,22 +1917,6 @@ __global__ __launch_bounds__(LDSTAB ? 1024 : 256) void demux_lut8x2_kernel(const
 	else flush_counts_spread(a.table, a.counts, lp, hist, lane, wc);
 }
 
-template <bool LDSTAB, bool DETAIL>
-static const void *demux_lut_fn(int W1, int W2, bool direct)
-{
-	if (direct) return W1 == 1 ? reinterpret_cast<const void *>(demux_lut_kernel<1, 0, true, LDSTAB, DETAIL>)
-	                           : reinterpret_cast<const void *>(demux_lut_kernel<2, 0, true, LDSTAB, DETAIL>);
-	if (W2 > 0) return W1 == 1 ? reinterpret_cast<const void *>(demux_lut_kernel<1, 1, false, LDSTAB, DETAIL>)
-	                           : reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, LDSTAB, DETAIL>);
-	switch (W1) {
-	case 1: return reinterpret_cast<const void *>(demux_lut_kernel<1, 0, false, LDSTAB, DETAIL>);
-	case 2: return reinterpret_cast<const void *>(demux_lut_kernel<2, 0, false, LDSTAB, DETAIL>);
-	case 3: return reinterpret_cast<const void *>(demux_lut_kernel<3, 0, false, LDSTAB, DETAIL>);
-	case 4: return reinterpret_cast<const void *>(demux_lut_kernel<4, 0, false, LDSTAB, DETAIL>);
-	default: return reinterpret_cast<const void *>(demux_lut_kernel<5, 0, false, LDSTAB, DETAIL>);
-	}
-}
-
 // rows too long for an LDS tile: one thread per row straight from global memory (correct, not fast)
 __global__ __launch_bounds__(256) void trim_rows_global_kernel(const uint8_t *__restrict__ qual, const uint16_t *__restrict__ len,
                                                                int stride, int64_t n, int m, uint16_t *__restrict__ lowest_k)
@@ -1964,85 +1935,130 @@ __global__ __launch_bounds__(256) void trim_rows_global_kernel(const uint8_t *__
 	}
 }
 
-// LDS layout + workgroup shape for a tile kernel; the grid comes from the occupancy API so that every
-// workgroup of the persistent grid is resident (a queued workgroup would run its whole share of tiles late).
-struct LaunchShape { LdsPlan lp; int grid, block, lds; };
+// ---------------------------------------------------------------------------------------------------
+// The launchers of the tile kernels.  What they decide is stated in sk_tileplan.h (and tested on the CPU: tests/cpp/tileplan_test.cpp);
+// here: the knobs are read (tile_knobs: an entry point of sk_capi.hip does, once per call, and hands them to launch_tile_pass), the call
+// is stated as a tileplan::Shape, the plan is asked, its kernel id mapped to a function and the occupancy API asked.
+// ---------------------------------------------------------------------------------------------------
+using tileplan::Knobs;
+using tileplan::Shape;
 
-static hipError_t plan_shape(const void *fn, const BarcodeDev &table, int64_t n, int image_bytes /* LDS image per wave */, bool with_tables, int max_nw,
-                             int n_cu, int images, int max_wg, LaunchShape &out)
+// The SK_* variables of the plan.  SK_NO_FUSED_DEMUX, SK_LUT_NW and SK_LUT_WG are read once per process; the others on every call, so
+// that one process can compare shapes and kernels on the same buffers (the tests, tools/ablate.py, tools/waves_exp.py, tools/demux_ab.py)
+// — in ONE walk over the environment, which costs what one getenv does.
+Knobs tile_knobs()
 {
-	static const int kLdsPerCu = 160 * 1024;
-	LdsPlan lp{};
-	lp.table_bytes = 0;
-	if (with_tables) {
-		int tb = table.bs ? table.bs_bytes : table.onehot ? table.S * padded_w(table.W) * 4 : table.S * table.L;
-		lp.table_bytes = (tb + 15) & ~15;
+	static const Knobs once = [] {
+		Knobs k;
+		k.no_fused_demux = getenv("SK_NO_FUSED_DEMUX") != nullptr;
+		if (const char *v = getenv("SK_LUT_NW")) k.lut_nw = atoi(v);
+		if (const char *v = getenv("SK_LUT_WG")) k.lut_wg = atoi(v);
+		return k;
+	}();
+	Knobs k = once;
+	auto value = [](const char *entry, const char *name) -> const char * {      // of "SK_" + name, when that is what the entry sets
+		const size_t len = strlen(name);
+		return strncmp(entry + 3, name, len) == 0 && entry[3 + len] == '=' ? entry + 3 + len + 1 : nullptr;
+	};
+	for (char **e = environ; e && *e; e++) {
+		const char *s = *e, *v;
+		if (s[0] != 'S' || s[1] != 'K' || s[2] != '_') continue;
+		if ((v = value(s, "TILE_WAVES"))) k.tile_waves = atoi(v);
+		else if ((v = value(s, "TILE_WGS"))) k.tile_wgs = atoi(v);
+		else if (value(s, "NO_HASH_DEMUX")) k.no_hash_demux = true;
+		else if ((v = value(s, "DEMUX_DIRECT"))) k.demux_direct = atoi(v) != 0;
+		else if ((v = value(s, "DEMUX_LDSTAB"))) k.demux_ldstab = atoi(v) != 0;
+		else if ((v = value(s, "DEMUX_ROWS2"))) k.demux_rows2 = atoi(v) != 0;
+		else if ((v = value(s, "LUT_MANY_GATHER"))) k.lut_many_gather = atoi(v) != 0;
 	}
-	lp.use_lds_hist = (with_tables && table.S + 3 <= kMaxLdsHist) ? 1 : 0;
-	lp.hist_off = lp.table_bytes;
-	lp.tiles_off = (lp.hist_off + (lp.use_lds_hist ? (table.S + 3) * 4 : 0) + 15) & ~15;
-	lp.tile_slot = kLdsPad + ((image_bytes + 15) & ~15) + kLdsPad;
-	// the shape search (occupancy queries, LDS opt-in) is cached per (device, kernel, LDS layout): small batches from
-	// the command-line hosts launch thousands of times with the same shape
-	struct Shape { int dev; const void *fn; int tiles_off, tile_slot, max_nw, max_wg, nw, wg; };
-	static std::mutex cache_m;
-	static std::vector<Shape> cache;
-	// tuning knobs (tools/ablate.py, tools/waves_exp.py): read per launch so that one process can compare shapes on the same buffers
-	const int env_nw = getenv("SK_TILE_WAVES") ? atoi(getenv("SK_TILE_WAVES")) : 0;
-	const int env_wg = getenv("SK_TILE_WGS") ? atoi(getenv("SK_TILE_WGS")) : 0;
-	const bool use_cache = env_nw == 0 && env_wg == 0;
-	int dev = 0;
+	return k;
+}
+
+// bytes of the matcher tables a tile kernel stages (stage_tables)
+static int matcher_bytes(const BarcodeDev &t) { return t.bs ? t.bs_bytes : t.onehot ? t.S * padded_w(t.W) * 4 : t.S * t.L; }
+
+Shape tile_shape(const TileArgs &a, int n_cu)
+{
+	Shape s;
+	s.n = a.n; s.stride = a.stride; s.n_cu = n_cu;
+	for (int mi = 0; mi < a.n_mates && mi < 2; mi++) { s.mask[mi] = a.mate[mi].out_seq != nullptr; s.trim[mi] = a.mate[mi].lowest_k != nullptr; }
+	s.has_bc = a.bc != nullptr; s.bc_stride = a.bc_stride;
+	s.lowest_diff = a.lowest_diff != nullptr; s.first_idx = a.first_idx != nullptr; s.last_idx = a.last_idx != nullptr;
+	s.detail_matched = a.detail_matched != 0;
+	s.counts_wide = a.counts_wide != nullptr;
+	s.many = a.many != nullptr; s.many_quads = a.many_quads;
+	const BarcodeDev &t = a.table;
+	s.S = t.S; s.G = t.G; s.bitsliced = t.bs != nullptr; s.matcher_bytes = matcher_bytes(t);
+	s.full_key = t.nbr.tab != nullptr; s.W1 = t.nbr.W1; s.W2 = t.nbr.W2; s.mask_slots = t.nbr.mask;
+	s.factored = t.nbr.pair.tab != nullptr; s.pair_bytes = t.nbr.pair.bytes;
+	return s;
+}
+
+// The answers of hipOccupancyMaxActiveBlocksPerMultiprocessor (workgroups of nw waves and lds bytes per CU), kept per (device,
+// kernel, nw, lds): small batches from the command-line hosts launch thousands of times with the same shape, and a shape seen
+// before costs no HIP call here.  A kernel's first query on a device opts it in to the CU's whole LDS.
+// (n questions about one kernel at a time: the candidates of the shape search, under one lock)
+static hipError_t occupancy(const void *fn, int n, const int *nw, const int *lds, int *wg)
+{
+	struct Occ { int dev; const void *fn; int nw, lds, wg; };
+	static std::mutex m;
+	static std::vector<Occ> cache;
+	int dev = 0, found = 0;
 	hipError_t e = hipGetDevice(&dev);
 	if (e != hipSuccess) return e;
-	int best_nw = 0, best_wg = 0, best_waves = 0;
-	if (use_cache) {
-		std::lock_guard<std::mutex> lk(cache_m);
-		for (const Shape &c : cache)
-			if (c.dev == dev && c.fn == fn && c.tiles_off == lp.tiles_off && c.tile_slot == lp.tile_slot * images && c.max_nw == max_nw && c.max_wg == max_wg) {
-				best_nw = c.nw; best_wg = c.wg; best_waves = c.nw * c.wg;
-				break;
-			}
-	}
-	if (best_waves == 0) {
-		e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
-		if (e != hipSuccess) return e;
-		for (int nw = (env_nw > 0 && env_nw <= 8) ? env_nw : max_nw; nw >= 1; nw >>= 1) {
-			const int lds = lp.tiles_off + nw * images * lp.tile_slot;
-			if (lds > kLdsPerCu) continue;
-			int wg = 0;
-			e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, kWave * nw, (size_t)lds);
-			if (e != hipSuccess) return e;
-			if (env_wg > 0) { if (wg > env_wg) wg = env_wg; }
-			else if (max_wg > 0 && wg > max_wg) wg = max_wg;
-			if (wg * nw > best_waves) { best_waves = wg * nw; best_nw = nw; best_wg = wg; }
-		}
-		if (best_waves > 0 && use_cache) {
-			std::lock_guard<std::mutex> lk(cache_m);
-			cache.push_back({dev, fn, lp.tiles_off, lp.tile_slot * images, max_nw, max_wg, best_nw, best_wg});
+	bool opted_in = false;
+	for (int i = 0; i < n; i++) wg[i] = -1;
+	{
+		std::lock_guard<std::mutex> lk(m);
+		for (const Occ &o : cache) {
+			if (o.dev != dev || o.fn != fn) continue;
+			opted_in = true;
+			for (int i = 0; i < n; i++)
+				if (wg[i] < 0 && o.nw == nw[i] && o.lds == lds[i]) { wg[i] = o.wg; found++; }
 		}
 	}
-	if (best_waves == 0) return hipErrorInvalidValue;
-	out.lds = lp.tiles_off + best_nw * images * lp.tile_slot;
-	int64_t ntiles = (n + kTileRows - 1) / kTileRows;
-	int64_t want = (ntiles + best_nw - 1) / best_nw;
-	int64_t cap = (int64_t)n_cu * best_wg;
-	out.grid = (int)(want < cap ? want : cap);
-	out.block = kWave * best_nw;
-	out.lp = lp;
+	if (found == n) return hipSuccess;
+	if (!opted_in) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
+	for (int i = 0; i < n && e == hipSuccess; i++) {
+		if (wg[i] >= 0) continue;
+		e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg[i], fn, kWave * nw[i], (size_t)lds[i]);
+		if (e != hipSuccess) break;
+		std::lock_guard<std::mutex> lk(m);
+		cache.push_back({dev, fn, nw[i], lds[i], wg[i]});
+	}
+	return e;
+}
+
+// LDS layout + workgroup shape + grid of a tile kernel (tileplan: tile_lds, tile_candidates, tile_pick, grid_for)
+struct LaunchShape { LdsPlan lp; int grid, block, lds; };
+
+static hipError_t plan_shape(const void *fn, const Knobs &k, const BarcodeDev &table, int64_t n, int image_bytes /* LDS image per wave */, bool with_tables,
+                             int n_cu, int max_wg, LaunchShape &out)
+{
+	out.lp = tileplan::tile_lds(with_tables, with_tables ? matcher_bytes(table) : 0, table.S, image_bytes);
+	const tileplan::Candidates c = tileplan::tile_candidates(k, out.lp, 4);
+	int occ[4];
+	hipError_t e = occupancy(fn, c.n, c.nw, c.lds, occ);
+	if (e != hipSuccess) return e;
+	const tileplan::Pick p = tileplan::tile_pick(k, c, occ, max_wg);
+	if (p.nw == 0) return hipErrorInvalidValue;
+	out.lds = p.lds;
+	out.grid = (int)tileplan::grid_for(tileplan::units(n, kTileRows), p.nw, n_cu, p.wg);
+	out.block = kWave * p.nw;
 	return hipSuccess;
 }
 
-static hipError_t plan_and_launch(const void *fn, const TileArgs &b, int row_bytes, bool with_tables, int max_nw, int n_cu, hipStream_t st, int images = 1,
-                                  int max_wg = 0)
+static hipError_t plan_and_launch(const void *fn, const Knobs &k, const TileArgs &b, int row_bytes, bool with_tables, int n_cu, int max_wg, hipStream_t st)
 {
 	LaunchShape sh;
-	hipError_t e = plan_shape(fn, b.table, b.n, kTileRows * row_bytes, with_tables, max_nw, n_cu, images, max_wg, sh);
+	hipError_t e = plan_shape(fn, k, b.table, b.n, kTileRows * row_bytes, with_tables, n_cu, max_wg, sh);
 	if (e != hipSuccess) return e;
 	TileArgs bb = b;
 	void *kargs[] = {(void *)&bb, (void *)&sh.lp};
 	return hipLaunchKernel(fn, dim3(sh.grid), dim3(sh.block), kargs, sh.lds, st);
 }
 
+// ---- kernel id -> function: every instantiation of the tile and lookup kernels is named here, once ----
 template <bool DEMUX, int SLOTS>
 static const void *tile_blocked_fn(int mode)
 {
@@ -2053,6 +2069,65 @@ static const void *tile_blocked_fn(int mode)
 	case 3: return reinterpret_cast<const void *>(tile_blocked_kernel<3, DEMUX, SLOTS>);
 	default: return reinterpret_cast<const void *>(tile_blocked_kernel<4, DEMUX, SLOTS>);
 	}
+}
+static const void *tile_blocked_fn(bool demux, int n_mates, int mode)
+{
+	if (n_mates == 1) return demux ? tile_blocked_fn<true, SK_SLOTS1>(mode) : tile_blocked_fn<false, SK_SLOTS1>(mode);
+	return demux ? tile_blocked_fn<true, kSlots>(mode) : tile_blocked_fn<false, kSlots>(mode);
+}
+
+static const void *demux_fn(const tileplan::KernelId &id)
+{
+	using namespace tileplan;
+#define SK_ID(...) KernelId{__VA_ARGS__}.key()
+#define SK_LUT(W1, W2, DIRECT, LDSTAB, DETAIL, PAIR, MANY) \
+	case SK_ID(kLookup, W1, W2, DIRECT, LDSTAB, DETAIL, PAIR, MANY): return reinterpret_cast<const void *>(demux_lut_kernel<W1, W2, DIRECT, LDSTAB, DETAIL, PAIR, MANY>);
+#define SK_LUT9(LDSTAB, DETAIL)      /* the key shapes of one form: rows loaded as they lie; two halves beside a separator, gathered; gathered rows */ \
+	SK_LUT(1, 0, true, LDSTAB, DETAIL, false, false) SK_LUT(2, 0, true, LDSTAB, DETAIL, false, false) \
+	SK_LUT(1, 1, false, LDSTAB, DETAIL, false, false) SK_LUT(2, 2, false, LDSTAB, DETAIL, false, false) \
+	SK_LUT(1, 0, false, LDSTAB, DETAIL, false, false) SK_LUT(2, 0, false, LDSTAB, DETAIL, false, false) SK_LUT(3, 0, false, LDSTAB, DETAIL, false, false) \
+	SK_LUT(4, 0, false, LDSTAB, DETAIL, false, false) SK_LUT(5, 0, false, LDSTAB, DETAIL, false, false)
+#define SK_8X2(LDSTAB, DETAIL, MANY) \
+	case SK_ID(kLookup8x2, 0, 0, false, LDSTAB, DETAIL, false, MANY): return reinterpret_cast<const void *>(demux_lut8x2_kernel<LDSTAB, DETAIL, MANY>);
+	// (the kernels lie in the code object in the order they are named: blocked, these, tile pass — kept, so that the device code stays
+	// byte for byte what it was when launch_tile_pass named them in a nest of ternaries)
+	switch (id.key()) {
+	case SK_ID(kMatcherTile): return reinterpret_cast<const void *>(demux_tile_kernel);
+	// the factored form
+	SK_LUT(1, 1, false, true, true, true, false) SK_LUT(1, 1, false, true, false, true, false)
+	SK_LUT(2, 2, false, true, true, true, false) SK_LUT(2, 2, false, true, false, true, false)
+	// 8-byte rows, two per lane
+	SK_8X2(true, true, false) SK_8X2(true, false, false) SK_8X2(false, true, false) SK_8X2(false, false, false)
+	// one row per lane: the table in LDS or in the vector cache, with the detail columns or without
+	SK_LUT9(true, true) SK_LUT9(true, false) SK_LUT9(false, true) SK_LUT9(false, false)
+	// many batches in one launch: 8-byte rows; gathered 8 + 8 (SK_LUT_MANY_GATHER=1), factored or full-key
+	SK_8X2(true, true, true) SK_8X2(true, false, true)
+	SK_LUT(2, 2, false, true, true, true, true) SK_LUT(2, 2, false, true, false, true, true)
+	SK_LUT(2, 2, false, true, true, false, true) SK_LUT(2, 2, false, true, false, false, true)
+	default: return nullptr;
+	}
+#undef SK_8X2
+#undef SK_LUT9
+#undef SK_LUT
+#undef SK_ID
+}
+
+template <bool DEMUX, int SLOTS>
+static const void *tile_pass_fn(int mode)
+{
+	switch (mode) {
+	case 0: return reinterpret_cast<const void *>(tile_pass_kernel<0, DEMUX, SLOTS>);
+	case 1: return reinterpret_cast<const void *>(tile_pass_kernel<1, DEMUX, SLOTS>);
+	case 2: return reinterpret_cast<const void *>(tile_pass_kernel<2, DEMUX, SLOTS>);
+	case 3: return reinterpret_cast<const void *>(tile_pass_kernel<3, DEMUX, SLOTS>);
+	default: return reinterpret_cast<const void *>(tile_pass_kernel<4, DEMUX, SLOTS>);
+	}
+}
+static const void *tile_pass_fn(const tileplan::MatePlan &mp, int mode)
+{
+	if (mp.demux) return tile_pass_fn<true, kSlots>(mode);
+	if (mp.slots == kSlotsTrim) return tile_pass_fn<false, kSlotsTrim>(mode);
+	return mp.slots == SK_SLOTS1 ? tile_pass_fn<false, SK_SLOTS1>(mode) : tile_pass_fn<false, kSlots>(mode);
 }
 
 bool blocked_shape_ok(const BlockedArgs &a)
@@ -2071,65 +2146,51 @@ hipError_t launch_tile_blocked(const BlockedArgs &a, int n_cu, hipStream_t st)
 	if (!blocked_shape_ok(a)) return hipErrorInvalidValue;
 	if ((a.n + kTileRows - 1) / kTileRows > (int64_t)1 << 30) return hipErrorInvalidValue;      // tiles are counted in 32 bits
 	const bool demux = a.in_bc >= 0;
-	// chunks in flight per stream: 2 / 3 / 4 measure the same on the two-mate pass (10.56-10.64 ms), 5 is slower
-	const int slots = a.n_mates == 1 ? SK_SLOTS1 : kSlots;
-	const void *fn;
-	if (a.n_mates == 1) fn = demux ? tile_blocked_fn<true, SK_SLOTS1>(a.qc.mode) : tile_blocked_fn<false, SK_SLOTS1>(a.qc.mode);
-	else fn = demux ? tile_blocked_fn<true, kSlots>(a.qc.mode) : tile_blocked_fn<false, kSlots>(a.qc.mode);
-	const int nchunkp = (((kTileRows * a.stride + 1023) >> 10) + slots - 1) / slots * slots;
-	int image = nchunkp * 1024;                                       // the LDS image takes whole chunks, trim or not
-	if (demux && image < 2048) image = 2048;
-	const int64_t ntiles = (a.n + kTileRows - 1) / kTileRows;
-	const int max_wg = a.n_mates == 1 ? 3 : (ntiles < (int64_t)n_cu * 4 * 2 * 16 ? 3 : 2);   // as launch_tile_pass
+	const void *fn = tile_blocked_fn(demux, a.n_mates, a.qc.mode);
+	const int image = tileplan::blocked_image(a.stride, tileplan::blocked_slots(a.n_mates), demux);
 	LaunchShape sh;
-	hipError_t e = plan_shape(fn, a.table, a.n, image, demux, 4, n_cu, 1, max_wg, sh);
+	hipError_t e = plan_shape(fn, tile_knobs(), a.table, a.n, image, demux, n_cu, tileplan::blocked_max_wg(a.n_mates, a.n, n_cu), sh);
 	if (e != hipSuccess) return e;
 	BlockedArgs bb = a;
 	void *kargs[] = {(void *)&bb, (void *)&sh.lp};
 	return hipLaunchKernel(fn, dim3(sh.grid), dim3(sh.block), kargs, sh.lds, st);
 }
 
-template <bool DEMUX, int SLOTS>
-static const void *tile_pass_fn(int mode)
+// the barcode phase as a launch of its own: the sheet's lookup table (one lookup per read; with the ctx's wide counters its adds are
+// atomics into lines of their own and nothing is folded per launch), or the matchers
+static hipError_t launch_demux(const TileArgs &b, const Knobs &k, const Shape &s, const tileplan::DemuxPlan &dp, int n_cu, hipStream_t st)
 {
-	switch (mode) {
-	case 0: return reinterpret_cast<const void *>(tile_pass_kernel<0, DEMUX, SLOTS>);
-	case 1: return reinterpret_cast<const void *>(tile_pass_kernel<1, DEMUX, SLOTS>);
-	case 2: return reinterpret_cast<const void *>(tile_pass_kernel<2, DEMUX, SLOTS>);
-	case 3: return reinterpret_cast<const void *>(tile_pass_kernel<3, DEMUX, SLOTS>);
-	default: return reinterpret_cast<const void *>(tile_pass_kernel<4, DEMUX, SLOTS>);
+	const void *fn = demux_fn(dp.id);
+	if (!fn) return hipErrorInvalidValue;
+	const bool by_table = dp.id.family != tileplan::kMatcherTile;
+	TileArgs bb = b;
+	hipError_t e;
+	if (by_table) {
+		int wg = 0;
+		e = occupancy(fn, 1, &dp.nw, &dp.lds, &wg);
+		if (e != hipSuccess) return e;
+		if (wg < 1) return hipErrorInvalidValue;
+		const int64_t grid = tileplan::grid_for(tileplan::lookup_units(s), dp.nw, n_cu, dp.wg(wg));
+		if (tileplan::drops_count_rep(grid, s)) bb.table.count_rep = nullptr;
+		void *kargs[] = {(void *)&bb, (void *)&dp.lp};
+		e = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(kWave * dp.nw), kargs, dp.lds, st);
+	} else {
+		e = plan_and_launch(fn, k, b, b.bc_stride, true, n_cu, 0, st);
 	}
+	if (e == hipSuccess && !(by_table && bb.counts_wide)) e = launch_counts_fold(bb, by_table, st);      // (the wide counters are folded when somebody reads them)
+	return e;
 }
 
-// ONE statement of when the barcode phase rides in the tile pass: launch_tile_pass decides with it, and the C-ABI layer asks it
-// whether a call needs the neighbourhood table built (a call that does not fuse takes the table for its barcode launch; were
-// the two to disagree, no table would be there and the S x L matchers would run instead: correct, 10-50 x slower).
-// any_mate = some mate has work; a stride beyond kMaxTileStride sends the mates to the fallback kernels, which fuse nothing.
-// SK_NO_FUSED_DEMUX (tests, tools) is read once per process.
-bool tile_pass_fuses_demux(bool has_bc, bool any_mate, int stride, bool has_bitsliced, int G, int S, int bc_stride)
-{
-	static const bool env_no_fuse = getenv("SK_NO_FUSED_DEMUX") != nullptr;
-	return has_bc && any_mate && stride <= kMaxTileStride && has_bitsliced && G <= 4 && S > 0 && kTileRows * bc_stride <= 2048 && !env_no_fuse;
-}
-
-// does a barcode-phase launch of these arguments take the sheet's lookup table (one lookup per read; with the ctx's wide counters its
-// adds are atomics into lines of their own and nothing is folded per launch)?
-bool tile_pass_demux_by_table(const TileArgs &b)
-{
-	const bool env_no_hash = getenv("SK_NO_HASH_DEMUX") != nullptr;
-	const bool want_detail = b.lowest_diff || b.first_idx || b.last_idx;
-	return (b.table.nbr.tab || b.table.nbr.pair.tab) && (!want_detail || b.detail_matched) && kTileRows * b.bc_stride <= 2048 && !env_no_hash;
-}
-
-hipError_t launch_tile_pass(const TileArgs &a, int n_cu, hipStream_t st)
+hipError_t launch_tile_pass(const TileArgs &a, const Knobs &k, int n_cu, hipStream_t st)
 {
 	if (a.n <= 0) return hipSuccess;
 	if ((a.n + kTileRows - 1) / kTileRows > (int64_t)1 << 30) return hipErrorInvalidValue;      // the kernels count tiles in 32 bits (2^36 rows: no device holds them)
+	const Shape s = tile_shape(a, n_cu);
+	const tileplan::DemuxPlan dp = tileplan::demux_plan(k, s);
+	const tileplan::MatePlan mp = tileplan::mate_plan(k, s);
+	if (s.many && !dp.many_ok) return hipErrorInvalidValue;      // (the caller asks many_ok first: sk_fused_pass_many_dev)
 	TileArgs b = a;
-	bool any_mate = false;
-	for (int mi = 0; mi < b.n_mates; mi++) any_mate = any_mate || b.mate[mi].out_seq || b.mate[mi].lowest_k;
-	// rows that do not fit an LDS tile: trim falls back to the row-per-thread kernel, mask to the flat one
-	if (any_mate && b.stride > kMaxTileStride) {
+	if (mp.fallback)
 		for (int mi = 0; mi < b.n_mates; mi++) {
 			MateDev &mt = b.mate[mi];
 			if (mt.out_seq) {
@@ -2145,142 +2206,17 @@ hipError_t launch_tile_pass(const TileArgs &a, int n_cu, hipStream_t st)
 			}
 			mt.out_seq = nullptr; mt.lowest_k = nullptr;
 		}
-		any_mate = false;
-	}
-	// the barcode phase rides in the tile pass when the bit-sliced matcher applies (S <= 128) and the tile's
-	// barcodes fit two 1 KiB register chunks; otherwise it is its own launch beside the mate pass
-	const bool fuse_demux = tile_pass_fuses_demux(b.bc != nullptr, any_mate, b.stride, b.table.bs != nullptr, b.table.G, b.table.S, b.bc_stride);
-	if (b.bc && !fuse_demux) {
-		// the sheet has a neighbourhood table and the call wants the decision alone, or the detail columns of matched rows
-		// only (TileArgs::detail_matched): one lookup per read
-		const bool env_no_hash = getenv("SK_NO_HASH_DEMUX") != nullptr;
-		const bool want_detail = b.lowest_diff || b.first_idx || b.last_idx;
-		const bool by_table = tile_pass_demux_by_table(b);
-		hipError_t e;
-		TileArgs bb = b;
-		if (b.many && !by_table) return hipErrorNotSupported;      // (many batches in one launch: the table's kernels only)
-		if (by_table) {
-			const LutDev &t = b.table.nbr;
-			// rows on dword boundaries whose key is one or two dwords: lane r loads row r as it lies (one 8 B/lane load for 8-byte
-			// rows); every other shape gathers (demux_lut_kernel).  (SK_DEMUX_DIRECT=0 / SK_DEMUX_LDSTAB=0 force the other forms:
-			// the tests run every kernel on the same inputs)
-			const bool pair = t.pair.tab != nullptr;                  // the factored form (sk_lut.h): its three tables always in LDS
-			const char *env_direct = getenv("SK_DEMUX_DIRECT");
-			const bool direct = !pair && (b.bc_stride & 3) == 0 && t.W2 == 0 && t.W1 <= 2 && 4 * t.W1 <= b.bc_stride && (!env_direct || atoi(env_direct) != 0);
-			const char *env_ldstab = getenv("SK_DEMUX_LDSTAB");
-			const int table_bytes = pair ? t.pair.bytes : (t.mask + 1) * 2 * 8;
-			const bool ldstab = pair || (table_bytes <= (128 << 10) && (!env_ldstab || atoi(env_ldstab) != 0));
-			// rows of exactly 8 key bytes on an 8-byte pitch: two rows per lane (demux_lut8x2_kernel) — always when the detail columns
-			// are written too, and for the decision alone from 1.5 M rows (after round 4's instruction diet: 10 M rows 20.4 us
-			// against 23.6 with one row per lane, 2 M 8.3 / 9.5, 6 M 14.6 / 16.9, 100 M the same; 1 M 7.8 / 7.3: a workgroup's
-			// first tile is its whole share there).  SK_DEMUX_ROWS2=0 / 1 force the choice (tools/demux_ab.py, tests).
-			const char *env_rows2 = getenv("SK_DEMUX_ROWS2");
-			const bool rows2 = direct && t.W1 == 2 && b.bc_stride == 8 && (env_rows2 ? atoi(env_rows2) != 0 : (want_detail || b.n >= 1500000));
-			const void *fn = pair ? (t.W1 == 1 ? (want_detail ? reinterpret_cast<const void *>(demux_lut_kernel<1, 1, false, true, true, true>) : reinterpret_cast<const void *>(demux_lut_kernel<1, 1, false, true, false, true>))
-			                                   : (want_detail ? reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, true, true, true>) : reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, true, false, true>)))
-			                 : rows2 ? (ldstab ? (want_detail ? reinterpret_cast<const void *>(demux_lut8x2_kernel<true, true>) : reinterpret_cast<const void *>(demux_lut8x2_kernel<true, false>))
-			                                 : (want_detail ? reinterpret_cast<const void *>(demux_lut8x2_kernel<false, true>) : reinterpret_cast<const void *>(demux_lut8x2_kernel<false, false>)))
-			                 : ldstab ? (want_detail ? demux_lut_fn<true, true>(t.W1, t.W2, direct) : demux_lut_fn<true, false>(t.W1, t.W2, direct))
-			                          : (want_detail ? demux_lut_fn<false, true>(t.W1, t.W2, direct) : demux_lut_fn<false, false>(t.W1, t.W2, direct));
-			if (b.many) {
-				// many batches in one launch: the two kernels that serve the benchmark's sheets have the form; any other shape is the caller's loop
-				if (!ldstab) return hipErrorNotSupported;
-				// (the gathered-row kernel has the form too and keeps it for A/B — SK_LUT_MANY_GATHER=1 — but its many-batch launch is SLOWER than its
-				// launches back to back, which is what the caller's loop does: 96 dual-index, 4 x 10 M rows from HBM, 0.51 of the HBM peak against 0.56)
-				const char *mg = getenv("SK_LUT_MANY_GATHER");
-				const bool many_gather = mg && atoi(mg) != 0;
-				if (rows2) fn = want_detail ? reinterpret_cast<const void *>(demux_lut8x2_kernel<true, true, true>) : reinterpret_cast<const void *>(demux_lut8x2_kernel<true, false, true>);
-				else if (many_gather && !direct && t.W1 == 2 && t.W2 == 2)
-					fn = pair ? (want_detail ? reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, true, true, true, true>) : reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, true, false, true, true>))
-					          : (want_detail ? reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, true, true, false, true>) : reinterpret_cast<const void *>(demux_lut_kernel<2, 2, false, true, false, false, true>));
-				else return hipErrorNotSupported;
-			}
-			LdsPlan lp{};
-			lp.use_lds_hist = 1;                                      // S + 3 <= kMaxLdsHist
-			lp.hist_off = 0;
-			lp.table_bytes = ldstab ? table_bytes : 0;
-			lp.tiles_off = (((b.table.S + 3) * 4 + 15) & ~15) + lp.table_bytes;
-			lp.tile_slot = 4 * kTileRows * 4;                         // rows come straight from memory: no image; 1 KiB per wave in which a quad's codes change lanes
-			// sixteen waves share a table copy; eight once the call is long and the table leaves room for one workgroup per CU only
-			// (rows from HBM, 100 M pairs of the 96 dual-index sheet: 381 us against 398; shorter calls want the waves)
-			int nw = ldstab ? ((lp.table_bytes > (64 << 10) && b.n >= 4000000) ? 8 : 16) : 4;
-			// tuning knobs (tools/lut_cold_ab.py), read once per process; the kernels that keep their table in the vector cache are
-			// compiled for 256 threads, so they take 4 waves at most
-			static const int env_nw = [] { const char *v = getenv("SK_LUT_NW"); return v ? atoi(v) : 0; }();
-			static const int env_wg = [] { const char *v = getenv("SK_LUT_WG"); return v ? atoi(v) : 0; }();
-			if (env_nw >= 1 && env_nw <= (ldstab ? 16 : 4)) nw = env_nw;
-			while (nw > 4 && lp.tiles_off + nw * lp.tile_slot > 160 * 1024) nw >>= 1;
-			const int lds = lp.tiles_off + nw * lp.tile_slot;
-			struct Occ { int dev; const void *fn; int lds, nw, wg; };
-			static std::mutex occ_m;
-			static std::vector<Occ> occ;
-			int dev = 0, wg = 0;
-			e = hipGetDevice(&dev);
-			if (e != hipSuccess) return e;
-			{
-				std::lock_guard<std::mutex> lk(occ_m);
-				for (const Occ &o : occ) if (o.dev == dev && o.fn == fn && o.lds == lds && o.nw == nw) wg = o.wg;
-			}
-			if (wg == 0) {
-				e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-				if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, kWave * nw, (size_t)lds);
-				if (e != hipSuccess) return e;
-				if (wg < 1) return hipErrorInvalidValue;
-				std::lock_guard<std::mutex> lk(occ_m);
-				occ.push_back({dev, fn, lds, nw, wg});
-			}
-			// sixteen waves per CU whatever the table leaves room for: with its rows coming from HBM a 10 M-row call of the cfg 3 sheet
-			// took 25.3 us on sixteen and 26.7 on thirty-two (each wave's first load is a full HBM round trip before anything
-			// moves, and twice the waves end in twice the stragglers); 100 M rows the same (tools/lut_cold_ab.py)
-			if (ldstab && wg > 1) wg = 1;
-			if (env_wg >= 1) wg = env_wg;
-			const int tile_rows = 4 * kTileRows;                      // a wave's unit: 256 rows in either kernel
-			const int64_t ntiles = b.many ? (int64_t)b.many_quads : (b.n + tile_rows - 1) / tile_rows, want = (ntiles + nw - 1) / nw, cap = (int64_t)n_cu * wg;
-			const int64_t grid = want < cap ? want : cap;
-			// a few hundred workgroups add to the counters directly; thousands go through the spread copies and the fold
-			if (grid <= 512 || bb.counts_wide) bb.table.count_rep = nullptr;
-			void *kargs[] = {(void *)&bb, (void *)&lp};
-			e = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(kWave * nw), kargs, lds, st);
-		} else {
-			e = plan_and_launch(reinterpret_cast<const void *>(demux_tile_kernel), b, b.bc_stride, true, 4, n_cu, st);
-		}
-		if (e == hipSuccess && !(by_table && bb.counts_wide)) e = launch_counts_fold(bb, by_table, st);      // (the wide counters are folded when somebody reads them)
+	if (dp.id.family != tileplan::kNoLaunch) {
+		hipError_t e = launch_demux(b, k, s, dp, n_cu, st);
 		if (e != hipSuccess) return e;
 	}
-	if (!any_mate) return hipSuccess;
-	int row_bytes = 0;
-	for (int mi = 0; mi < b.n_mates; mi++)
-		if (b.mate[mi].lowest_k) row_bytes = b.stride;          // only the trim scan needs the LDS image
+	if (!mp.tiles) return hipSuccess;
 	const int64_t total = b.n * (int64_t)b.stride;
 	if (total & 3)
 		for (int mi = 0; mi < b.n_mates; mi++)
 			if (b.mate[mi].out_seq) mask_tail_kernel<<<1, 4, 0, st>>>(b.mate[mi].seq, b.mate[mi].qual, b.mate[mi].out_seq, total, b.qc.min_baseq);
-	if (fuse_demux && b.bc_stride > row_bytes) row_bytes = b.bc_stride;      // the barcode phase puts the tile's barcodes into the wave's LDS slot
-	// Shape of the phase kernel: workgroups of four waves, and how many of them a CU holds depends on what the pass is
-	// bound by (tools/waves_exp.py, tools/small_n.py; same buffers, one process):
-	//  * two mates, streaming-bound: TWO per CU (eight resident waves).  More waves keep more requests in flight than
-	//    HBM serves well: 62.5 M clusters 9.52 ms with 16 waves, 9.31 ms with 8; at 16 M clusters +5 % for the fused
-	//    pass, +14 % for mask + trim of two mates.  Short inputs (fewer than 16 tiles per wave) take three, to shorten
-	//    the tail: 1 M clusters 176 -> 160 us;
-	//  * one mate with the mask: three (1 M reads 101 -> 89 us, no difference at 16 M);
-	//  * trim alone, bound by the scan's VALU work: four (16 M reads of full-length scans 1.19 -> 0.80 ms).
-	const int64_t ntiles = (b.n + kTileRows - 1) / kTileRows;
-	const int wg_two_mates = ntiles < (int64_t)n_cu * 4 * 2 * 16 ? 3 : 2;
-	if (fuse_demux) return plan_and_launch(tile_pass_fn<true, kSlots>(b.qc.mode), b, row_bytes, true, 4, n_cu, st, 1, wg_two_mates);
-	b.bc = nullptr;
-	// One mate = two read streams at most: keep four chunks per stream in flight instead of two (mask + trim of one
-	// mate 4.9 -> 5.1 TB/s at 16 M x 150; no gain with two mates or the barcode phase).  Trim alone reads ONE stream and
-	// spends most of its time in the scan: there the whole next tile (ten chunks at 150 bp) is kept in flight
-	// (3.6 -> 3.9 -> 4.3 TB/s with 2 / 4 / 10 slots on read-like qualities).
-	int active = 0;
-	bool any_mask = false;
-	for (int mi = 0; mi < b.n_mates; mi++) {
-		active += (b.mate[mi].out_seq || b.mate[mi].lowest_k) ? 1 : 0;
-		any_mask = any_mask || b.mate[mi].out_seq;
-	}
-	if (active == 1 && !any_mask) return plan_and_launch(tile_pass_fn<false, 10>(b.qc.mode), b, row_bytes, false, 4, n_cu, st, 1, 4);
-	if (active == 1) return plan_and_launch(tile_pass_fn<false, SK_SLOTS1>(b.qc.mode), b, row_bytes, false, 4, n_cu, st, 1, 3);
-	return plan_and_launch(tile_pass_fn<false, kSlots>(b.qc.mode), b, row_bytes, false, 4, n_cu, st, 1, wg_two_mates);
+	if (!mp.demux) b.bc = nullptr;
+	return plan_and_launch(tile_pass_fn(mp, b.qc.mode), k, b, mp.row_bytes, mp.demux, n_cu, mp.max_wg, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
