@@ -15,12 +15,14 @@
 // characters 0..14 follow in the low word, 15..30 in the high word: 31 characters at most.  The high word is
 // stored inverted so that 0 means "claimed but not published yet" on a table that is cleared with memset.
 #include <hip/hip_runtime.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "sk_censusplan.h"
 #include "sk_internal.h"
 
 namespace sk {
@@ -35,21 +37,10 @@ struct CensusSlot {          // 32 bytes, one HBM sector pair
 	u64 first_inv;           // ~(lowest row index seen): atomicMax keeps the first occurrence
 };
 
-// The partition path (large launches): keys the front tables had no room for leave the front kernel as 16-byte records,
-// partitioned by the region of the HBM table their slot lies in (kSpillBuckets regions) INSIDE that kernel: a record draws
-// its place in the (workgroup, bucket) region of the record array from the workgroup's cursor of that bucket (an LDS add with
-// return) and goes there with one 16-byte store.  A wave's 64 records go to 64 different lines; the lines of the
-// workgroups' open regions (256 x 128 x 128 B = 4 MiB) stay in L2 until they are full.  The records are combined per bucket in
-// LDS before they touch the table (census_add below).  (Through round 4 the records were written as they came, then
-// counted, scanned and moved to 1 024 buckets by two more kernels: every record crossed HBM four times — 62 + 7 of a noisy
-// launch's 314 us of kernels and two of its five kernel boundaries.  A first form of this round staged the records per
-// bucket in each wave's LDS and flushed whole pieces: the stages took the front table's room and the flushes its time.)
-constexpr int kSpillBucketsLog2 = 8;
-constexpr int kSpillBuckets = 1 << kSpillBucketsLog2;
+// The partition path (large launches) and its constants — kSpillBuckets regions of the HBM table, records of barcodes of at most
+// kSpillMaxLen characters, kSpillMaxGrid workgroups — are stated in sk_censusplan.h, with every other constant host and device share.
 // a key's bucket: the top bits of its hash — the 1/256 of LEVEL 1 its home slot lies in, whatever the tables' sizes
 __device__ __forceinline__ uint32_t census_bucket(uint32_t h) { return h >> (32 - kSpillBucketsLog2); }
-constexpr int kSpillMaxLen = 24;         // 24 characters = 96 bits; the key's fourth dword is then the marker alone
-constexpr int kSpillMaxGrid = 1024;      // workgroups of the front kernel the combine pass can address
 
 struct CensusSpill {
 	uint4 *key = nullptr;        // [grid][kSpillBuckets][cap]: a record is the key's first three dwords (barcodes of at most
@@ -66,10 +57,7 @@ struct CensusSpill {
 	u32 merge_copies = 0;        // != 0: the front kernel's tables leave their workgroup as records, not as inserts
 };
 
-// A record's fourth dword: the row index within the launch (a launch is at most 2^25 rows: kCensusChunk) and how many rows
-// the record stands for — digit d = 1..31 at level v = 0..3, d << (5 v) rows: a row the front tables had no room for is
-// (d, v) = (1, 0); a front-table key counted c times leaves the workgroup as the non-zero base-32 digits of c.
-constexpr int kRecRowBits = 25;
+// A record's fourth dword: the row index within the launch (kRecRowBits bits) and how many rows the record stands for (sk_censusplan.h)
 __device__ __forceinline__ u32 census_rec_row(u32 w) { return w & ((1u << kRecRowBits) - 1u); }
 __device__ __forceinline__ u32 census_rec_count(u32 w) { return (((w >> 27) & 31u) + 1u) << (5u * ((w >> kRecRowBits) & 3u)); }
 
@@ -89,10 +77,6 @@ struct Census {
 };
 
 constexpr int kCensusStats = 4;          // [0] distinct keys, [1] rows counted, [2] rows rejected, [3] probe overflows
-constexpr u64 kInitialSlots = 1ull << 26;   // 2 GiB of the 288: one launch may then take 32 M rows (SK_CENSUS_SLOTS_LOG2 overrides; tests use it)
-constexpr u32 kLogCap = 1u << 16;           // claim-log entries per region: 256 x 65 536 slots = 64 MiB (SK_CENSUS_LOG_CAP_LOG2 overrides; tests shrink it)
-constexpr int64_t kCensusChunk = 1 << 25;   // most rows per launch; the table is grown between launches so that it is never
-constexpr int64_t kCensusMinChunk = 1 << 22;   // more than half full even if every row of the next launch is a new key
 constexpr int kLdsSlots = 2048;
 constexpr int kLdsProbes = 8;             // (3 through round 4, when an item met a hundred distinct keys: with 256 buckets a noisy item meets 430 in 2 048
                                           // slots, and a key that finds no place sends every one of its records to HBM by itself)
@@ -541,19 +525,12 @@ struct CensusArgs {
 	                          // protocol the fast look leans on (tests/test_census_isa.py guards the compiler side); ~3 x slower
 };
 
-constexpr int kCensusWaves = 16;          // waves per workgroup (one per CU): they share the front table
-constexpr int kCensusMaxStride = 64;      // a row's span is at most 9 dwords (census_load_rows)
-
 __device__ __forceinline__ void census_wave_fence()
 {
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-constexpr int kCensusMaxSub = 2;          // 64-row tiles per wave and step (three and four timed the same and needed scratch for the longest strings)
-constexpr int kCensusStepBytes = 5120;    // most bytes per wave and step before the cap on R (census_add)
-constexpr int kCensusQueue = 128;         // flush queue entries (16 B key + 4 B row): fewer than 64 left over + one tile's 64
 
 template <int R, int NW> struct CensusRowRegs { u32 g[R][NW + 1]; int32_t code[kCensusMaxSub] = {0, 0}; };
 
@@ -644,6 +621,7 @@ template <int R, int NW, bool SPILL> __global__ __launch_bounds__(kCensusWaves *
 	uint8_t *slot = census_smem + front_bytes + (size_t)wave * tile_slot;
 	u32 *lh = reinterpret_cast<u32 *>(census_smem + front_bytes + (size_t)nwave * tile_slot + 64);      // SPILL: the workgroup's records per bucket (its cursors into the bucket regions)
 	constexpr int kQueueCap = 64 + R * 64;
+	static_assert(kQueueCap == censusplan::queue_cap(R), "the plan's wave slot is sized for another queue (sk_censusplan.h)");
 	u32 *const qr = reinterpret_cast<u32 *>(slot);
 	u32 *const qx = qr + kQueueCap;
 	u32 n_carry = 0u;                                                  // wave-uniform: entries left over from the step before
@@ -1347,7 +1325,8 @@ __global__ __launch_bounds__(256) void census_compact_kernel(const CensusSlot *t
 }
 
 // the instantiations: R tiles per step x dwords per row (2, 5, 8: barcodes of at most 8, 20, 31 characters) x spill
-constexpr int kCensusVariants = kCensusMaxSub * 3 * 2;
+// (in the order of censusplan::variant)
+constexpr int kCensusVariants = censusplan::kVariants;
 static const void *census_variant(int v)
 {
 	static const void *const tab[kCensusVariants] = {
@@ -1360,8 +1339,27 @@ static const void *census_variant(int v)
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
+// What a launch is made of is decided in sk_censusplan.h (and tested on the CPU: tests/cpp/censusplan_test.cpp).  Its LDS layout is
+// the kernel's: one side changed alone does not compile (the queue capacity is held to the plan's inside census_kernel).
+static_assert(censusplan::front_entry_bytes(0) == FrontShape<2>::kEntryBytes && censusplan::front_entry_bytes(1) == FrontShape<5>::kEntryBytes &&
+              censusplan::front_entry_bytes(2) == FrontShape<8>::kEntryBytes, "the plan's front-table entry is not the kernel's");
+static_assert(censusplan::class_dwords(0) == 2 && censusplan::class_dwords(1) == 5 && censusplan::class_dwords(2) == 8, "the instantiated row widths");
 
 static void census_spill_free(Census *cs);
+
+// The SK_CENSUS_* variables, read on every call of census_create and census_add — the tests and the A/B tools change them between
+// calls inside one process — in ONE walk over the environment, which costs what one getenv does.
+static censusplan::Knobs census_knobs()
+{
+	censusplan::Knobs k;
+	for (char **e = environ; e && *e; e++) {
+		const char *s = *e;
+		if (strncmp(s, "SK_CENSUS_", 10) != 0) continue;
+		const char *eq = strchr(s + 10, '=');
+		if (eq) censusplan::set_knob(k, s + 10, (size_t)(eq - (s + 10)), eq + 1);
+	}
+	return k;
+}
 
 static hipError_t census_alloc_table(Census *cs, u64 slots, hipStream_t st)
 {
@@ -1376,19 +1374,14 @@ hipError_t census_create(Census **out, hipStream_t st)
 	Census *cs = new Census();
 	hipError_t e = hipMalloc((void **)&cs->stats, kCensusStats * sizeof(u64));
 	if (e == hipSuccess) e = hipMemsetAsync(cs->stats, 0, kCensusStats * sizeof(u64), st);
-	u64 init_slots = kInitialSlots;
-	if (const char *ev = getenv("SK_CENSUS_SLOTS_LOG2")) {
-		const int lg = atoi(ev);
-		if (lg >= 10 && lg <= 32) init_slots = 1ull << lg;
-	}
-	if (e == hipSuccess) e = census_alloc_table(cs, init_slots, st);
-	cs->log_cap = kLogCap;
-	if (const char *ev = getenv("SK_CENSUS_LOG_CAP_LOG2")) { const int lg = atoi(ev); if (lg >= 0 && lg <= 20) cs->log_cap = 1u << lg; else if (lg == -1) cs->log_cap = 0u; }
+	const censusplan::Knobs k = census_knobs();
+	if (e == hipSuccess) e = census_alloc_table(cs, k.initial_slots, st);
+	cs->log_cap = k.log_cap;
 	if (e == hipSuccess) e = hipMalloc((void **)&cs->log, (size_t)kLogRegions * std::max(cs->log_cap, 1u) * sizeof(u32));
 	if (e == hipSuccess) e = hipMalloc((void **)&cs->log_count, (size_t)kLogRegions * 32 * sizeof(u32));
 	if (e == hipSuccess) e = hipMemsetAsync(cs->log_count, 0, (size_t)kLogRegions * 32 * sizeof(u32), st);
 	for (int v = 0; v < kCensusVariants; v++)
-		if (e == hipSuccess) e = hipFuncSetAttribute(census_variant(v), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		if (e == hipSuccess) e = hipFuncSetAttribute(census_variant(v), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
 	if (e != hipSuccess) { census_destroy(cs); return e; }
 	*out = cs;
 	return hipSuccess;
@@ -1481,9 +1474,8 @@ static hipError_t census_reserve(Census *cs, u64 incoming, int n_cu, hipStream_t
 {
 	const u64 need = 2 * (cs->distinct + incoming);
 	if (need <= cs->slots) return hipSuccess;
-	u64 slots = cs->slots;
-	while (slots < need) slots <<= 1;
-	if (slots > (1ull << 32)) return hipErrorOutOfMemory;      // the hash is 32 bits wide (and this would be a 128 GiB table)
+	const u64 slots = censusplan::grown_slots(cs->slots, need);
+	if (slots == 0) return hipErrorOutOfMemory;
 	CensusSlot *old_tab = cs->tab;
 	const u64 old_slots = cs->slots;
 	hipError_t e = census_alloc_table(cs, slots, st);
@@ -1530,80 +1522,28 @@ static hipError_t census_spill_reserve(Census *cs, int grid, u32 cap, hipStream_
 	return hipSuccess;
 }
 
-constexpr int64_t kSpillMinRows = 1 << 19;      // smaller launches insert directly: the partition path is four more kernels.  Measured (tools/census_small.py, round 4,
-                                                // insert-in-place / partition, noisy run): 250 k rows 58 / 68 us, 1 M 100 / 80, 4 M 187 / 110, 8 M 308 / 149; rows that
-                                                // are all sheet barcodes: 250 k 40 / 47, 1 M 65 / 55, 4 M 84 / 68 (round 3's crossover was at 8 M rows)
-
 hipError_t census_add(Census *cs, const uint8_t *bc, int bc_stride, int L, int64_t n, const int32_t *assign, int64_t row_base,
                       int n_cu, hipStream_t st)
 {
-	if (bc_stride > kCensusMaxStride) return hipErrorInvalidValue;
-	int R = kCensusStepBytes / (64 * bc_stride);
-	R = R < 1 ? 1 : (R > kCensusMaxSub ? kCensusMaxSub : R);
-	if (const char *ev = getenv("SK_CENSUS_TILES")) { const int v = atoi(ev); if (v >= 1 && v <= R) R = v; }      // experiments
-	const int nw_dwords = L <= 8 ? 2 : (L <= 20 ? 5 : 8);
-	// (two 64-row tiles per step at most: more bought nothing — R = 1 ... 4 timed the same within the boxes' noise in round 4 — and
-	// a tile's 64 queue entries are 43 front-table entries of a 17-byte sheet)
-	// a wave's slot: its queue of rows that take the long way, 64 left over + the step's R x 64, each its NW dwords and its
-	// row's index; behind it the flush queue of the launches that insert by themselves (over the queue's dead part)
-	auto slot_bytes = [&](int r, bool spill_layout) {
-		const int queue_cap = 64 + r * 64;
-		int bytes = queue_cap * (4 * nw_dwords + 4);
-		if (!spill_layout) {
-			const int flush_end = ((queue_cap * 4 + 64 * 4 * nw_dwords + 15) & ~15) + kCensusQueue * 20;
-			if (bytes < flush_end) bytes = flush_end;
-		}
-		return (bytes + 15) & ~15;
-	};
-	// the front table takes what is left of the CU's 160 KiB (SK_CENSUS_FRONT_ENTRIES: tests shrink it so that small inputs
-	// walk "no room in either place")
-	const int nw_class = L <= 8 ? 0 : (L <= 20 ? 1 : 2);
-	const int front_entry_bytes = nw_class == 2 ? 52 : 36;            // FrontShape<NW>::kEntryBytes
-	auto plan_lds = [&](int r, bool spill_layout, int &tile_slot, int &front_entries) {
-		tile_slot = slot_bytes(r, spill_layout);
-		size_t lds = (size_t)kCensusWaves * tile_slot + 64 + (kSpillBuckets + 4) * sizeof(u32);      // + the workgroup's cursors and its step counter
-		front_entries = (int)((160 * 1024 - 16 - lds) / front_entry_bytes) & ~63;
-		if (const char *ev = getenv("SK_CENSUS_FRONT_ENTRIES")) { const int v = atoi(ev) & ~63; if (v >= 64 && v <= front_entries) front_entries = v; }
-		return lds + (((size_t)front_entries * front_entry_bytes + 15) & ~(size_t)15);
-	};
-	int wgs_per_cu = 1;
-	if (const char *ev = getenv("SK_CENSUS_WGS")) { const int v = atoi(ev); if (v >= 1 && v <= 4) wgs_per_cu = v; }      // experiments
-	int direct_pct = 50;                                    // SK_CENSUS_SPILL_MAX_PCT: more spilled rows than this share of a launch are inserted directly
-	if (const char *ev = getenv("SK_CENSUS_SPILL_MAX_PCT")) { const int v = atoi(ev); if (v >= 0 && v <= 100) direct_pct = v; }
-	int64_t spill_min_rows = kSpillMinRows;                 // SK_CENSUS_SPILL_MIN_ROWS_LOG2: tests lower it
-	if (const char *ev = getenv("SK_CENSUS_SPILL_MIN_ROWS_LOG2")) { const int lg = atoi(ev); if (lg >= 6 && lg <= 30) spill_min_rows = (int64_t)1 << lg; }
-	int direct_split = 8;                                   // SK_CENSUS_DIRECT_SPLIT: workgroups per region of census_direct_kernel (experiments)
-	if (const char *ev = getenv("SK_CENSUS_DIRECT_SPLIT")) { const int v = atoi(ev); if (v >= 1 && v <= 64) direct_split = v; }
-	int merge_copies = 1;                                   // SK_CENSUS_MERGE_RECORDS=0: the front kernel inserts its tables itself, as small launches do (A/B, tests)
-	if (const char *ev = getenv("SK_CENSUS_MERGE_RECORDS")) merge_copies = atoi(ev) != 0;
-	int spill_mode = -1;                                    // SK_CENSUS_SPILL=0/1: never / always (tests, experiments)
-	if (const char *ev = getenv("SK_CENSUS_SPILL")) spill_mode = atoi(ev) != 0;
-	// (SK_CENSUS_CHUNK_LOG2 / SK_CENSUS_MIN_CHUNK_LOG2: tests shrink the launches to walk the grow / smaller-bite decisions)
-	int64_t chunk = kCensusChunk, min_chunk = kCensusMinChunk;
-	if (const char *ev = getenv("SK_CENSUS_CHUNK_LOG2")) { const int lg = atoi(ev); if (lg >= 6 && lg <= kRecRowBits) chunk = (int64_t)1 << lg; }      // (a record's row index has kRecRowBits bits)
-	if (const char *ev = getenv("SK_CENSUS_MIN_CHUNK_LOG2")) { const int lg = atoi(ev); if (lg >= 6 && lg <= 30) min_chunk = (int64_t)1 << lg; }
-	{	// a launch's matrix stays below 2 GiB: the front kernel addresses it through one descriptor with 32-bit offsets
-		const int64_t max_rows = ((((int64_t)1 << 31) - (1 << 24)) / bc_stride) & ~(int64_t)63;
-		if (chunk > max_rows) chunk = max_rows;
-	}
-	if (min_chunk > chunk) min_chunk = chunk;
+	namespace plan = censusplan;
+	const plan::Knobs k = census_knobs();
+	const int R = plan::tiles_per_step(k, bc_stride);
+	if (R == 0) return hipErrorInvalidValue;
+	const int nw_class = plan::nw_class(L);
+	const int64_t chunk = plan::chunk_rows(k, bc_stride), min_chunk = plan::min_chunk_rows(k, chunk);
 	int64_t nr = 0;
 	for (int64_t o = 0; o < n; o += nr) {
-		// The launch must not be able to fill the table beyond one half even if every row is a new key.  When
-		// the bound on the key count says it could, fetch the exact count; then either take a smaller bite
-		// (at least kCensusMinChunk rows: launches have a fixed cost) or grow the table.
+		// a bite of the input the table has room for (the plan's rules), the table grown where it has none worth a launch
 		nr = (n - o) < chunk ? (n - o) : chunk;
 		hipError_t e = hipSuccess;
-		if (2 * (cs->distinct + (u64)nr) > cs->slots && !getenv("SK_CENSUS_TRUST_SLOTS")) {      // (the env: experiments with a table that is known to be large enough)
+		if (plan::bite_needs_count(cs->distinct, nr, cs->slots, k)) {
 			uint64_t s[4];
 			e = census_stats(cs, s, st);
 			if (e != hipSuccess) return e;
-			const int64_t room = (int64_t)(cs->slots / 2) - (int64_t)cs->distinct;
-			const int64_t least = nr < min_chunk ? nr : min_chunk;
-			if (room >= least) nr = nr < room ? nr : room;        // a smaller bite fits the table as it is
-			else e = census_reserve(cs, (u64)nr, n_cu, st);       // no room worth a launch: grow for the whole bite
+			const plan::Bite b = plan::bite_after_count(cs->distinct, cs->slots, nr, min_chunk, nr == n - o);
+			if (b.grow) e = census_reserve(cs, (u64)nr, n_cu, st);
 			if (e != hipSuccess) return e;
-			if (nr < n - o && nr >= 64) nr &= ~(int64_t)63;       // later launches start on a 16-byte boundary of the matrix
+			nr = b.nr;
 		}
 		cs->distinct += (u64)nr;                              // upper bound until the next census_stats()
 		CensusArgs a;
@@ -1615,43 +1555,29 @@ hipError_t census_add(Census *cs, const uint8_t *bc, int bc_stride, int L, int64
 		a.row_base = row_base + o;
 		a.t = census_tab_of(cs);
 		a.stats = cs->stats;
-		a.long_way_only = getenv("SK_CENSUS_LONG_WAY_ONLY") && atoi(getenv("SK_CENSUS_LONG_WAY_ONLY")) != 0;
-		bool spill = L <= kSpillMaxLen && (spill_mode < 0 ? nr >= spill_min_rows : spill_mode != 0);
-		// One tile per step for the launches that write records: the step's queue is a third smaller, and what it gives back goes
-		// to the front table (2 270 -> 2 950 entries for 17-byte rows) — the table's size is worth more than the second tile (32 M
-		// noisy rows 0.320 -> 0.312 ms, clean 0.245 -> 0.231; with 1 024 entries 0.34-0.41, with 512 0.53; tools/ab/census_env_ab.py)
-		const int Rk = (spill && nw_class >= 1 && !getenv("SK_CENSUS_TILES")) ? 1 : R;
-		auto grid_of = [&](int r) {
-			const int64_t groups = (nr + (int64_t)64 * r * kCensusWaves - 1) / ((int64_t)64 * r * kCensusWaves);
-			const int g = n_cu * wgs_per_cu;
-			return g > groups ? (int)groups : g;
-		};
-		int grid = grid_of(Rk);
+		a.long_way_only = k.long_way_only;
+		bool spill = plan::wants_spill(k, L, nr);
+		const int Rk = plan::tiles_for_launch(k, R, spill, nw_class);
+		const int grid = plan::grid(nr, Rk, n_cu, k);
 		a.sp = CensusSpill();
 		if (spill) {
-			// a (workgroup, bucket) region: twice the workgroup's share of a launch in which EVERY row is spilled and spreads evenly, and
-			// room for its front table's records; a piece that finds its region full is inserted by the front kernel itself
-			const int64_t nsteps = (nr + (int64_t)64 * Rk - 1) / ((int64_t)64 * Rk);
-			const int64_t per_wave = (nsteps + (int64_t)grid * kCensusWaves - 1) / ((int64_t)grid * kCensusWaves);
-			const int64_t wg_rows = per_wave * kCensusWaves * Rk * 64;
-			const int64_t cap = (((wg_rows + kSpillBuckets - 1) / kSpillBuckets) * 2 + 256 + 7) & ~(int64_t)7;
-			e = (grid <= kSpillMaxGrid && cap * kSpillBuckets < ((int64_t)1 << 27)) ? census_spill_reserve(cs, grid, (u32)cap, st) : hipErrorInvalidValue;
-			if (e != hipSuccess) { (void)hipGetLastError(); spill = false; grid = grid_of(Rk); }      // no room for the records: insert directly
+			const plan::Region rg = plan::spill_region(nr, Rk, grid);
+			e = rg.ok ? census_spill_reserve(cs, grid, rg.cap, st) : hipErrorInvalidValue;
+			if (e != hipSuccess) { (void)hipGetLastError(); spill = false; }      // no room for the records: insert directly (the tiles per step stay)
 			else {
 				a.sp = cs->sp;
-				a.sp.cap = (u32)cap;
+				a.sp.cap = rg.cap;
 				a.sp.grid = (u32)grid;
-				a.sp.direct_above = (u32)((uint64_t)nr * (uint64_t)direct_pct / 100);
-				a.sp.merge_copies = (u32)merge_copies;
+				a.sp.direct_above = plan::direct_above(nr, k);
+				a.sp.merge_copies = k.merge_records ? 1u : 0u;
 			}
 		}
-		int tile_slot = 0, front_entries = 0;
-		const size_t lds = plan_lds(Rk, spill, tile_slot, front_entries);
-		hipLaunchKernelGGL(reinterpret_cast<void (*)(const CensusArgs, const int, const int)>(const_cast<void *>(census_variant(((Rk - 1) * 3 + nw_class) * 2 + (spill ? 1 : 0)))),
-		                   dim3(grid), dim3(kCensusWaves * 64), lds, st, a, tile_slot, front_entries);
+		const plan::Layout l = plan::lds_layout(k, Rk, nw_class, spill);
+		hipLaunchKernelGGL(reinterpret_cast<void (*)(const CensusArgs, const int, const int)>(const_cast<void *>(census_variant(plan::variant(Rk, nw_class, spill)))),
+		                   dim3(grid), dim3(kCensusWaves * 64), (size_t)l.bytes, st, a, l.tile_slot, l.front_entries);
 		if (spill) {
-			census_combine_kernel<<<2 * n_cu, kCombineThreads, 0, st>>>(a);
-			census_direct_kernel<<<grid * direct_split, kDirectThreads, 0, st>>>(a, direct_split);
+			census_combine_kernel<<<plan::combine_grid(n_cu), kCombineThreads, 0, st>>>(a);
+			census_direct_kernel<<<plan::direct_grid(grid, k), kDirectThreads, 0, st>>>(a, k.direct_split);
 		}
 		e = hipGetLastError();
 		if (e != hipSuccess) return e;
