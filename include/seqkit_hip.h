@@ -466,7 +466,7 @@ int sk_bam_file_pairs_next(sk_ctx *ctx, sk_bam_pairs_window *w);
  * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
  * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
  * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
- * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample or sk_bam_file_merge, below, whose windows it hands out too):
+ * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample, sk_bam_file_recalc_tlen or sk_bam_file_merge, below, whose windows it hands out too):
  * SK_ERR_INVALID.                                                                                                                 */
 #define SK_REWRITE_TRIM_QNAMES     1
 #define SK_REWRITE_QNAME_FROM_TAGS 2
@@ -546,6 +546,38 @@ int sk_subsample_keep(uint64_t seed, uint64_t draw, float fraction);
 int sk_bam_file_subsample(sk_ctx *ctx, const char *path, float fraction, uint64_t seed, int level /* 0 stored, 1 deflate */,
                           uint64_t window_bytes /* 0 = default */, int64_t *n_records, int64_t *n_total, uint64_t *raw_bytes, int *handled,
                           double info[8]);
+
+/* ---- BAM out for `sam recalculate tlen` (src/sam_recalculate_tlen.rs:42-111) ----------------------------------------------------
+ * sk_bam_file_recalc_tlen: sk_bam_file_rewrite's front half, window pipeline and header; a record is written byte for byte except its
+ * TLEN (the 4 bytes at record offset 32), or not at all.  A record is a candidate iff it is paired (0x1), mapped and its mate mapped
+ * (neither 0x4 nor 0x8), refID == next refID, |pos - next pos| <= max_len (in 64 bits) and bits 0x10 and 0x20 differ; every other
+ * record is written with TLEN 0.  The candidates' key is the qname; in file order the 1st, 3rd, 5th .. candidate of a key waits, and
+ * the 2nd, 4th .. is the mate of the one just before it (the reference's map, whose entry is removed when the mate arrives).  For a
+ * pair, earlier record a and later b, all in 64 bits: start(x) = pos, or for a reverse read (0x10) the CIGAR's end_pos as SK_COL_END
+ * less 1; t = |start(b) - start(a)| + 1, negated when pos(b) > pos(a), and 0 when start(b) < start(a) and b is reverse or start(b) >
+ * start(a) and b is not; b gets the low 32 bits of t, a those of -t.  A candidate still waiting at the end is discarded: not written.
+ * *n_records: the records written; *n_discarded: those discarded; *raw_bytes: the whole output BAM, inflated.  The windows come from
+ * sk_bam_file_rewrite_next under its rules, first and n numbering the records WRITTEN; a file none of whose records is written yields,
+ * as a file without records does there, one window: the header's members and the EOF block.
+ * sk_bam_file_recalc_tlen_discarded: the names of discarded records first .. first + n - 1, in file order, into n slots of 256 bytes,
+ * each the qname and NULs up to the slot's end.  Valid from sk_bam_file_recalc_tlen's return (*handled = 1) until the next
+ * sk_bam_file_* call on the ctx other than sk_bam_file_rewrite_next, after the last window too; a range outside [0, *n_discarded], or
+ * no such call to ask: SK_ERR_INVALID.
+ * *handled = 0 (info[5] = -(30 + bits)) leaves the file to the caller's reader, nothing written: bit 1 a paired, mapped record with a
+ * mapped mate and 0x100 or 0x800 (the reference ends there), 2 a pair whose records have equal 0x40 bits (the reference's assert), 8 a
+ * record whose variable part is shorter than its fields, 16 a qname byte >= 0x80 on any record (the reference panics on a name that is
+ * not UTF-8: the caller's reader decides exactly) or a NUL inside a qname (a slot could not say where it ends), 32 a CIGAR operation code above 8 on a reverse candidate (the reference panics
+ * there if the record ends up in a pair: the caller's reader decides exactly), 64 two different keys with one hash (verified byte for
+ * byte, never guessed; records linked under such a hash may add 2 or 32); info[5] = -21: 2^32 records or more, or the working memory
+ * cannot be had: 16 B per record for the offsets, 8 B
+ * per record and 1 MiB at most for the TLENs, the discard list and its name slots, and 32 B per record and the sort's scratch for the
+ * passes where those do not fit into the device buffer of the compressed file, which is idle by then (SK_TLEN_OWN_MEMORY set: never
+ * there; for tests).  max_len <= 0 or a bad level: SK_ERR_INVALID.  level, window_bytes: as sk_bam_file_rewrite.  SK_TLEN_KEY_BITS=k
+ * (1 .. 63, read per call) keeps only the low k bits of the hash: a knob for tests of the collision check, of no other use.       */
+int sk_bam_file_recalc_tlen(sk_ctx *ctx, const char *path, int64_t max_len, int level /* 0 stored, 1 deflate */,
+                            uint64_t window_bytes /* 0 = default */, int64_t *n_records, int64_t *n_discarded, uint64_t *raw_bytes,
+                            int *handled, double info[8]);
+int sk_bam_file_recalc_tlen_discarded(sk_ctx *ctx, int64_t first, int64_t n, uint8_t *names /* HOST: n slots of 256 bytes */);
 
 /* ---- BAM out for `sam merge` (src/sam_merge.rs:58-103) -----------------------------------------------------------------------
  * sk_bam_file_merge: sk_bam_file_rewrite's front half for each of n_paths files (2 .. 99), its window pipeline and header (input 1's).

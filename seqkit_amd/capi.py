@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_merge", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_on_target_set_regions", "sk_on_target_add", "sk_on_target_add_dev", "sk_on_target_get",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
@@ -255,6 +255,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_subsample_keep": (i32, [C.c_uint64, C.c_uint64, C.c_float]),
         "sk_bam_file_merge": (i32, [vp, C.POINTER(C.c_char_p), i32, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_subsample": (i32, [vp, C.c_char_p, C.c_float, C.c_uint64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_recalc_tlen": (i32, [vp, C.c_char_p, i64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_recalc_tlen_discarded": (i32, [vp, i64, i64, vp]),
         "sk_bam_file_coverage": (i32, [vp, C.c_char_p, i32, vp, i64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
@@ -530,6 +532,17 @@ class Context:
         """sk_bam_file_subsample: (handled, records written, records counted, inflated output bytes, info f64[8]); then
         bam_file_rewrite_windows() yields the windows."""
         return self._bam_out_call("sk_bam_file_subsample", path, (fraction, seed, level, window_bytes), with_duplicates=True)
+
+    def bam_file_recalc_tlen(self, path: str, max_len: int = 5000, level: int = 1, window_bytes: int = 0):
+        """sk_bam_file_recalc_tlen: (handled, records written, records discarded, inflated output bytes, info f64[8]); then
+        bam_file_rewrite_windows() yields the windows and bam_file_recalc_tlen_discarded() the discarded records' names."""
+        return self._bam_out_call("sk_bam_file_recalc_tlen", path, (max_len, level, window_bytes), with_duplicates=True)
+
+    def bam_file_recalc_tlen_discarded(self, first: int, n: int):
+        """sk_bam_file_recalc_tlen_discarded: the names (bytes) of discarded records first .. first + n - 1, in file order."""
+        slots = np.zeros(max(n, 0) * 256, dtype=np.uint8)
+        self._check(self._lib.sk_bam_file_recalc_tlen_discarded(self._h, first, n, slots.ctypes.data if n > 0 else None), "sk_bam_file_recalc_tlen_discarded")
+        return [bytes(slots[k * 256:(k + 1) * 256]).split(b"\0", 1)[0] for k in range(n)]
 
     def bam_file_merge(self, paths, suffix: bool = False, level: int = 1, window_bytes: int = 0):
         """sk_bam_file_merge: (handled, records, inflated output bytes, info f64[8]); then bam_file_rewrite_windows() yields the windows."""

@@ -16,7 +16,7 @@
 // region test (S2: it does not depend on record order), and whatever is irregular falls back to the reader
 // here before anything has been written.  `sam to` takes the file the same way: the device writes every record's text, window by
 // window, and the mate pairing stays here.  The commands that write BAM to stdout (trim qnames, tags from qname, qname from tags, minimize,
-// mark duplicates, subsample, merge) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
+// mark duplicates, subsample, recalculate tlen, merge) share one way through: the gate (device_path), the windows' members to stdout (bam_out_from_file), and for what the
 // device does not take the reader and writer of HostBamRewrite around the command's own per-record loop.  `sam coverage histogram` goes
 // through the same gate with sk_bam_file_coverage and prints 10 001 lines; its host reader states the rule in one sort and one sweep.
 #include <unistd.h>
@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <deque>
 #include <memory>
 #include <new>
 #include <string>
@@ -1175,7 +1176,7 @@ static bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl)
 }
 
 // The device path of a BAM-writing command: `start` makes the file call that sets the windows up (sk_bam_file_rewrite, _minimize,
-// _markdup, _subsample or _merge), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
+// _markdup, _subsample, _recalc_tlen or _merge), and the members go to stdout as they arrive.  -1: nothing has been written, and the caller's reader serves the file (one
 // the file path does not take, a device without room, or a record the reference would stop at).  Otherwise the number of records.
 template <class Start>
 static int64_t bam_out_from_file(Start start)
@@ -1646,6 +1647,122 @@ static int subsample_cmd(int argc, char **argv)
 	return 0;
 }
 
+// ---- sam recalculate tlen ----------------------------------------------------------------------------------------------
+// src/sam_recalculate_tlen.rs: TLEN becomes the distance between the mates' 5' ends; a candidate whose mate never comes is dropped with
+// a line on stderr.  A regular file goes to the device whole (sk_bam_file_recalc_tlen: classes, the mates linked by a sort of the names'
+// hashes, the pairs' TLENs, the written records compacted, then the rewrite windows; the dropped records' names afterwards); stdin,
+// SEQKIT_HOST_INFLATE=1 and every file the device declines — a record the reference stops at, a name or a CIGAR it might stop at, an
+// invalid record, or two names with one hash — go through the reference's own loop below: a FIFO of reads and a map from a name to the
+// place of the read that waits for its mate.
+static const char *USAGE_RECALCULATE_TLEN =
+	"\nUsage:\n  sam recalculate tlen [options] <bam_file>\n\nOptions:\n"
+	"  --uncompressed    Output in uncompressed BAM format\n"
+	"  --max-len=N       Maximum fragment length [default: 5000]\n\n"
+	"Recalculates SAM record TLEN (template length) field based on the distance\nbetween the 5' ends of paired mates. This ensures that the TLEN represents the \n"
+	"actual DNA fragment length.\n";
+
+static void discarded_line(const uint8_t *name, size_t n)                    // :103
+{
+	fputs("Read ", stderr);
+	fwrite(name, 1, n, stderr);
+	fputs(" discarded due to missing mate.\n", stderr);
+}
+
+static int recalculate_tlen_cmd(int argc, char **argv)
+{
+	std::vector<host::Opt> opts = {{"--uncompressed", false, false, ""}, {"--max-len", true, false, "5000"}};
+	std::vector<std::string> pos;
+	if (!host::parse_args(argc, argv, 3, opts, pos, 1) || pos.size() != 1) error("Invalid arguments.\n%s", USAGE_RECALCULATE_TLEN);
+	const std::string path = expand_home(pos[0]);
+	int64_t max_len = 0;
+	if (!parse_i64(opts[1].value, max_len)) max_len = 0;                         // :29 parse().unwrap_or(0)
+	if (max_len <= 0) error("--max-len must be a positive integer.");            // :30
+	const int level = opts[0].present ? 0 : 1;
+	host::gpu_warmup();
+	int64_t n_disc = 0;
+	if (device_path("sam recalculate tlen", path, [&] { return bam_out_from_file([&](sk_ctx *ctx, uint64_t window, int64_t *n, uint64_t *raw, int *handled) {
+		    return sk_bam_file_recalc_tlen(ctx, path.c_str(), max_len, level, window, n, &n_disc, raw, handled, nullptr); }); }) >= 0) {
+		std::vector<uint8_t> names;
+		for (int64_t first = 0; first < n_disc;) {
+			const int64_t step = std::min<int64_t>(n_disc - first, 4096);
+			names.resize((size_t)step * 256);
+			check(sk_bam_file_recalc_tlen_discarded(host::gpu(), first, step, names.data()), "sk_bam_file_recalc_tlen_discarded");
+			for (int64_t k = 0; k < step; k++) discarded_line(names.data() + k * 256, strlen(reinterpret_cast<const char *>(names.data() + k * 256)));
+			first += step;
+		}
+		return 0;
+	}
+	HostBamRewrite io(path, level);
+	BamStream &bam = io.bam;
+	BamOut &out = io.out;
+	struct TlenRead { bool ready; int32_t tlen; std::vector<uint8_t> rec; };   // :20-24 (rec: block_size, core and variable part)
+	std::deque<TlenRead> reads;                                                  // :38-40
+	std::unordered_map<std::string, size_t> mates;
+	size_t reads_written = 0;
+	auto write = [&](TlenRead &r) {                                             // :90-92 set_insert_size, write
+		for (int k = 0; k < 4; k++) r.rec[32 + k] = (uint8_t)((uint32_t)r.tlen >> (8 * k));
+		out.put(r.rec.data(), r.rec.size());
+	};
+	// the 5' end of a queued or current record (:60-61); cigar() panics at an operation code above 8
+	auto start_of = [](const std::vector<uint8_t> &rec) {
+		const int64_t p = (int32_t)le32(rec.data() + 8);
+		if (!(rec[18] & 0x10)) return p;
+		bool bad_op = false;
+		const int64_t e = cigar_end_pos(rec.data() + 36 + rec[12], le32(rec.data() + 16) & 0xffff, p, &bad_op);
+		if (bad_op) panic("Unexpected cigar operation");
+		return e - 1;
+	};
+	BamCore c;
+	BamStream::Var v;
+	std::vector<uint8_t> body;
+	std::string name;
+	while (bam.next_full(c, v, body)) {
+		const size_t L = v.l_read_name - 1;
+		if (!host::utf8_valid(body.data(), L)) panic("called `Result::unwrap()` on an `Err` value: Utf8Error");   // :43
+		TlenRead rd{true, 0, {}};
+		rd.rec.assign(bam.head, bam.head + 36);
+		rd.rec.insert(rd.rec.end(), body.begin(), body.end());
+		const uint16_t f = c.flag;
+		if (!(f & 0x1) || (f & 0x4) || (f & 0x8)) reads.push_back(std::move(rd));                        // :44-47
+		else if (f & 0x900) error("Secondary and supplementary read alignments are not supported.");   // :48-49
+		else if (c.tid != c.mtid || std::llabs((long long)c.pos - (long long)c.mpos) > max_len || !(f & 0x10) == !(f & 0x20))
+			reads.push_back(std::move(rd));                                                            // :50-54
+		else {
+			name.assign(reinterpret_cast<const char *>(body.data()), L);
+			auto it = mates.find(name);
+			if (it != mates.end()) {                                            // :57-79
+				TlenRead &mate = reads[it->second - reads_written];
+				mates.erase(it);
+				if (!((f ^ mate.rec[18]) & 0x40)) panic("assertion failed: read.is_first_in_template() != mate.is_first_in_template()");
+				const int64_t start_pos = start_of(rd.rec), mate_start_pos = start_of(mate.rec);
+				int64_t tlen = std::llabs((long long)(start_pos - mate_start_pos)) + 1;
+				if (c.pos > (int32_t)le32(mate.rec.data() + 8)) tlen = -tlen;
+				if ((start_pos < mate_start_pos && (f & 0x10)) || (start_pos > mate_start_pos && !(f & 0x10))) tlen = 0;
+				rd.tlen = (int32_t)(uint32_t)(uint64_t)tlen;                    // `as i32`: the low 32 bits
+				mate.tlen = (int32_t)(uint32_t)(uint64_t)(-tlen);
+				mate.ready = true;
+				reads.push_back(std::move(rd));
+			} else {
+				mates.emplace(name, reads_written + reads.size());
+				rd.ready = false;
+				reads.push_back(std::move(rd));
+			}
+		}
+		while (!reads.empty() && reads.front().ready) {                         // :89-95
+			write(reads.front());
+			reads.pop_front();
+			reads_written++;
+		}
+	}
+	bam.raise_deferred();                                                       // (before the reads still queued would be written)
+	for (TlenRead &r : reads) {                                                 // :101-111
+		if (!r.ready) { discarded_line(r.rec.data() + 36, (size_t)r.rec[12] - 1); continue; }
+		write(r);
+	}
+	io.close();
+	return 0;
+}
+
 // ---- sam merge -----------------------------------------------------------------------------------------------------------
 // src/sam_merge.rs: the inputs' records by (u32 refID, i32 pos), each input's own order kept.  The reference's heap leaves the order of
 // records of DIFFERENT inputs with one key to its internals; here they go by the input's place on the command line, so
@@ -2029,6 +2146,7 @@ int main(int argc, char **argv)
 	else if (argc >= 2 && is(1, "minimize")) rc = minimize_cmd(argc, argv);
 	else if (argc >= 3 && is(1, "mark") && is(2, "duplicates")) rc = mark_duplicates_cmd(argc, argv);
 	else if (argc >= 2 && is(1, "subsample")) rc = subsample_cmd(argc, argv);
+	else if (argc >= 3 && is(1, "recalculate") && is(2, "tlen")) rc = recalculate_tlen_cmd(argc, argv);
 	else if (argc >= 2 && is(1, "merge")) rc = merge_cmd(argc, argv);
 	else if (argc >= 3 && is(1, "coverage") && is(2, "histogram")) rc = coverage_histogram_cmd(argc, argv);
 	else fprintf(stderr, "%s\n", USAGE_TOP);

@@ -192,6 +192,12 @@ struct RewriteState : WindowedState {
 	void *d_blocks = nullptr;
 	hipEvent_t ev_copy[2] = {nullptr, nullptr};     // the copy of packed buffer b on the second stream
 	uint64_t raw[2] = {0, 0};
+	// sk_bam_file_recalc_tlen_discarded: the discarded records' stream offsets in file order and a staging area of kTlenNameSlots name
+	// slots (device, the kept head of ctx slot kKeepPassWork), of the file call disc_gen (0: none)
+	static constexpr uint64_t kTlenNameSlots = 4096;
+	uint64_t disc_gen = 0, n_disc = 0;
+	const uint64_t *disc = nullptr;
+	uint8_t *d_names = nullptr;
 	~RewriteState() { for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
 };
 

@@ -1,5 +1,5 @@
-// sk_bamfile_out.cpp — the BAM-writing file calls (include/seqkit_hip.h: sk_bam_file_rewrite, _minimize, _markdup, _subsample, _merge and
-// sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
+// sk_bamfile_out.cpp — the BAM-writing file calls (include/seqkit_hip.h: sk_bam_file_rewrite, _minimize, _markdup, _subsample, _recalc_tlen,
+// _merge and sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -381,6 +381,118 @@ extern "C" int sk_bam_file_subsample(sk_ctx *c, const char *path, float fraction
 	const int rc = rw_begin(c, cl, fr, o, sk::launch_bam_copy_write, level, window_bytes, counts[1], counts[2], n_records, raw_bytes, handled, info);
 	if (rc == SK_OK && *handled && n_total) *n_total = (int64_t)counts[0];
 	return rc;
+}
+
+// ---- sam recalculate tlen (include/seqkit_hip.h: sk_bam_file_recalc_tlen, _discarded; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then the passes of sk_bamtlen.hip around sk_bamminimize.hip's sort and run pass, which link the mates, and
+// sk_bamsubsample.hip's scans and compaction, which leave the WRITTEN records' stream and output offsets where sk_bam_file_rewrite
+// leaves every record's.  The working memory is sk_bam_file_subsample's, 32 B per record and the scratch of the sort and the scans, placed
+// as there: behind the sort the idle key buffer holds src and the record lengths, the idle index buffer the TLENs in file order, the
+// sorted indices' buffer the places and the sorted keys' buffer the output offsets.  What the windows and
+// sk_bam_file_recalc_tlen_discarded read is kept in ctx slot kKeepPassWork: one region of 8 B per record with the written records'
+// TLENs (4 B each) from its start and the discarded records' stream offsets (8 B each) up to its end — every record is one or the
+// other — and the name slots of one chunk of discarded records.  Declined files: the list in include/seqkit_hip.h.
+extern "C" int sk_bam_file_recalc_tlen(sk_ctx *c, const char *path, int64_t max_len, int level, uint64_t window_bytes, int64_t *n_records,
+                                       int64_t *n_discarded, uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_recalc_tlen", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (n_discarded) *n_discarded = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (max_len <= 0) return sk::ctx_fail(c, SK_ERR_INVALID, "max_len = %lld", (long long)max_len);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const int64_t nb = fr.nb;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 32)) BF_LEAVE(21);
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 0, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const int n_cu = sk::ctx_n_cu(c);
+	int bits = 63;                                                      // (a test knob: fewer bits make hash collisions reachable; bit `bits` marks a record that is no candidate)
+	if (const char *ev = getenv("SK_TLEN_KEY_BITS")) { const int v = atoi(ev); if (v >= 1 && v <= 63) bits = v; }
+	passmem::SortBufs sb;
+	BF_HIP(pass_temp(sb, N ? N : 1, bits + 1, st, [&](size_t *b) { return sk::bam_sub_scans(nullptr, b, nullptr, nullptr, nullptr, N ? N : 1, st); }));
+	uint64_t *krec = nullptr;
+	uint32_t *agg = nullptr;
+	passmem::Layout L;
+	L.add(sb.key, N * 8); L.add(krec, N * 8); L.add(sb.idx, N * 4); L.add(agg, (N / 1024 + 2) * 4); L.add(sb.temp, sb.temp_bytes);
+	const size_t a_kept = up(N * 8 + 8);
+	const passmem::Placement pl = passmem::place(a_kept + (size_t)std::min<uint64_t>(N, RewriteState::kTlenNameSlots) * 256, L.total(), fr.fsize + 64,
+	                                             getenv("SK_TLEN_OWN_MEMORY") != nullptr);             // (the knob: for tests of the other placement)
+	uint8_t *own = nullptr;
+	if (!pass_memory(c, pl, own)) BF_LEAVE(21);
+	pl.trace(fr.who, "", "the compressed file's buffer");
+	L.carve(pl.scratch_at(own, fr.d_comp));
+	int32_t *tlen_out = (int32_t *)own;
+	uint64_t written = 0, total = 0;
+	if (N) {
+		// ---- classes and keys: the passes below read the names, flags and CIGARs of valid records only
+		BF_HIP(sk::launch_bam_tlen_keys(fr.d_out, fr.d_bend, fr.d_entry, nb, o.d_rb, max_len, bits, krec, sb.key[0], sb.idx[0], o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 a record the reference stops at, 8 an invalid record, 16 a name byte >= 0x80)
+		// ---- the mates' link, the pairs' TLENs: the file is served or left here
+		int cur = 0;
+		size_t tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sort_pairs(sb.temp, &tb, sb.key, sb.idx, N, bits + 1, &cur, st));
+		uint32_t *src = (uint32_t *)sb.key[cur ^ 1], *cnt = src + N;
+		BF_HIP(sk::launch_bam_min_ids(fr.d_out, krec, sb.key[cur], sb.idx[cur], N, bits, sk::kTlenIdRule, agg, src, cnt, sb.idx[cur ^ 1], o.d_decline, st));
+		uint32_t *len = cnt, *pos = sb.idx[cur];                          // (the opener counts, the ids and the sorted pairs are idle from here on)
+		int32_t *tlen = (int32_t *)sb.idx[cur ^ 1];
+		uint64_t *off = sb.key[cur];
+		BF_HIP(sk::launch_bam_tlen_resolve(fr.d_out, krec, src, N, tlen, len, o.d_decline, n_cu, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (2 mates with equal 0x40 bits, 32 a CIGAR operation code above 8, 64 two names with one hash)
+		// ---- the written records' stream and output offsets and TLENs, the discarded records' stream offsets
+		tb = sb.temp_bytes;
+		BF_HIP(sk::bam_sub_scans(sb.temp, &tb, len, pos, off, N, st));
+		uint32_t last[2] = {0, 0};                                       // the last record: its place, its length
+		BF_HIP(hipMemcpyAsync(&last[0], pos + (N - 1), 4, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipMemcpyAsync(&last[1], len + (N - 1), 4, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipMemcpyAsync(&total, off + (N - 1), 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+		written = (uint64_t)last[0] + (last[1] ? 1 : 0);
+		total += last[1];
+		BF_HIP(sk::launch_bam_sub_compact(krec, len, pos, off, N, o.s->krec, o.s->kout, st));
+		BF_HIP(sk::launch_bam_tlen_gather(krec, len, pos, tlen, N, tlen_out, (uint64_t *)(own + N * 8) - (N - written), n_cu, st));
+	}
+	const WindowWriter write = [tlen_out](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_tlen_write(w, tlen_out, n_cu, s); };
+	const int rc = rw_begin(c, cl, fr, o, write, level, window_bytes, written, total, n_records, raw_bytes, handled, info);
+	if (rc == SK_OK && *handled) {
+		RewriteState &s = *o.s;
+		s.disc_gen = s.gen; s.n_disc = N - written;
+		s.disc = (const uint64_t *)(own + N * 8) - s.n_disc;
+		s.d_names = own + a_kept;
+		if (n_discarded) *n_discarded = (int64_t)s.n_disc;
+	}
+	return rc;
+}
+
+extern "C" int sk_bam_file_recalc_tlen_discarded(sk_ctx *c, int64_t first, int64_t n, uint8_t *names)
+{
+	if (!c) return SK_ERR_INVALID;
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	if (!R || !R->rw.current(R->gen) || R->rw.disc_gen != R->gen)
+		return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_recalc_tlen_discarded: no sk_bam_file_recalc_tlen to ask");
+	const RewriteState &s = R->rw;
+	if (first < 0 || n < 0 || (uint64_t)first > s.n_disc || (uint64_t)n > s.n_disc - (uint64_t)first)
+		return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_recalc_tlen_discarded: records %lld .. +%lld of %llu", (long long)first, (long long)n, (unsigned long long)s.n_disc);
+	if (n == 0) return SK_OK;
+	if (!names) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_recalc_tlen_discarded: names is NULL");
+	if (int r = sk::ctx_bind(c)) return r;
+	hipStream_t st = sk::ctx_stream(c);
+	for (int64_t done = 0; done < n;) {                                   // (a chunk of slots at a time through the staging area)
+		const int64_t step = std::min<int64_t>(n - done, (int64_t)RewriteState::kTlenNameSlots);
+		BF_HIP(sk::launch_bam_tlen_names(s.d_out, s.disc, first + done, step, s.d_names, sk::ctx_n_cu(c), st));
+		BF_HIP(hipMemcpyAsync(names + done * 256, s.d_names, (size_t)step * 256, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+		done += step;
+	}
+	return SK_OK;
 }
 
 // ---- sam merge (include/seqkit_hip.h: sk_bam_file_merge; the windows come from sk_bam_file_rewrite_next) ---

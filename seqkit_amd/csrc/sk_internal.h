@@ -290,6 +290,25 @@ hipError_t bam_sub_scans(void *temp, size_t *temp_bytes, const uint32_t *len, ui
 hipError_t launch_bam_sub_compact(const uint64_t *krec, const uint32_t *len, const uint32_t *pos, const uint64_t *off, uint64_t n, uint64_t *kept_rec,
                                   uint64_t *kept_out, hipStream_t st);
 hipError_t launch_bam_copy_write(const WriteWindow &w, int n_cu, hipStream_t st);
+// ---- sam recalculate tlen: the record passes of sk_bam_file_recalc_tlen (sk_bamtlen.hip) ----
+// The rule its key columns are written under, for bam_sort_pairs and launch_bam_min_ids: the whole name is the key, and there are records
+// that take no part, so key_bits is at most 63 (which ones the key kernel here decides by the record's class; the two read of
+// skip_flags only that it is not 0).
+constexpr IdRule kTlenIdRule{1, ~0u};
+// keys: as launch_bam_min_keys, a candidate's key the hash of its name and every other record's the skip bit; decline bits 1 (a record
+// the reference stops at), 8 (an invalid record), 16 (a name byte >= 0x80).  resolve: from src (launch_bam_min_ids) tlen[k] for every
+// record that is written and len[k] = its bytes, 0 for a candidate without a mate; decline bits 2 (mates with equal 0x40 bits) and 32 (a
+// CIGAR operation code above 8 on a reverse candidate).  gather (pos: bam_sub_scans over len): the written records' TLENs in written
+// order and the discarded records' stream offsets in file order.  write: as launch_bam_copy_write, bytes 32-35 of every record from
+// tlen.  names: discarded records first .. first + n - 1 into n slots of 256 bytes, each the name and NULs behind it.
+hipError_t launch_bam_tlen_keys(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, int64_t max_len,
+                                int key_bits, uint64_t *krec, uint64_t *key, uint32_t *idx, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_tlen_resolve(const uint8_t *stream, const uint64_t *krec, const uint32_t *src, uint64_t n, int32_t *tlen, uint32_t *len,
+                                   uint32_t *decline, int n_cu, hipStream_t st);
+hipError_t launch_bam_tlen_gather(const uint64_t *krec, const uint32_t *len, const uint32_t *pos, const int32_t *tlen, uint64_t n, int32_t *tlen_out,
+                                  uint64_t *disc, int n_cu, hipStream_t st);
+hipError_t launch_bam_tlen_write(const WriteWindow &w, const int32_t *tlen, int n_cu, hipStream_t st);
+hipError_t launch_bam_tlen_names(const uint8_t *stream, const uint64_t *disc, int64_t first, int64_t n, uint8_t *out, int n_cu, hipStream_t st);
 // ---- sam merge: the record passes of sk_bam_file_merge (sk_bammerge.hip) ----
 // The per-record columns in input order (input 1's records first, then input 2's ..): the record's address as an offset from input 1's
 // stream mod 2^64, its key (u32 refID) << 32 | (u32 pos ^ 0x80000000), its index, its output bytes and its input number (1-based).

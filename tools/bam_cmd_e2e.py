@@ -16,7 +16,14 @@ PATH, for a profiler run of the command] [--merge: only the `sam merge` rows, se
 and the parts to DIR (in.bam, p2_0.bam .., p8_0.bam ..), for a profiler run of the command] [--pairing: only the `sam to` pairing rows,
 see below] [--pairing-file=PATH: only write that row's file to PATH, for a profiler run of the command] [--on-target: only the `sam
 statistics --on-target` rows, see below] [--on-target-files=DIR: only write that row's file and BED to DIR (in.bam, t.bed), for a profiler
-run of the command]
+run of the command] [--recalc-tlen: only the `sam recalculate tlen` rows, see below] [--use-file=PATH: with --recalc-tlen, the file
+--markdup-file wrote to PATH instead of a new one; it is left there]
+
+--recalc-tlen: the mark duplicates file (position-sorted; every record a candidate, the mates adjacent: every pair is found, nothing is
+discarded, and every TLEN is rewritten).  Rows, all to /dev/null: `sam trim qnames` on the device path (--yardstick-sam: another
+build's, the parent commit's) — it reads and writes the same bytes —, `sam recalculate tlen` on the device path and, twice, through the
+host reader.  The ratio recalculate tlen / trim qnames is printed run for run next to the spread (max - min) of the trim qnames
+repeats.  With --check the device path and the host reader also write a file each, and the inflated outputs and stderr are compared.
 
 --on-target: the subsample file (position-sorted, 200 references) and a BED of 4 000 regions over its references, a fifth of them short
 ones under a long one.  Rows, all to /dev/null: `sam count --single-end <file> <bed>` on the device path (--yardstick-sam: another
@@ -95,6 +102,8 @@ pairing = "--pairing" in sys.argv
 pairing_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--pairing-file=")), None)
 on_target = "--on-target" in sys.argv
 on_target_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--on-target-files=")), None)
+recalc_tlen = "--recalc-tlen" in sys.argv
+use_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--use-file=")), None)
 merge_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--merge-files=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -116,7 +125,7 @@ def bgzf(data, level=1):
 
 unit = bytearray()
 starts, ends = [], []
-dup_mode = markdup or markdup_file is not None
+dup_mode = markdup or markdup_file is not None or recalc_tlen
 tl_prev, umi_prev = 0, b""
 for i in range(PAIRS):
     tl = int(rng.lognormal(np.log(170), 0.35))
@@ -384,6 +393,55 @@ def subsample_rows():
     os.rmdir(d)
 
 
+def recalc_tlen_rows():
+    global bam
+    t0 = time.perf_counter()
+    if use_file:
+        bam = use_file
+    else:
+        write_count_file(bam)
+    print(f"recalculate tlen file: {n} BAM records on {reps} references, sorted, every record a candidate, mates adjacent, {os.path.getsize(bam) / 1e6:.0f} MB, "
+          + ("as given" if use_file else f"written in {time.perf_counter() - t0:.1f} s") + f"; {runs} runs per device row, alternating, 2 through the host reader", flush=True)
+    trim_sam = yardstick_sam or SAM
+    trim_label = "sam trim qnames        device" + (" (yardstick build)" if yardstick_sam else "")
+    rows = {}
+    for k in range(runs):
+        for label, cmd, env in ((trim_label, [trim_sam, "trim", "qnames", bam], None),
+                                ("sam recalculate tlen   device", [SAM, "recalculate", "tlen", bam], None),
+                                ("sam recalculate tlen   host  ", [SAM, "recalculate", "tlen", bam], {"SEQKIT_HOST_INFLATE": "1"})):
+            if env and k >= 2:
+                continue
+            dt, cpu, rc, _, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+            lines = err.decode(errors="replace").split("\n")
+            served = [ln for ln in lines if ln.startswith("sam ")]
+            assert rc == 0 and served and ("host reader" if env else "device path") in served[0], (label, rc, err[-400:])
+            rows.setdefault(label, []).append((dt, cpu, [ln for ln in lines if ln.startswith("sk_bam_file_recalc_tlen:")]))
+    for label, r in rows.items():
+        w, c = [x[0] for x in r], [x[1] for x in r]
+        print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r)
+              + f"  (wall {min(w):.2f}-{max(w):.2f} s, CPU {min(c):.1f}-{max(c):.1f} s)", flush=True)
+    for ln in rows["sam recalculate tlen   device"][-1][2]:
+        print("  " + ln, flush=True)
+    rt = [x[0] for x in rows["sam recalculate tlen   device"]]
+    tq = [x[0] for x in rows[trim_label]]
+    host = [x[0] for x in rows["sam recalculate tlen   host  "]]
+    print("recalculate tlen / trim qnames, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(rt, tq))
+          + f"; medians {float(np.median(rt)) / float(np.median(tq)):.2f}x; median difference {float(np.median(rt)) - float(np.median(tq)):+.2f} s against trim qnames' "
+          f"max - min {max(tq) - min(tq):.2f} s = {(max(tq) - min(tq)) / float(np.median(tq)):.2f} of its median; device / host reader (medians) = "
+          f"{float(np.median(rt)) / float(np.median(host)):.2f}", flush=True)
+    if markdup_check:
+        got = []
+        for env in (None, {"SEQKIT_HOST_INFLATE": "1"}):
+            dt, cpu, rc, _, err = timed([SAM, "recalculate", "tlen", bam], env, sink=out)
+            got.append((rc, inflated_digest(out), err))
+        assert got[0] == got[1], got
+        print(f"sam recalculate tlen > file: inflated outputs and stderr identical on both paths ({got[0][1]})", flush=True)
+        os.remove(out)
+    if not use_file:
+        os.remove(bam)
+    os.rmdir(d)
+
+
 def write_part_files(dirname, parts):
     """the count file's records dealt alternately into `parts` files: record j of every repeat goes to part j mod parts; the paths"""
     u = np.frombuffer(unit, dtype=np.uint8)
@@ -606,6 +664,9 @@ if markdup_file is not None or subsample_file is not None:
     sys.exit(0)
 if markdup:
     markdup_rows()
+    sys.exit(0)
+if recalc_tlen:
+    recalc_tlen_rows()
     sys.exit(0)
 if subsample:
     subsample_rows()
