@@ -60,10 +60,13 @@ def header(text, refs):
     return raw
 
 
-def bgzf(raw, piece=0xFF00, level=6):
+def bgzf(raw, piece=0xFF00, level=6, cuts=None):
+    """cuts: the stream offsets at which the blocks end (ascending, the last one len(raw)), instead of blocks of `piece` bytes"""
     out = []
-    for o in range(0, len(raw), piece):
-        data = raw[o:o + piece]
+    bounds = zip([0] + list(cuts[:-1]), cuts) if cuts is not None else ((o, o + piece) for o in range(0, len(raw), piece))
+    assert cuts is None or int(cuts[-1]) == len(raw)
+    for lo, hi in bounds:
+        data = raw[int(lo):int(hi)]
         c = zlib.compressobj(level, zlib.DEFLATED, -15)
         comp = c.compress(data) + c.flush()
         out.append(struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(comp) + 25) + comp
@@ -76,11 +79,11 @@ REFS = [(b"chr1", 248956422), (b"chr2", 242193529), (b"chrM", 16569)]
 TEXT = b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % r for r in REFS) + b"@PG\tID:x\n\n\n" + b"\0" * 7
 
 
-def write(path, recs, text=TEXT, refs=REFS, piece=0xFF00, level=6):
-    """piece: the inflated bytes of a BGZF block; level: zlib's (1 writes a large file cheaply, 0 stores)"""
+def write(path, recs, text=TEXT, refs=REFS, piece=0xFF00, level=6, cuts=None):
+    """piece: the inflated bytes of a BGZF block (cuts: where the blocks end instead); level: zlib's (1 writes a large file cheaply, 0 stores)"""
     raw = header(text, refs) + b"".join(recs)
     with open(path, "wb") as f:
-        f.write(bgzf(raw, piece, level))
+        f.write(bgzf(raw, piece, level, cuts))
     return raw
 
 

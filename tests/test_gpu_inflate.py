@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import bam_spec
+from tests.bam_decoy import plain_entries
 from tests.cli_util import write_bam
 
 pytestmark = pytest.mark.gpu
@@ -287,15 +288,7 @@ def test_bam_walk_and_reduce(ctx, oracle, mode):
     ends = cut_blocks(raw, first, rng, mode)
     n = len(ends)
     # the entries a plain walk finds: for every block the first record that begins at or behind its beginning
-    starts = []
-    o = first
-    while o < len(raw):
-        starts.append(o)
-        o += 4 + struct.unpack_from("<I", raw, o)[0]
-    assert o == len(raw)
-    starts = np.array(starts + [len(raw)], dtype=np.uint64)
-    begins = np.concatenate([[0], ends[:-1]]).astype(np.uint64)
-    want_entry = starts[np.searchsorted(starts, np.maximum(begins, first))]
+    want_entry = np.array(plain_entries(raw, first, ends), dtype=np.uint64)
     d = Dev(ctx)
     try:
         d_stream = d.put(np.frombuffer(raw, dtype=np.uint8))
