@@ -77,11 +77,12 @@ def build_hosts(force: bool = False) -> list[str]:
     os.makedirs(BINDIR, exist_ok=True)
     out = []
     for name, srcs, libs in (("fasta", ["host_common.cpp", "host_inflate.cpp", "fasta_main.cpp", "fasta_text.cpp"], ["-lz", "-ldl"]),
-                             ("sam", ["host_common.cpp", "host_inflate.cpp", "sam_main.cpp"], ["-lz", "-ldl"])):
+                             ("sam", ["host_common.cpp", "host_inflate.cpp", "sam_main.cpp", "sam_bamio.cpp", "sam_columns.cpp", "sam_reads.cpp",
+                                      "sam_bamout.cpp", "sam_coverage.cpp"], ["-lz", "-ldl"])):
         if not all(os.path.exists(os.path.join(CSRC, s)) for s in srcs):
             continue
         target = os.path.join(BINDIR, name)
-        deps = srcs + ["host_common.h", "sam_pairing.h", "sk_bamfmt.h", os.path.join(REPO, "include", "seqkit_hip.h"), LIB_PATH]
+        deps = srcs + ["host_common.h", "sam_host.h", "sam_pairing.h", "sk_bamfmt.h", os.path.join(REPO, "include", "seqkit_hip.h"), LIB_PATH]
         if force or _stale(target, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I", os.path.join(REPO, "include"),
                    "-o", target] + srcs + ["-L", LIBDIR, "-lseqkit_hip", "-Wl,-rpath,$ORIGIN/../lib"] + libs

@@ -515,12 +515,8 @@ static void bgzf_append_block(std::string &out, const char *in, size_t n)
 		crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), reinterpret_cast<const Bytef *>(in), (uInt)n);
 	}
 	const size_t bsize = 18 + clen + 8;                         // < 65536: kBgzfInput leaves room for incompressible data
-	static const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
-	memcpy(blk, head, 16);
-	blk[16] = (uint8_t)((bsize - 1) & 0xff);
-	blk[17] = (uint8_t)((bsize - 1) >> 8);
-	uint8_t *t = blk + 18 + clen;
-	for (int k = 0; k < 4; k++) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
+	bamfmt::bgzf_head(blk, bsize);
+	bamfmt::bgzf_trailer(blk + 18 + clen, crc, (uint32_t)n);
 	out.resize(at + bsize);
 }
 

@@ -1,4 +1,4 @@
-// sam_pairing.h — what `sam to` (sam_main.cpp) does with the windows of the two file calls that serve it, apart from the device and the
+// sam_pairing.h — what `sam to` (sam_reads.cpp) does with the windows of the two file calls that serve it, apart from the device and the
 // sinks, so that a stand-alone program can run it (tests/cpp/pairing_test.cpp): the loop over the windows of sk_bam_file_pairs, whose
 // texts arrive paired and in output order, and the pairing of src/sam_to_fastq.rs:113-137 on the host over the windows of
 // sk_bam_file_reads, whose texts arrive in file order.  `next(&w)` fills the next window (w.n == 0: the end); `write(stream, p, n)`

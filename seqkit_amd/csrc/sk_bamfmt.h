@@ -1,4 +1,4 @@
-// sk_bamfmt.h — BAM and BGZF format bits that the library (sk_bamfile*.cpp) and the hosts (sam_main.cpp, host_common.cpp) read or write.
+// sk_bamfmt.h — BAM and BGZF format bits that the library (sk_bamfile*.cpp) and the hosts (sam_*.cpp, host_common.cpp) read or write.
 // Plain C++: the hosts are built with g++.
 #pragma once
 #include <stddef.h>
@@ -15,6 +15,34 @@ inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1]
 
 // the BGZF end-of-file marker: an empty member (SAMv1 §4.1.2)
 constexpr uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// A BGZF member (SAMv1 §4.1): the gzip head whose 'BC' extra field carries BSIZE - 1 at 16..17, a DEFLATE payload from 18 on, then
+// CRC32 and ISIZE of the bytes it inflates to.  Which payload a member gets is its writer's decision, and so is the CRC's computation.
+constexpr uint8_t kBgzfHead[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+
+// the 18 bytes of head of a member of bsize bytes in all (head, payload and trailer: at most 65536)
+inline void bgzf_head(uint8_t *m, size_t bsize)
+{
+	memcpy(m, kBgzfHead, 16);
+	m[16] = (uint8_t)((bsize - 1) & 0xff);
+	m[17] = (uint8_t)((bsize - 1) >> 8);
+}
+
+// a payload of one stored block (BFINAL = 1, BTYPE = 00; LEN, ~LEN, the bytes) at p; its length, len + 5
+inline size_t bgzf_stored(uint8_t *p, const uint8_t *src, uint32_t len)
+{
+	p[0] = 1;
+	p[1] = (uint8_t)(len & 0xff); p[2] = (uint8_t)(len >> 8);
+	p[3] = (uint8_t)(~len & 0xff); p[4] = (uint8_t)((~len >> 8) & 0xff);
+	memcpy(p + 5, src, len);
+	return (size_t)len + 5;
+}
+
+// the 8 bytes behind the payload
+inline void bgzf_trailer(uint8_t *t, uint32_t crc, uint32_t isize)
+{
+	for (int k = 0; k < 4; k++) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)(isize >> (8 * k)); }
+}
 
 // Header::from_template + Writer (htslib sam_hdr_write): the text up to its first NUL, trailing '\n's stripped and one appended when
 // anything is left; the reference list as read (htslib would rebuild it from the @SQ lines: DESIGN.md §10).  h: "BAM\1" .. the end of

@@ -18,6 +18,7 @@
 #include "../../include/seqkit_hip.h"
 #include "sk_internal.h"
 #include "sk_hoststage.h"
+#include "sk_bamfmt.h"
 
 struct sk_ctx {
 	int device = 0;
@@ -1491,7 +1492,6 @@ int sk_bgzf_deflate(sk_ctx *c, const uint8_t *in, size_t in_bytes, const sk_defl
 	SK_HIP(c, hipMemcpyAsync(crc.data(), d_crc, n * 4, hipMemcpyDeviceToHost, c->stream));
 	SK_HIP(c, hipMemcpyAsync(pin, d_slots, b_slots, hipMemcpyDeviceToHost, c->stream));
 	SK_HIP(c, hipStreamSynchronize(c->stream));
-	static const uint8_t head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
 	size_t at = 0;
 	for (size_t i = 0; i < n; i++) {
 		const uint32_t len = blocks[i].in_len, pay = res[2 * i];
@@ -1500,19 +1500,10 @@ int sk_bgzf_deflate(sk_ctx *c, const uint8_t *in, size_t in_bytes, const sk_defl
 		const size_t bsize = 18 + clen + 8;
 		if (at + bsize > out_cap) return fail(c, SK_ERR_INVALID, "out_cap = %zu is too small (block %zu ends at %zu)", out_cap, i, at + bsize);
 		uint8_t *m = out + at;
-		memcpy(m, head, 16);
-		m[16] = (uint8_t)((bsize - 1) & 0xff);
-		m[17] = (uint8_t)((bsize - 1) >> 8);
-		if (stored) {
-			m[18] = 1;                                                    // BFINAL = 1, BTYPE = 00
-			m[19] = (uint8_t)(len & 0xff); m[20] = (uint8_t)(len >> 8);
-			m[21] = (uint8_t)(~len & 0xff); m[22] = (uint8_t)((~len >> 8) & 0xff);
-			memcpy(m + 23, in + blocks[i].in_off, len);
-		} else {
-			memcpy(m + 18, pin + i * (size_t)SK_DEFLATE_SLOT, pay);
-		}
-		uint8_t *t = m + 18 + clen;
-		for (int k = 0; k < 4; k++) { t[k] = (uint8_t)(crc[i] >> (8 * k)); t[4 + k] = (uint8_t)(len >> (8 * k)); }
+		bamfmt::bgzf_head(m, bsize);
+		if (stored) bamfmt::bgzf_stored(m + 18, in + blocks[i].in_off, len);
+		else memcpy(m + 18, pin + i * (size_t)SK_DEFLATE_SLOT, pay);
+		bamfmt::bgzf_trailer(m + 18 + clen, crc[i], len);
 		at += bsize;
 		out_off[i + 1] = at;
 	}

@@ -1342,7 +1342,7 @@ __global__ __launch_bounds__(256) void bam_walk_reduce_kernel(const WalkArgs a, 
 // The fixed-core fields of every record of a verified chain, in file order, into SoA columns (sk_bam_file_columns).  A wave per
 // BGZF block: lane 0 follows the chain from entry[c] to the block's end and leaves every record's offset in LDS (sk_bamblock.h:
 // block_record_offsets), then the 64 lanes take consecutive records and store each column coalesced.  rec_base[c] = index of block c's first record (exclusive prefix of the walk's counts).
-// end_pos is BamStream::next(..., want_end)'s (sam_main.cpp): pos plus the lengths of the ops M D N = X (0 2 3 7 8), summed in
+// end_pos is BamStream::next(..., want_end)'s (sam_bamio.cpp): pos plus the lengths of the ops M D N = X (0 2 3 7 8), summed in
 // 64 bits and truncated; pos itself when the variable part is shorter than the read name and the CIGAR.
 struct GatherCols {
 	uint16_t *flag;

@@ -1,5 +1,5 @@
 """A third, independent decode of BAM for the parity tests — written from the SAM/BAM specification (SAMv1 §4.1 BGZF,
-§4.2 BAM), NOT from this repo's readers (seqkit_amd/csrc/sam_main.cpp, oracle/sam_oracle_main.c) and not from the
+§4.2 BAM), NOT from this repo's readers (seqkit_amd/csrc/sam_bamio.cpp, oracle/sam_oracle_main.c) and not from the
 tests' own writer: a shared misreading of the format in those three would pass their mutual comparisons; it would not
 pass this one.  Plain Python: struct + zlib.
 

@@ -1,5 +1,5 @@
 """B1 (src/common.rs:121-157, htslib in the reference): the BAM decode of BOTH command-line readers — the product's
-(seqkit_amd/csrc/sam_main.cpp) and the oracle's (oracle/sam_oracle_main.c) — against a third decode written from the
+(seqkit_amd/csrc/sam_bamio.cpp) and the oracle's (oracle/sam_oracle_main.c) — against a third decode written from the
 SAM/BAM specification alone (tests/bam_spec.py), on the BAM files the CLI tests write and on a BGZF file whose blocks
 carry an extra gzip subfield (legal per RFC 1952, never produced by the tests' own writer)."""
 import os
