@@ -1,4 +1,4 @@
-// sk_hoststage.h — what a host-pointer entry point (sk_capi.hip) stages through the ctx's workspace: the call's columns, each stated
+// sk_hoststage.h — what a host-pointer entry point (sk_capi_*.cpp; sk_ctx.h: ChunkPipe) stages through the ctx's workspace: the call's columns, each stated
 // once with its bytes per row, its direction and the caller's pointer.  From that one list: the rows of a chunk, the bytes of a
 // workspace half, where every column's region lies in it, and what is copied in before the launch and out behind it.  Plain C++,
 // nothing of the device: tests/cpp/hoststage_test.cpp carves heap memory with it.

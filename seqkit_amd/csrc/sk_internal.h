@@ -1,4 +1,4 @@
-// sk_internal.h — shared between the C-ABI layer (sk_capi.hip) and the gfx950 kernels (sk_kernels.hip).
+// sk_internal.h — shared between the C-ABI layer (sk_capi_*.cpp, sk_capi_comm.hip) and the gfx950 kernels (sk_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -409,7 +409,7 @@ constexpr int kMaxCensusLen = 31;
 
 }  // namespace sk
 
-// ---- what the file calls (sk_bamfile*.cpp) need of a ctx (sk_capi.hip owns the struct) ----
+// ---- what the file calls (sk_bamfile*.cpp) need of a ctx (sk_ctx.h holds the struct, for the units of the C-ABI layer alone; sk_capi_ctx.cpp defines these) ----
 struct sk_ctx;
 namespace sk {
 // The buffers that stay with a ctx from call to call (ctx_keep).  The file calls' front half (sk_bamfile.cpp: bam_file_front) keeps the

@@ -3,7 +3,7 @@
 // layout and what grid, and the slots and workgroup cap of the mate pass.  Pure arithmetic on plain facts (Knobs: the SK_* tuning
 // variables as read; Shape: the call): no HIP, no heap, no getenv — it runs on every launch of the command-line hosts' small batches.
 // sk_kernels.hip reads the environment, builds the Shape, asks here, maps the kernel id to a function and makes the occupancy query;
-// sk_capi.hip asks the same functions what a call needs.  tests/cpp/tileplan_test.cpp holds every rule to expectations written out
+// sk_capi_fused.cpp asks the same functions what a call needs.  tests/cpp/tileplan_test.cpp holds every rule to expectations written out
 // by hand, on the CPU.
 #pragma once
 #include <stdint.h>

@@ -1,6 +1,6 @@
-// hoststage_test.cpp — sk_hoststage.h (what the host-pointer entry points of sk_capi.hip stage through the ctx's workspace) on the host,
+// hoststage_test.cpp — sk_hoststage.h (what the host-pointer entry points of sk_capi_*.cpp stage through the ctx's workspace) on the host,
 // built with the address and undefined-behaviour sanitizers (tests/test_hoststage_cpu.py).  The column lists of the entry points are
-// restated here as sk_capi.hip gives them, in every mode that changes the list; the chunk rules and the bytes of a half are written
+// restated here as sk_capi_*.cpp give them, in every mode that changes the list; the chunk rules and the bytes of a half are written
 // out a second time as the plain arithmetic the entry points did by hand before the header existed.
 #include <stdint.h>
 #include <stdio.h>
