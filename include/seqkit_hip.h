@@ -466,7 +466,7 @@ int sk_bam_file_pairs_next(sk_ctx *ctx, sk_bam_pairs_window *w);
  * last window ending with the 28-byte BGZF EOF block; n == 0 && bytes == 0 at the end.  Concatenated, the windows' bytes are the
  * output file.  The HOST bytes (the ctx's, page-locked) hold until the next call on the ctx; the device rewrites and compresses the
  * following window while the caller writes this one.  Calling it after another sk_bam_file_* call, or without
- * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample, sk_bam_file_recalc_tlen or sk_bam_file_merge, below, whose windows it hands out too):
+ * sk_bam_file_rewrite (or sk_bam_file_minimize, sk_bam_file_markdup, sk_bam_file_subsample, sk_bam_file_recalc_tlen, sk_bam_file_merge or sk_bam_file_concatenate, below, whose windows it hands out too; the last of them decides by its flags whether there is a header window and an EOF block):
  * SK_ERR_INVALID.                                                                                                                 */
 #define SK_REWRITE_TRIM_QNAMES     1
 #define SK_REWRITE_QNAME_FROM_TAGS 2
@@ -598,6 +598,26 @@ int sk_bam_file_recalc_tlen_discarded(sk_ctx *ctx, int64_t first, int64_t n, uin
  * as sk_bam_file_rewrite.                                                                                                         */
 int sk_bam_file_merge(sk_ctx *ctx, const char *const *paths, int n_paths, int suffix, int level /* 0 stored, 1 deflate */,
                       uint64_t window_bytes /* 0 = default */, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
+
+/* ---- BAM out for `sam concatenate` (src/sam_concatenate.rs:35-49) ------------------------------------------------------------
+ * sk_bam_file_concatenate: ONE input of the command — sk_bam_file_rewrite's front half and window pipeline over the file at path, every
+ * record in file order with '.' and the decimal digits of number (1 .. 4294967295: 2 .. 11 bytes) appended to its name, l_read_name and
+ * block_size grown by those bytes, every other byte as it was (refID and next refID too: nothing is remapped).  The caller chains the
+ * inputs, one call each with number = 1, 2, ..; the ctx holds one input's streams at a time.  flags: with SK_CONCAT_HEADER the windows
+ * begin with this file's output header (sk_bam_file_rewrite's rule) in members of its own, without it no header window is issued; with
+ * SK_CONCAT_EOF the last window ends with the 28-byte BGZF EOF block, without it none does.  An input without records and with
+ * flags == 0 has no window at all (the first sk_bam_file_rewrite_next returns the end); with SK_CONCAT_EOF alone it has one window of
+ * n == 0, bytes == 28.  *n_records: the file's records; *raw_bytes: what this call's members inflate to (the header when asked for, and
+ * the records).  The windows come from sk_bam_file_rewrite_next under its rules.  *handled = 0 leaves the file to the caller's reader,
+ * nothing written: info[5] = -(30 + bits) with bit 1 a suffixed name of more than 254 bytes (the reference panics there), 8 a record
+ * whose variable part is shorter than its fields; info[5] = -21: the working memory cannot be had (16 B per record for the offsets and
+ * the scan's scratch where that does not fit into the device buffer of the compressed file, idle by then); any other negative info[5]:
+ * the check at which the front half left the file.  number == 0, flags outside 0 .. 3 or a bad level: SK_ERR_INVALID.  level,
+ * window_bytes: as sk_bam_file_rewrite.                                                                                            */
+#define SK_CONCAT_HEADER 1   /* the windows begin with this file's output header in members of its own */
+#define SK_CONCAT_EOF    2   /* the last window ends with the 28-byte BGZF EOF block */
+int sk_bam_file_concatenate(sk_ctx *ctx, const char *path, uint32_t number, int flags, int level /* 0 stored, 1 deflate */,
+                            uint64_t window_bytes /* 0 = default */, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
 
 /* ---- `sam coverage histogram` (src/sam_coverage_histogram.rs; this build's reading of `samtools depth -a`) --------
  * sk_bam_file_coverage: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0

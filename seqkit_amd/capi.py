@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_concatenate", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_on_target_set_regions", "sk_on_target_add", "sk_on_target_add_dev", "sk_on_target_get",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
@@ -94,6 +94,7 @@ class _OutWindow(C.Structure):
 REWRITE_OP = {"trim qnames": 1, "qname from tags": 2, "tags from qname": 3}
 # sk_bam_file_minimize: the flags
 MINIMIZE_READ_IDS, MINIMIZE_BASE_QUALITIES, MINIMIZE_TAGS = 1, 2, 4
+CONCAT_HEADER, CONCAT_EOF = 1, 2     # SK_CONCAT_*
 COVERAGE_BINS = 10001                # SK_COVERAGE_BINS
 
 
@@ -254,6 +255,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_file_markdup": (i32, [vp, C.c_char_p, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_subsample_keep": (i32, [C.c_uint64, C.c_uint64, C.c_float]),
         "sk_bam_file_merge": (i32, [vp, C.POINTER(C.c_char_p), i32, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_concatenate": (i32, [vp, C.c_char_p, C.c_uint32, i32, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_subsample": (i32, [vp, C.c_char_p, C.c_float, C.c_uint64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_recalc_tlen": (i32, [vp, C.c_char_p, i64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_recalc_tlen_discarded": (i32, [vp, i64, i64, vp]),
@@ -553,6 +555,11 @@ class Context:
                                                 C.byref(handled), info), "sk_bam_file_merge")
         return bool(handled.value), int(n_rec.value), int(raw_bytes.value), [float(x) for x in info]
 
+    def bam_file_concatenate(self, path: str, number: int, flags: int = 3, level: int = 1, window_bytes: int = 0):
+        """sk_bam_file_concatenate, one input of `sam concatenate`: (handled, records, inflated bytes of this call's members, info f64[8]);
+        then bam_file_rewrite_windows() yields the windows.  flags: CONCAT_HEADER | CONCAT_EOF."""
+        return self._bam_out_call("sk_bam_file_concatenate", path, (number, flags, level, window_bytes))
+
     def bam_file_coverage(self, path: str, mode: int = 0, targets=()):
         """sk_bam_file_coverage: (handled, hist u64[COVERAGE_BINS], target positions, positions deeper than the last bin, counted records,
         info f64[8]).  mode 0 everywhere, 1 region, 2 BED; targets: (refID, beg, end) triples, 0-based half-open."""
@@ -565,7 +572,7 @@ class Context:
         return bool(handled.value), hist, int(n_pos.value), int(n_drop.value), int(n_counted.value), [float(x) for x in info]
 
     def bam_file_rewrite_windows(self):
-        """sk_bam_file_rewrite_next (after bam_file_rewrite, bam_file_minimize, bam_file_markdup, bam_file_subsample or bam_file_merge) until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""
+        """sk_bam_file_rewrite_next (after bam_file_rewrite, bam_file_minimize, bam_file_markdup, bam_file_subsample, bam_file_merge or bam_file_concatenate) until the end: one dict per window (first, n, bgzf: a bytes copy of its members, raw_bytes)."""
         while True:
             w = _OutWindow()
             self._check(self._lib.sk_bam_file_rewrite_next(self._h, C.byref(w)), "sk_bam_file_rewrite_next")

@@ -308,10 +308,15 @@ void BamOut::deflate_here(const std::vector<sk_deflate_block> &blocks, std::vect
 static BamOut *g_bam_out = nullptr;
 static void finish_bam_out() { if (g_bam_out) g_bam_out->finish(); }    // a panic unwinds through the Writer's drop: what was written stays valid BAM
 
+void finish_at_exit(BamOut *out)
+{
+	g_bam_out = out;
+	host::at_exit_flush(finish_bam_out);
+}
+
 void HostBamRewrite::start()
 {
-	g_bam_out = &out;
-	host::at_exit_flush(finish_bam_out);
+	finish_at_exit(&out);
 	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
 	out.put(hdr.data(), hdr.size());
 	out.flush();

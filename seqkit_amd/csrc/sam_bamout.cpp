@@ -1,5 +1,6 @@
 // sam_bamout.cpp — the `sam` commands that write BAM to stdout: trim qnames, tags from qname, qname from tags, minimize, mark duplicates,
-// subsample, recalculate tlen, merge.  They share one way through: device_path, bam_out_from_file and HostBamRewrite (sam_host.h).
+// subsample, recalculate tlen, merge, concatenate.  They share one way through: device_path, bam_out_from_file and HostBamRewrite
+// (sam_host.h); concatenate, whose inputs each choose their way, states its own at its end.
 #include <sys/random.h>
 
 #include <deque>
@@ -640,5 +641,86 @@ int merge_cmd(int argc, char **argv)
 		}
 	}
 	io.close();
+	return 0;
+}
+
+// ---- sam concatenate -----------------------------------------------------------------------------------------------------
+// src/sam_concatenate.rs: the inputs one after the other in command-line order, ".1", ".2", .. behind every read name, under the FIRST
+// input's header; the later inputs' headers are read and skipped, not compared.  The inputs are taken one at a time, and each chooses
+// its own way: a regular file is offered to the device (sk_bam_file_concatenate, which serves ONE input of a longer output: the header
+// only with input 1, the EOF block only with the last); "-", SEQKIT_HOST_INFLATE=1 and every input the device declines — an invalid
+// record, a suffixed name above 254 bytes — are read record by record here, that input alone, and the next one is offered to the device
+// again.  The order on stdout is this command's business: what the host writer holds is flushed before a device-served input's members
+// are written.  From the first byte of output on, every way out through error() or panic() finishes the stream with the EOF block.
+static const char *USAGE_CONCATENATE =
+	"\nUsage:\n  sam concatenate [options] <bam_files>...\n\nOptions:\n"
+	"  --uncompressed    Output in uncompressed BAM format\n\n"
+	"Concatenates two or more BAM files together, ensuring that read\nidentifiers do not clash. Currently we simply add a '.1' suffix to all\n"
+	"read identifiers found in the first BAM file, a '.2' suffix to all all\nread identifiers found in the second BAM file, and so forth.\n";
+
+int concatenate_cmd(int argc, char **argv)
+{
+	std::vector<host::Opt> opts = {{"--uncompressed", false, false, ""}};
+	std::vector<std::string> pos;
+	if (!host::parse_args(argc, argv, 2, opts, pos, (size_t)-1) || pos.empty()) error("Invalid arguments.\n%s", USAGE_CONCATENATE);
+	if (pos.size() < 2) error("At least two BAM files must be provided for concatenation.");      // :24-26
+	const int level = opts[0].present ? 0 : 1;
+	std::vector<std::string> paths;
+	for (const std::string &p : pos) paths.push_back(expand_home(p));
+	host::gpu_warmup();
+	BamOut out(level);
+	bool eof_written = false;
+	BamCore c;
+	BamStream::Var v;
+	std::vector<uint8_t> body, rec;
+	const std::vector<uint8_t> none;
+	std::string name;
+	for (size_t b = 0; b < paths.size(); b++) {
+		const std::string &path = paths[b];
+		const bool first = b == 0, last = b + 1 == paths.size();
+		int64_t n_dev = -1;
+		if (file_path_wanted(path)) {
+			sk_ctx *ctx = host::gpu();
+			int64_t n_rec = 0;
+			uint64_t raw = 0;
+			int handled = 0;
+			const int flags = (first ? SK_CONCAT_HEADER : 0) | (last ? SK_CONCAT_EOF : 0);
+			if (sk_bam_file_concatenate(ctx, path.c_str(), (uint32_t)(b + 1), flags, level, file_window_bytes(), &n_rec, &raw, &handled, nullptr) == SK_OK && handled) {
+				out.flush();                                                    // (what a host-read input before this one left: a short last member is fine)
+				finish_at_exit(&out);
+				sk_bam_out_window w;
+				for (;;) {
+					check(sk_bam_file_rewrite_next(ctx, &w), "sk_bam_file_rewrite_next");
+					if (w.n == 0 && w.bytes == 0) break;
+					BamOut::write_all(w.bgzf, (size_t)w.bytes);
+				}
+				n_dev = n_rec;
+				if (last) { eof_written = true; finish_at_exit(nullptr); }
+			}
+		}
+		if (bamfile_trace()) {
+			if (n_dev >= 0) fprintf(stderr, "sam concatenate: input %zu: device path, %lld records\n", b + 1, (long long)n_dev);
+			else fprintf(stderr, "sam concatenate: input %zu: host reader\n", b + 1);
+		}
+		if (n_dev >= 0) continue;
+		BamStream bam(path, first);                                             // :28, :37 (a file that cannot be opened ends the command here)
+		if (first) {
+			const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
+			out.put(hdr.data(), hdr.size());
+			out.flush();                                                        // (the header goes in members of its own)
+		}
+		finish_at_exit(&out);
+		const std::string suffix = "." + std::to_string(b + 1);                 // :41
+		while (bam.next_full(c, v, body)) {                                     // :43-48
+			name.assign(reinterpret_cast<const char *>(body.data()), v.l_read_name - 1);
+			name += suffix;
+			if (name.size() > 254) panic("assertion failed: new_qname.len() < 255");
+			renamed_record(rec, bam.head, name, body.data() + v.l_read_name, body.size() - v.l_read_name, none);
+			out.put(rec.data(), rec.size());
+		}
+		bam.raise_deferred();
+	}
+	if (!eof_written) out.finish();
+	finish_at_exit(nullptr);
 	return 0;
 }

@@ -148,6 +148,9 @@ private:
 	std::vector<uint8_t> buf_, comp_;
 };
 
+// From here on error() and panic() finish `out` (what is left and the EOF block) before the process ends; nullptr: no longer.
+void finish_at_exit(BamOut *out);
+
 // The first RX field's value when its type is Z or H (bam_aux_get: the walk stops, not finding it, where the aux data stop parsing)
 bool find_rx(const uint8_t *a, size_t n, const uint8_t *&val, size_t &vl);
 
@@ -204,4 +207,5 @@ int mark_duplicates_cmd(int argc, char **argv);
 int subsample_cmd(int argc, char **argv);
 int recalculate_tlen_cmd(int argc, char **argv);
 int merge_cmd(int argc, char **argv);
+int concatenate_cmd(int argc, char **argv);
 int coverage_histogram_cmd(int argc, char **argv);

@@ -37,6 +37,13 @@ __device__ __forceinline__ uint32_t bam_le32_bytes(const uint8_t *p)
 	return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
+// is the record one htslib reads (sk_bamwrite.hip: rw_plan's bit 8): the decline rule of the merge and concatenate passes
+__device__ __forceinline__ bool bam_record_valid(const uint8_t *r)
+{
+	const uint32_t bs = bam_le32_bytes(r), lo = r[12], nc = bam_le32_bytes(r + 16) & 0xffffu, S = bam_le32_bytes(r + 20);
+	return !(bs < 32u || lo < 1u || S > 0x7fffffffu || 4ull * nc + lo + (((unsigned long long)S + 1) >> 1) + S > (unsigned long long)(bs - 32u));
+}
+
 // lane 0's walk: the offsets (from entry) of the records that begin in [entry, end) into off[], at most kBlockRecs; returns their count
 __device__ __forceinline__ uint32_t block_record_offsets(const uint8_t *stream, unsigned long long entry, unsigned long long end, uint16_t *off)
 {

@@ -184,8 +184,9 @@ struct RewriteState : WindowedState {
 	int level = 1;
 	uint64_t *krec = nullptr, *kout = nullptr;
 	std::vector<uint64_t> wo;
-	std::vector<uint8_t> header;                 // the output header (the first window)
+	std::vector<uint8_t> header;                 // the output header (the first window); empty: the call writes none (sk_bam_file_concatenate)
 	bool header_done = false;
+	bool eof_due = true;                         // the 28-byte EOF block is still to come (false from the start: the call writes none)
 	uint8_t *d_raw = nullptr, *d_slots = nullptr, *d_pack[2] = {nullptr, nullptr}, *h_pin[2] = {nullptr, nullptr};
 	uint32_t *d_tokens = nullptr, *d_result = nullptr, *d_crc = nullptr;
 	uint64_t *d_msz = nullptr, *h_size = nullptr;   // h_size[b]: window b's packed bytes (page-locked)

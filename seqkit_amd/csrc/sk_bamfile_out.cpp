@@ -1,5 +1,5 @@
 // sk_bamfile_out.cpp — the BAM-writing file calls (include/seqkit_hip.h: sk_bam_file_rewrite, _minimize, _markdup, _subsample, _recalc_tlen,
-// _merge and sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
+// _merge, _concatenate and sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -90,9 +90,10 @@ static int rw_open(sk_ctx *c, Cleanup &cl, const Front &fr, int blk_cols, RwOpen
 
 // What they share once the stream and output offsets (s.krec, s.kout) of the N records that go out are there — every record of the file,
 // or for sk_bam_file_subsample the kept ones —: the window plan, the window area, and the header's members on their way.  `write`:
-// what writes a window; `total`: the records' output bytes.
+// what writes a window; `total`: the records' output bytes; `ends`: SK_CONCAT_HEADER | SK_CONCAT_EOF, both for every call but
+// sk_bam_file_concatenate.
 static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WindowWriter &write, int level, uint64_t window_bytes, uint64_t N,
-                    uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8])
+                    uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8], int ends = SK_CONCAT_HEADER | SK_CONCAT_EOF)
 {
 	RewriteState &s = *o.s;
 	int krc = SK_OK;
@@ -101,7 +102,8 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, co
 	bool room = true;
 	if (int r = plan_windows(c, cl, window_bytes, s.kout, nullptr, N, total, 0, s, s.wo, nullptr, mx, &room)) return r;
 	if (!room) BF_LEAVE(21);
-	s.header = bamfmt::rewrite_header(fr.header);
+	s.header.clear();
+	if (ends & SK_CONCAT_HEADER) s.header = bamfmt::rewrite_header(fr.header);
 	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
 	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
 	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
@@ -123,7 +125,8 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, co
 	for (int b = 0; b < 2; b++)
 		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
 	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
-	s.write = write; s.level = level; s.header_done = false;
+	s.write = write; s.level = level;
+	s.header_done = !(ends & SK_CONCAT_HEADER); s.eof_due = (ends & SK_CONCAT_EOF) != 0;
 	s.begin(fr.d_out, ((Ranges *)sk::ctx_ext(c))->gen);
 	int rc = SK_OK;
 	if (rw_issue(c, s, 0, &rc)) s.cur = 0;
@@ -608,6 +611,56 @@ extern "C" int sk_bam_file_merge(sk_ctx *c, const char *const *paths, int n_path
 	return rw_begin(c, cl, all, o, write, level, window_bytes, N, total, n_records, raw_bytes, handled, info);
 }
 
+// ---- sam concatenate (include/seqkit_hip.h: sk_bam_file_concatenate; the windows come from sk_bam_file_rewrite_next) ---
+// ONE input of the command: the front half, then sk_bamconcat.hip's sizing pass, which leaves every record's stream offset and output
+// length (its own and the suffix's) in the two columns of ctx slot kKeepFileCols, and sk_bammerge.hip's scan over them.  No key, no
+// sort, no gather, nothing kept for the windows but the number itself; the scan's scratch lies in the compressed file's device
+// buffer, idle by then, or where that is too small in ctx slot kKeepPassWork.  The header and the EOF block are the caller's to ask
+// for (flags): the ctx holds one input's streams at a time, and the caller chains the inputs.
+extern "C" int sk_bam_file_concatenate(sk_ctx *c, const char *path, uint32_t number, int flags, int level, uint64_t window_bytes, int64_t *n_records,
+                                       uint64_t *raw_bytes, int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_concatenate", handled, info, cl, fr, [&] {
+		    if (n_records) *n_records = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (number == 0) return sk::ctx_fail(c, SK_ERR_INVALID, "number = 0");
+		    if (flags & ~(SK_CONCAT_HEADER | SK_CONCAT_EOF)) return sk::ctx_fail(c, SK_ERR_INVALID, "flags = %d", flags);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const uint64_t N = fr.n_records;
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 0, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	uint32_t sl = 2;                                                    // '.' and the digits
+	for (uint32_t v = number; v >= 10u; v /= 10u) sl++;
+	uint64_t total = 0;
+	if (N) {
+		void *temp = nullptr;
+		size_t tb = 0;
+		BF_HIP(sk::bam_merge_scan(nullptr, &tb, nullptr, N, st));
+		passmem::Layout L;
+		L.add(temp, tb);
+		const passmem::Placement pl = passmem::place(0, L.total(), fr.fsize + 64, false);
+		uint8_t *own = nullptr;
+		if (!pass_memory(c, pl, own)) BF_LEAVE(21);
+		L.carve(pl.scratch_at(own, fr.d_comp));
+		// ---- sizes and checks: the input is served or left here
+		BF_HIP(sk::launch_bam_concat_size(fr.d_out, fr.d_bend, fr.d_entry, fr.nb, o.d_rb, sl, o.s->krec, o.s->kout, o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 a suffixed name above 254 bytes, 8 an invalid record)
+		BF_HIP(sk::bam_merge_scan(temp, &tb, o.s->kout, N, st));
+		BF_HIP(hipMemcpyAsync(&total, o.s->kout + N, 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	const WindowWriter write = [number, sl](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_concat_write(w, number, sl, n_cu, s); };
+	return rw_begin(c, cl, fr, o, write, level, window_bytes, N, total, n_records, raw_bytes, handled, info, flags);
+}
+
 extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
 {
 	if (!c || !w) return SK_ERR_INVALID;
@@ -617,7 +670,14 @@ extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
 	if (int r = sk::ctx_bind(c)) return r;
 	RewriteState &s = R->rw;
 	const int b = s.cur;
-	if (b < 0) return SK_OK;                                            // the end
+	if (b < 0) {                                                        // the end
+		if (s.eof_due) {                                                // (no window carried the EOF block: a call without header and records)
+			s.eof_due = false;
+			memcpy(s.h_pin[0], bamfmt::kBgzfEof, 28);
+			w->bgzf = s.h_pin[0]; w->bytes = 28;
+		}
+		return SK_OK;
+	}
 	BF_HIP(hipEventSynchronize(s.ev[b]));
 	uint64_t bytes = s.h_size[b];
 	int rc = SK_OK;
@@ -627,7 +687,7 @@ extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
 	if (bytes) BF_HIP(hipMemcpyAsync(s.h_pin[b], s.d_pack[b], (size_t)bytes, hipMemcpyDeviceToHost, st2));
 	BF_HIP(hipEventRecord(s.ev_copy[b], st2));
 	BF_HIP(hipEventSynchronize(s.ev_copy[b]));
-	if (s.cur < 0) { memcpy(s.h_pin[b] + bytes, bamfmt::kBgzfEof, 28); bytes += 28; }   // the last window ends with the EOF block
+	if (s.cur < 0 && s.eof_due) { s.eof_due = false; memcpy(s.h_pin[b] + bytes, bamfmt::kBgzfEof, 28); bytes += 28; }   // the last window ends with the EOF block
 	w->first = s.first[b]; w->n = s.n[b];
 	w->bgzf = s.h_pin[b]; w->bytes = bytes; w->raw_bytes = s.raw[b];
 	return SK_OK;

@@ -37,13 +37,6 @@ typedef unsigned long long u64;
 
 constexpr int kMergeThreads = 256;
 
-// is the record one htslib reads (sk_bamwrite.hip: rw_plan's bit 8)
-__device__ __forceinline__ bool merge_valid(const uint8_t *r)
-{
-	const u32 bs = bam_le32_bytes(r), lo = r[12], nc = bam_le32_bytes(r + 16) & 0xffffu, S = bam_le32_bytes(r + 20);
-	return !(bs < 32u || lo < 1u || S > 0x7fffffffu || 4ull * nc + lo + (((u64)S + 1) >> 1) + S > (u64)(bs - 32u));
-}
-
 __global__ __launch_bounds__(kBlockThreads) void bam_merge_key_kernel(const uint8_t *stream, const u64 *bend, const u64 *entry_of, int64_t nb, const u64 *rb,
                                                                          u64 delta, u32 input, u32 sl, const MergeCols m, uint32_t *decline)
 {
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(kBlockThreads) void bam_merge_key_kernel(const uint
 	for (u32 j = (u32)lane; j < n; j += 64u) {
 		const uint8_t *r = stream + entry + off[j];
 		const u64 k = k0 + j;
-		if (!merge_valid(r)) dec |= 8u;
+		if (!bam_record_valid(r)) dec |= 8u;
 		else if (sl && (u32)r[12] - 1u + sl > 254u) dec |= 1u;
 		m.addr[k] = delta + entry + off[j];
 		m.key[k] = ((u64)bam_le32_bytes(r + 4) << 32) | (u64)(bam_le32_bytes(r + 8) ^ 0x80000000u);

@@ -328,6 +328,13 @@ hipError_t launch_bam_merge_order(const MergeCols &cols, uint64_t n, uint32_t *d
 hipError_t launch_bam_merge_gather(const uint32_t *idx, const MergeCols &cols, uint64_t n, uint64_t *krec, uint64_t *kout, uint8_t *kin, hipStream_t st);
 hipError_t bam_merge_scan(void *temp, size_t *temp_bytes, uint64_t *kout, uint64_t n, hipStream_t st);
 hipError_t launch_bam_merge_write(const WriteWindow &w, const uint8_t *kin, int n_cu, hipStream_t st);
+// ---- sam concatenate: the record passes of sk_bam_file_concatenate (sk_bamconcat.hip) ----
+// size: every record's stream offset (krec) and output bytes block_size + 4 + suffix_len (kout; bam_merge_scan then makes offsets of
+// them), rb: the blocks' first records; decline bits 8 (an invalid record) and 1 (a suffixed name above 254 bytes).  write: as
+// launch_bam_copy_write, '.' and the decimal digits of number — suffix_len bytes, 2 .. 11 — behind every record's name.
+hipError_t launch_bam_concat_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, uint32_t suffix_len,
+                                  uint64_t *krec, uint64_t *kout, uint32_t *decline, hipStream_t st);
+hipError_t launch_bam_concat_write(const WriteWindow &w, uint32_t number, uint32_t suffix_len, int n_cu, hipStream_t st);
 // ---- sam to: the mate pairing of sk_bam_file_pairs and its windows' text (sk_bampair.hip) ----
 // Over the K kept records of launch_bam_reads_index (file order; kind 0 unpaired, 1 first, 2 last mate).  A record's fate: where its text
 // goes; aux: for a record of a pair the kept index of the record that COMPLETED the pair, for a leftover its order record.  Its class: what

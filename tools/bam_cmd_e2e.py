@@ -17,7 +17,15 @@ and the parts to DIR (in.bam, p2_0.bam .., p8_0.bam ..), for a profiler run of t
 see below] [--pairing-file=PATH: only write that row's file to PATH, for a profiler run of the command] [--on-target: only the `sam
 statistics --on-target` rows, see below] [--on-target-files=DIR: only write that row's file and BED to DIR (in.bam, t.bed), for a profiler
 run of the command] [--recalc-tlen: only the `sam recalculate tlen` rows, see below] [--use-file=PATH: with --recalc-tlen, the file
---markdup-file wrote to PATH instead of a new one; it is left there]
+--markdup-file wrote to PATH instead of a new one; it is left there] [--concatenate: only the `sam concatenate` rows, see below]
+[--concatenate-files=DIR: only write those rows' two files to DIR (a.bam, b.bam), for a profiler run of the command]
+
+--concatenate: the mark duplicates file cut in two: the first half of its repeats and the second, each position-sorted, under one
+header.  Rows, all to /dev/null: `sam merge --suffix a b` on the device path (--yardstick-sam: another build's, the parent commit's) —
+it writes the same records under the same names, and keys, sorts and gathers them besides —, `sam concatenate a b` on the device
+path and, twice, through the host reader.  The ratio concatenate / merge --suffix is printed run for run and by the medians next to the
+spread (max - min) of the merge repeats.  With --check the device path and the host reader also write a file each, and the inflated
+outputs are compared with each other and with merge --suffix's (the halves do not interleave: the two commands write the same stream).
 
 --recalc-tlen: the mark duplicates file (position-sorted; every record a candidate, the mates adjacent: every pair is found, nothing is
 discarded, and every TLEN is rewritten).  Rows, all to /dev/null: `sam trim qnames` on the device path (--yardstick-sam: another
@@ -103,6 +111,8 @@ pairing_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("-
 on_target = "--on-target" in sys.argv
 on_target_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--on-target-files=")), None)
 recalc_tlen = "--recalc-tlen" in sys.argv
+concatenate = "--concatenate" in sys.argv
+concatenate_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--concatenate-files=")), None)
 use_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--use-file=")), None)
 merge_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--merge-files=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
@@ -125,7 +135,7 @@ def bgzf(data, level=1):
 
 unit = bytearray()
 starts, ends = [], []
-dup_mode = markdup or markdup_file is not None or recalc_tlen
+dup_mode = markdup or markdup_file is not None or recalc_tlen or concatenate or concatenate_files is not None
 tl_prev, umi_prev = 0, b""
 for i in range(PAIRS):
     tl = int(rng.lognormal(np.log(170), 0.35))
@@ -442,6 +452,66 @@ def recalc_tlen_rows():
     os.rmdir(d)
 
 
+def write_half_files(dirname):
+    """the mark duplicates file cut in two: the first half of its repeats in a.bam, the second in b.bam; the paths"""
+    halves = [os.path.join(dirname, "a.bam"), os.path.join(dirname, "b.bam")]
+    for path, tids in zip(halves, (range(0, reps // 2), range(reps // 2, reps))):
+        with open(path, "wb") as f:
+            f.write(header(reps))
+            with ThreadPoolExecutor(16) as ex:
+                for blob in ex.map(with_tid, tids):
+                    f.write(blob)
+            f.write(bgzf(b""))
+    return halves
+
+
+def concatenate_rows():
+    t0 = time.perf_counter()
+    halves = write_half_files(d)
+    print(f"concatenate files: the mark duplicates file of {n} BAM records on {reps} references cut in two, each half sorted ("
+          + ", ".join(f"{os.path.getsize(p) / 1e6:.0f}" for p in halves) + f" MB), written in {time.perf_counter() - t0:.1f} s; {runs} runs per device row, "
+          "alternating, 2 through the host reader", flush=True)
+    merge_sam = yardstick_sam or SAM
+    merge_label = "sam merge --suffix  device" + (" (yardstick build)" if yardstick_sam else "")
+    rows = {}
+    for k in range(runs):
+        for label, cmd, env in ((merge_label, [merge_sam, "merge", "--suffix"] + halves, None),
+                                ("sam concatenate     device", [SAM, "concatenate"] + halves, None),
+                                ("sam concatenate     host  ", [SAM, "concatenate"] + halves, {"SEQKIT_HOST_INFLATE": "1"})):
+            if env and k >= 2:
+                continue
+            dt, cpu, rc, _, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+            lines = err.decode(errors="replace").split("\n")
+            served = [ln for ln in lines if ln.startswith("sam ")]
+            assert rc == 0 and served and all(("host reader" if env else "device path") in ln for ln in served), (label, rc, err[-400:])
+            rows.setdefault(label, []).append((dt, cpu, [ln for ln in lines if ln.startswith("sk_bam_file_concatenate:")]))
+    for label, r in rows.items():
+        w, c = [x[0] for x in r], [x[1] for x in r]
+        print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r)
+              + f"  (wall median {float(np.median(w)):.2f} s, {min(w):.2f}-{max(w):.2f} s, CPU {min(c):.1f}-{max(c):.1f} s)", flush=True)
+    for ln in rows["sam concatenate     device"][-1][2]:
+        print("  " + ln, flush=True)
+    cc = [x[0] for x in rows["sam concatenate     device"]]
+    mg = [x[0] for x in rows[merge_label]]
+    host = [x[0] for x in rows["sam concatenate     host  "]]
+    print("concatenate / merge --suffix, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(cc, mg))
+          + f"; medians {float(np.median(cc)) / float(np.median(mg)):.2f}x; median difference {float(np.median(cc)) - float(np.median(mg)):+.2f} s against merge's "
+          f"max - min {max(mg) - min(mg):.2f} s = {(max(mg) - min(mg)) / float(np.median(mg)):.2f} of its median; device / host reader (medians) = "
+          f"{float(np.median(cc)) / float(np.median(host)):.2f}", flush=True)
+    if markdup_check:
+        got = []
+        for cmd, env in (([merge_sam, "merge", "--suffix"] + halves, None), ([SAM, "concatenate"] + halves, None),
+                         ([SAM, "concatenate"] + halves, {"SEQKIT_HOST_INFLATE": "1"})):
+            dt, cpu, rc, _, err = timed(cmd, env, sink=out)
+            got.append((rc, inflated_digest(out), err))
+        assert got[0] == got[1] == got[2], got
+        print(f"sam concatenate > file: inflated outputs identical on both paths and to merge --suffix's ({got[0][1]})", flush=True)
+        os.remove(out)
+    for p in halves:
+        os.remove(p)
+    os.rmdir(d)
+
+
 def write_part_files(dirname, parts):
     """the count file's records dealt alternately into `parts` files: record j of every repeat goes to part j mod parts; the paths"""
     u = np.frombuffer(unit, dtype=np.uint8)
@@ -667,6 +737,14 @@ if markdup:
     sys.exit(0)
 if recalc_tlen:
     recalc_tlen_rows()
+    sys.exit(0)
+if concatenate_files is not None:
+    write_half_files(concatenate_files)
+    print(f"wrote {concatenate_files}/a.bam and b.bam: {n} records", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if concatenate:
+    concatenate_rows()
     sys.exit(0)
 if subsample:
     subsample_rows()
