@@ -98,3 +98,114 @@ def test_deeper_than_the_last_bin_is_dropped():
     recs = [rec(b"p%d" % i, 0, 100, cigar=((M, i + 1),), l_seq=0) for i in range(10002)]
     hist, dropped, n_pos, _ = both(raw_of(recs, refs))
     assert dropped == 2 and hist[10000] == 1 and hist[9999] == 1 and hist[0] == 20000 - 10002 and n_pos == 20000
+
+
+# ---- the inputs that take the device path's fixed-size structures past their capacity (tests/test_gpu_bam_coverage.py runs them) ----
+@pytest.fixture(scope="module")
+def carry():
+    refs, recs = m.carry_input()
+    raw = raw_of(recs, refs)
+    return raw, m.sweep(raw)
+
+
+def test_carry_input_by_arithmetic(carry):
+    """no counter per position for 20 references of 2^31 - 1: the events statement against the sums written out by hand"""
+    raw, swept = carry
+    exp = m.carry_expected()
+    assert m.events(raw, swept=swept) == exp
+    hist, dropped, n_pos, n_counted = exp
+    assert (n_counted, hist[1], n_pos, hist[0], dropped) == (327680, 21474508800, 42949672940, 21475164140, 0)
+    assert sum(hist) == n_pos == m.target_size(raw, ("everywhere",))
+    # every gap is 65 535 positions but the one behind each reference's last run
+    widths = {}
+    for depth, inside, w in swept[0]:
+        if w:
+            assert inside == 1
+            widths[(depth, w)] = widths.get((depth, w), 0) + 1
+    assert widths == {(1, 65535): 327680, (0, 65535): 20 * 16383, (0, 98302): 20}
+
+
+def test_carry_input_wraps_an_lds_counter_on_four_workgroups_only(carry):
+    """the precondition of the GPU case: on the grid of a context planned for one CU some workgroup's counters of depth 0 and of depth
+    1 both pass 2^32; on the grid of a whole chip none comes near.  17 references are the fewest that still do, 16 do not."""
+    raw, swept = carry
+    n_events = len(swept[0]) + 1
+    assert n_events == 2 * 327680 + 2 * 20
+    assert m.hist_grid(n_events, 1) == 4 and m.hist_grid(n_events, 256) == 1024 and m.hist_grid(700, 256) == 3
+    four = m.lds_sums(swept, 4)
+    assert set(four) == {0, 1} and min(four.values()) > 1.2 * 2 ** 32
+    assert max(m.lds_sums(swept, 1024).values()) < 2 ** 32 // 100
+    for n_ref, wraps in ((17, True), (16, False)):                        # by the arithmetic of the issue: about 2 * 16 384 / 8 gaps a bin and workgroup
+        per_bin = n_ref * 16384 // 4 * 65535
+        assert (per_bin > 2 ** 32) == wraps
+
+
+def test_lds_sums_by_hand():
+    # event i: (depth, inside, w); workgroup (i // 256) % grid
+    gaps = [(0, 1, 10)] * 256 + [(1, 1, 7)] * 256 + [(0, 1, 65536), (0, 0, 5), (m.BINS, 1, 5), (0, 1, 0), (0, 1, 65535)] + [(1, 1, 1)] * 251 + [(1, 1, 3)]
+    assert m.lds_sums((gaps, 0), 1) == {0: 2560 + 65535, 1: 7 * 256 + 251 + 3}
+    assert m.lds_sums((gaps, 0), 2) == {0: 65535 + 2560, 1: 7 * 256 + 3}
+    assert m.lds_sums((gaps, 0), 3) == {0: 65535, 1: 7 * 256}
+    assert m.lds_sums((gaps, 0), 4) == {0: 65535, 1: 7 * 256}
+
+
+def test_split_input_has_every_gap_on_both_sides():
+    refs, recs, want = m.split_input()
+    raw = raw_of(recs, refs)
+    hist, dropped, n_pos, n_counted = both(raw)
+    assert refs == [(b"s", 1 << 20)] and n_pos == 1 << 20 and n_counted == len(recs) == 3 + 9999 + 3 + 6
+    got = {}
+    for depth, inside, w in m.sweep(raw)[0]:
+        if inside > 0 and 65535 <= w <= 65537:
+            got.setdefault(depth, []).append(w)
+    assert got == want and sorted(want) == [0, 1, m.BINS - 1, m.BINS]
+    assert hist[m.BINS - 1] == dropped == 65535 + 65536 + 65537 and hist[1] == dropped + 1 and hist[9999] == 1
+    assert [m.core(r)[1] for r in recs] == sorted(m.core(r)[1] for r in recs)
+
+
+def test_pow2_inputs():
+    sizes = []
+    for name, refs, recs in m.pow2_inputs():
+        raw = raw_of(recs, refs)
+        size = sum(ln for _, ln in refs)
+        sizes.append(size)
+        last = len(refs) - 1
+        ends = [m.runs(r, refs[m.core(r)[0]][1])[0] for r in recs if m.core(r)[0] == last]
+        assert any(rs and rs[-1][1] == refs[last][1] and m.core(r)[1] + 12 == refs[last][1] for r, rs in zip([r for r in recs if m.core(r)[0] == last], ends))
+        assert any(m.core(r)[:2] == (0, 0) and m.counted(r, len(refs)) for r in recs)
+        assert both(raw)[2] == size                                       # every reference has a counted record
+        hist, _, n_pos, _ = both(raw, ("region", refs[last][0]))
+        assert n_pos == refs[last][1] and sum(hist[1:]) > 0
+        assert both(raw, ("region", b"%s:%d-%d" % (refs[last][0], refs[last][1] - 3, refs[last][1] + 9)))[2] == 4
+    assert sizes == [(1 << 13) - 1, 1 << 13, (1 << 13) + 1, 1 << 12]
+
+
+def test_words_input():
+    refs, recs, bed, bed2 = m.words_input()
+    raw = raw_of(recs, refs)
+    assert len(refs) == 70 and all(200 <= ln < 600 for _, ln in refs)
+    assert {m.core(r)[0] for r in recs if m.counted(r, 70)} == set(m.WORDS_COUNTED)
+    assert {m.core(r)[0] for r in recs if not m.counted(r, 70)} == {t for t, _ in m.WORDS_NOT}
+    assert {t >> 5 for t in m.WORDS_COUNTED} == {0, 1, 2} and {t & 31 for t in m.WORDS_COUNTED} >= {0, 31, 1}
+    assert both(raw)[2] == sum(refs[t][1] for t in m.WORDS_COUNTED)
+    assert sorted(m.targets(raw, ("bed", bed))[0]) == list(m.WORDS_COUNTED) and both(raw, ("bed", bed))[2] == 70 * 7
+    assert sorted(m.targets(raw, ("bed", bed2))[0]) == [t for t in m.WORDS_COUNTED if t != 64]
+    assert both(raw, ("bed", bed2))[2] == 70 * 6 and refs[64][1] >= 190
+
+
+def test_deep_bed_cases():
+    bed = m.deep_bed()
+    merged = {}
+    for t, b, e in m.parse_bed(bed, m.DEEP_REFS):
+        merged.setdefault(t, []).append((b, e))
+    assert sorted(merged) == [0, 2] and len(merged[0]) > m.DEEP_N + 200 and merged[0] != sorted(merged[0])
+    assert all(m.merge(v) == [m.deep_iv(k) for k in range(m.DEEP_N)] for v in merged.values())
+    cases = m.deep_cases()
+    seen = set()
+    for name, recs, reported in cases:
+        raw = raw_of(recs, m.DEEP_REFS)
+        assert sorted(m.targets(raw, ("bed", bed))[0]) == sorted(t for t, yes in reported.items() if yes), name
+        assert both(raw, ("bed", bed))[2] == 50 * m.DEEP_N * sum(reported.values()), name
+        seen |= {(m.core(r)[0], m.core(r)[1]) for r in recs}
+    assert len(cases) == len(m.DEEP_RELATIONS) * len(m.DEEP_KS) + 3 and len(seen) > len(cases)
+    assert {yes for _, _, yes in m.DEEP_RELATIONS.values()} == {True, False}

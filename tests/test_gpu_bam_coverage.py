@@ -1,7 +1,10 @@
 """GPU: sk_bam_file_coverage — `sam coverage histogram` from sorted CIGAR events on the device (mark, emit, radix sort, scan, LDS
 histogram) — against the literal statement of tests/bam_coverage_model.py (one counter per position).  The one file whose references
 are too long for a counter per position is held to the events statement, which tests/test_bam_coverage_model.py holds to the literal
-one.  Every check asserts sum(hist) + n_dropped == n_positions == the size of the targets."""
+one.  Every check asserts sum(hist) + n_dropped == n_positions == the size of the targets.
+The last five tests take the path's fixed-size structures past their capacity — the 32-bit LDS counters of the histogram kernel, its
+split at gaps of 2^16, the sort's key width, the bitmaps' second and third word, the search in a long interval list — on inputs that
+tests/bam_coverage_model.py generates and tests/test_bam_coverage_model.py holds on the CPU."""
 import random
 
 import numpy as np
@@ -178,3 +181,87 @@ def test_arguments(ctx, bam):
     handled, hist, n_pos, n_drop, _, _ = ctx.bam_file_coverage(str(path), 1, [(2, 50, 90), (99, 0, 5), (2, 10, 60), (-1, 0, 5), (2, 70, 80)])
     assert handled and n_pos == 80 == int(hist.sum()) + n_drop
     assert hist.tolist() == m.literal(raw, ("region", b"ref2:11-90"))[0]
+
+
+# ---- past the capacity of the path's fixed-size structures ------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def one_cu(hip_lib):
+    """a context that plans for one CU, as `small[1]` of tests/test_gpu_small_grid.py (which imports this file, so it is made here):
+    launch_bam_cov_hist gives it four workgroups"""
+    from tests.test_gpu_small_grid import planned
+    c = planned("1")
+    assert c.planned_cus() == 1
+    yield c
+    c.close()
+
+
+def known(exp):
+    """a model for check(): what the caller has computed already"""
+    return lambda raw, mode: exp
+
+
+def test_lds_counters_wrap(ctx, one_cu, tmp):
+    """bam_cov_hist_kernel's carry, `if (old + (u32)w < old) atomicAdd(hist + depth, 1ull << 32)`: 327 680 runs of 65 535 positions, 65 535
+    apart, on 20 references of 2^31 - 1.  On the four workgroups of a context planned for one CU the gaps below 2^16 add up to 5.4e9 per
+    workgroup and depth, for depth 0 and for depth 1 (asserted from the model's sorted events): both counters wrap.  On the default
+    grid none does.  Both equal the sums written out by hand (tests/bam_coverage_model.py: carry_expected) and each other."""
+    refs, recs = m.carry_input()
+    path = tmp / "carry.bam"
+    raw = m.write(path, recs, text=TEXT, refs=refs, level=1)
+    swept = m.sweep(raw)
+    exp = m.carry_expected()
+    assert m.events(raw, swept=swept) == exp and exp[0][1] == 327680 * 65535 and exp[0][0] + exp[0][1] == exp[2] == 20 * ((1 << 31) - 1)
+    n_events = len(swept[0]) + 1
+    assert m.hist_grid(n_events, 1) == 4 < m.hist_grid(n_events, ctx.planned_cus())
+    four, whole = m.lds_sums(swept, 4), m.lds_sums(swept, m.hist_grid(n_events, ctx.planned_cus()))
+    assert four[0] > 1 << 32 and four[1] > 1 << 32 and max(whole.values()) < 1 << 32
+    got = [check(c, path, raw, ("everywhere",), model=known(exp)) for c in (one_cu, ctx)]
+    assert np.array_equal(got[0][0], got[1][0]) and got[0][1:] == got[1][1:] == (exp[2], 0)
+
+
+def test_gaps_on_both_sides_of_the_lds_split(ctx, one_cu, tmp):
+    """bam_cov_hist_kernel's `w >= 65536`: gaps of 65 535 (LDS), 65 536 and 65 537 (the global counter at once) at depth 0, 1, 10 000
+    (the last bin) and 10 001 (dropped)"""
+    refs, recs, gaps = m.split_input()
+    path, raw = make(tmp, "split.bam", recs, refs)
+    exp = m.literal(raw)
+    assert sorted(gaps) == [0, 1, 10000, 10001] and all(ws == [65535, 65536, 65537] for ws in gaps.values())
+    for c in (one_cu, ctx):
+        hist, n_pos, n_drop = check(c, path, raw, ("everywhere",), model=known(exp))
+        assert n_pos == 1 << 20 and n_drop == 3 * 65536 == hist[10000] and hist[1] == 3 * 65536 + 1
+
+
+def test_genome_sizes_at_a_power_of_two(ctx, tmp):
+    """sk_bam_file_coverage's `bits` loop: the largest sort key is the genome's size itself, the end of a run (and of a target) on the
+    last position; at 2^13 and 2^12 it alone needs the top bit"""
+    sizes = []
+    for name, refs, recs in m.pow2_inputs():
+        path, raw = make(tmp, "genome%s.bam" % name, recs, refs)
+        last = refs[-1]
+        sizes.append(check(ctx, path, raw, ("everywhere",))[1])
+        hist, n_pos, _ = check(ctx, path, raw, ("region", last[0]))
+        assert n_pos == last[1] and int(hist[1:].sum()) > 0
+        assert check(ctx, path, raw, ("region", b"%s:%d-%d" % (last[0], last[1] - 3, last[1] + 9)))[1] == 4
+        assert check(ctx, path, raw, ("bed", b"%s\t%d\t%d\ng0\t0\t1\n" % (last[0], last[1] - 1, last[1] + 5)))[1] == 2
+    assert sizes == [8191, 8192, 8193, 4096]
+
+
+def test_bitmap_words_beyond_the_first(ctx, tmp):
+    """cov_set_bit's word index and the host's reading of it: 70 references, counted records on 0 31 32 33 63 64 69 alone"""
+    refs, recs, bed, bed2 = m.words_input()
+    path, raw = make(tmp, "words.bam", recs, refs)
+    assert check(ctx, path, raw, ("everywhere",))[1] == sum(refs[t][1] for t in m.WORDS_COUNTED)
+    assert check(ctx, path, raw, ("bed", bed))[1] == 70 * 7                   # the seven references alone are reported
+    assert check(ctx, path, raw, ("bed", bed2))[1] == 70 * 6                  # ref64's interval lies behind its records
+    for t in (1, 31, 32, 64, 65, 69):
+        check(ctx, path, raw, ("region", b"ref%d" % t))
+
+
+def test_deep_bed(ctx, tmp):
+    """the binary search of bam_cov_mark_kernel in 1 000 merged intervals a reference, an empty range of `ioff` between two full ones:
+    a record in every relation to an interval, one a reference and file, so that each decides whether its reference is reported"""
+    bed = m.deep_bed()
+    for k, (name, recs, reported) in enumerate(m.deep_cases()):
+        path, raw = make(tmp, "deep%d.bam" % k, recs, m.DEEP_REFS)
+        _, n_pos, _ = check(ctx, path, raw, ("bed", bed))
+        assert n_pos == 50 * m.DEEP_N * sum(reported.values()), name

@@ -86,7 +86,8 @@ NOT_CAPPED = {
     "bgzf_pack_kernel": "launch_bgzf_pack ignores its n_cu: a workgroup per member",
     "count_order_tile_kernel": "sk_count_order_check_dev launches a workgroup per tile of records; its join is one workgroup",
     "sk_bam_fragments_bed_dev": "its kernels launch a thread per record, uncapped",
-    "census_clear_kernel": "census_reset launches a fixed grid that loops over the table's log at any CU count",
+    "census_clear_kernel": "census_reset launches a fixed grid that loops over the table's log at any CU count "
+                           "(both of its branches, the log's and the whole table's, run in tests/test_gpu_census_log.py)",
 }
 
 
