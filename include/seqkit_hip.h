@@ -619,6 +619,47 @@ int sk_bam_file_merge(sk_ctx *ctx, const char *const *paths, int n_paths, int su
 int sk_bam_file_concatenate(sk_ctx *ctx, const char *path, uint32_t number, int flags, int level /* 0 stored, 1 deflate */,
                             uint64_t window_bytes /* 0 = default */, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8]);
 
+/* ---- BAM out for `sam discard tail artifacts` (src/sam_discard_tail_artifacts.rs:129-226, :243-348; src/genome_reader.rs) ---------
+ * sk_bam_file_discard_tails: sk_bam_file_subsample's front half, window pipeline and header, the header's text followed by the co_bytes
+ * bytes at co_line (whole lines; l_text says so); a record is written byte for byte or not at all.  The genome is the FASTA file at
+ * fasta_path as its index describes it: n_refs entries (names[i], refs[i]), one per line of the caller's .fai, matched to the BAM
+ * header's reference names here (of two entries with one name the later counts).  Base p of a chromosome is the file's byte file_offset
+ * + p / line_bases * line_width + p % line_bases.  The library reads the file itself, only the spans of the chromosomes that mapped
+ * records name, into device memory that it frees before it returns.  An unmapped record (0x4) is written, whatever its refID.  A
+ * mapped record is walked from both ends as count_mismatches does: left from base 0 with ref_offset = pos over its operations in
+ * order, right from base l_seq - 1 with ref_offset = pos + (the D lengths less the I lengths of the whole CIGAR) over them in reverse;
+ * an operation reached when tail_length bases have been examined ends the walk; M = X examine their bases one by one (read base A C G T
+ * for codes 1 2 4 8, else N; the chromosome's byte at ref_offset + base index, ASCII-upper-cased; a mismatch unless they are equal or
+ * either is N), I counts one mismatch and moves the base index by its length and ref_offset against it, D counts one and moves
+ * ref_offset.  The record is failed, and not written, iff either count >= min_mismatches (the caller's check_threshold(tail_length,
+ * ratio); UINT32_MAX fails none).  *n_records: the records written; *n_total: all records; *n_failed, *n_passed: the mapped records
+ * failed and passed; *n_loads: the chromosome loads of the reference's loop after its first — the mapped records whose refID differs
+ * from the mapped record's before them, from 0 for the first; *raw_bytes: the whole output BAM, inflated.  The windows come from
+ * sk_bam_file_rewrite_next under its rules, first and n numbering the records WRITTEN.
+ * sk_bam_file_discard_tails_loads: the refIDs of loads first .. first + n - 1, in file order.  Valid from
+ * sk_bam_file_discard_tails's return (*handled = 1) until the next sk_bam_file_* call on the ctx other than sk_bam_file_rewrite_next,
+ * after the last window too; a range outside [0, *n_loads], or no such call to ask: SK_ERR_INVALID.
+ * *handled = 0 (info[5] = -(30 + bits)) leaves the file to the caller's reader, nothing written: bit 1 a mapped record with an
+ * operation outside M I D = X anywhere in its CIGAR (the reference panics where a walk reaches one: the caller's reader decides
+ * exactly), 2 an examined base whose read index lies outside [0, l_seq) or whose reference index lies outside the chromosome, 4 a
+ * header without references, a reference 0 or a mapped record's refID without a chromosome (outside the header, no entry of its name,
+ * or a span that ends beyond the file), 8 a record whose variable part is shorter than its fields, 16 a value the reference holds in an
+ * i32 outside that range (pos + the CIGAR's shift, a base index or ref_offset behind an I or D); info[5] = -21: 2^31 records or more
+ * (the reference's counters are i32), or memory cannot be had: the chromosomes' spans, 16 B per record for the offsets, 4 B per record
+ * for the loads, and 32 B per record, 36 B per reference and the scans' scratch for the passes where those do not fit into the device
+ * buffer of the compressed file, which is idle by then (SK_TAILS_OWN_MEMORY set: never there; for tests).  tail_length == 0, a NULL
+ * fasta_path or name, an entry with line_bases == 0 or line_width < line_bases, or a bad level: SK_ERR_INVALID.  level, window_bytes:
+ * as sk_bam_file_rewrite.                                                                                                          */
+typedef struct sk_genome_ref {     /* one line of a .fai behind its name */
+	uint64_t file_offset, length;  /* the first base's byte in the FASTA file; the chromosome's bases */
+	uint64_t line_bases, line_width;
+} sk_genome_ref;
+int sk_bam_file_discard_tails(sk_ctx *ctx, const char *path, const char *fasta_path, const char *const *names, const sk_genome_ref *refs,
+                              int32_t n_refs, uint32_t tail_length, uint32_t min_mismatches, const uint8_t *co_line, uint32_t co_bytes,
+                              int level /* 0 stored, 1 deflate */, uint64_t window_bytes /* 0 = default */, int64_t *n_records, int64_t *n_total,
+                              int64_t *n_failed, int64_t *n_passed, int64_t *n_loads, uint64_t *raw_bytes, int *handled, double info[8]);
+int sk_bam_file_discard_tails_loads(sk_ctx *ctx, int64_t first, int64_t n, int32_t *tids /* HOST */);
+
 /* ---- `sam coverage histogram` (src/sam_coverage_histogram.rs; this build's reading of `samtools depth -a`) --------
  * sk_bam_file_coverage: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0
  * cases, info[] as there), then the depth histogram of the target positions, from sorted CIGAR events on the device.  A record is

@@ -17,7 +17,7 @@ LIBDIR = os.path.join(ROOT, "lib")
 BINDIR = os.path.join(ROOT, "bin")
 LIB_PATH = os.path.join(LIBDIR, "libseqkit_hip.so")
 
-HIP_SOURCES = ["sk_kernels.hip", "sk_census.hip", "sk_inflate.hip", "sk_deflate.hip", "sk_bamtext.hip", "sk_bamwrite.hip", "sk_bamminimize.hip", "sk_bammarkdup.hip", "sk_bamsubsample.hip", "sk_bamtlen.hip", "sk_bammerge.hip", "sk_bamconcat.hip", "sk_bamcoverage.hip", "sk_bampair.hip", "sk_bamtarget.hip", "sk_capi_ctx.cpp", "sk_capi_barcodes.cpp", "sk_capi_comm.hip", "sk_capi_fused.cpp", "sk_capi_bam.cpp", "sk_capi_misc.cpp", "sk_bamfile.cpp", "sk_bamfile_reads.cpp", "sk_bamfile_out.cpp", "sk_bamfile_coverage.cpp", "sk_lut.cpp"]
+HIP_SOURCES = ["sk_kernels.hip", "sk_census.hip", "sk_inflate.hip", "sk_deflate.hip", "sk_bamtext.hip", "sk_bamwrite.hip", "sk_bamminimize.hip", "sk_bammarkdup.hip", "sk_bamsubsample.hip", "sk_bamtlen.hip", "sk_bammerge.hip", "sk_bamconcat.hip", "sk_bamtails.hip", "sk_bamcoverage.hip", "sk_bampair.hip", "sk_bamtarget.hip", "sk_capi_ctx.cpp", "sk_capi_barcodes.cpp", "sk_capi_comm.hip", "sk_capi_fused.cpp", "sk_capi_bam.cpp", "sk_capi_misc.cpp", "sk_bamfile.cpp", "sk_bamfile_reads.cpp", "sk_bamfile_out.cpp", "sk_bamfile_coverage.cpp", "sk_lut.cpp"]
 HIP_DEPS = HIP_SOURCES + ["sk_internal.h", "sk_ctx.h", "sk_lut.h", "sk_bamblock.h", "sk_bamfmt.h", "sk_bamfile.h", "sk_passmem.h", "sk_hoststage.h", "sk_tileplan.h", "sk_censusplan.h", os.path.join(REPO, "include", "seqkit_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
@@ -78,11 +78,11 @@ def build_hosts(force: bool = False) -> list[str]:
     out = []
     for name, srcs, libs in (("fasta", ["host_common.cpp", "host_inflate.cpp", "fasta_main.cpp", "fasta_text.cpp"], ["-lz", "-ldl"]),
                              ("sam", ["host_common.cpp", "host_inflate.cpp", "sam_main.cpp", "sam_bamio.cpp", "sam_columns.cpp", "sam_reads.cpp",
-                                      "sam_bamout.cpp", "sam_coverage.cpp"], ["-lz", "-ldl"])):
+                                      "sam_bamout.cpp", "sam_tails.cpp", "sam_coverage.cpp"], ["-lz", "-ldl"])):
         if not all(os.path.exists(os.path.join(CSRC, s)) for s in srcs):
             continue
         target = os.path.join(BINDIR, name)
-        deps = srcs + ["host_common.h", "sam_host.h", "sam_pairing.h", "sk_bamfmt.h", os.path.join(REPO, "include", "seqkit_hip.h"), LIB_PATH]
+        deps = srcs + ["host_common.h", "sam_host.h", "sam_pairing.h", "sam_tails.h", "sk_bamfmt.h", os.path.join(REPO, "include", "seqkit_hip.h"), LIB_PATH]
         if force or _stale(target, deps):
             cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I", os.path.join(REPO, "include"),
                    "-o", target] + srcs + ["-L", LIBDIR, "-lseqkit_hip", "-Wl,-rpath,$ORIGIN/../lib"] + libs

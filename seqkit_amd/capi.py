@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_concatenate", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_concatenate", "sk_bam_file_discard_tails", "sk_bam_file_discard_tails_loads", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_on_target_set_regions", "sk_on_target_add", "sk_on_target_add_dev", "sk_on_target_get",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
@@ -259,6 +259,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_file_subsample": (i32, [vp, C.c_char_p, C.c_float, C.c_uint64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_recalc_tlen": (i32, [vp, C.c_char_p, i64, i32, C.c_uint64, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_recalc_tlen_discarded": (i32, [vp, i64, i64, vp]),
+        "sk_bam_file_discard_tails": (i32, [vp, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), vp, i32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, i32, C.c_uint64,
+                                            C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32),
+                                            C.POINTER(C.c_double)]),
+        "sk_bam_file_discard_tails_loads": (i32, [vp, i64, i64, vp]),
         "sk_bam_file_coverage": (i32, [vp, C.c_char_p, i32, vp, i64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(i64), C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
@@ -559,6 +563,28 @@ class Context:
         """sk_bam_file_concatenate, one input of `sam concatenate`: (handled, records, inflated bytes of this call's members, info f64[8]);
         then bam_file_rewrite_windows() yields the windows.  flags: CONCAT_HEADER | CONCAT_EOF."""
         return self._bam_out_call("sk_bam_file_concatenate", path, (number, flags, level, window_bytes))
+
+    def bam_file_discard_tails(self, path: str, fasta_path: str, fai, tail_length: int, min_mismatches: int, co_line: bytes = b"", level: int = 1,
+                               window_bytes: int = 0):
+        """sk_bam_file_discard_tails: (handled, records written, all records, failed, passed, chromosome loads, inflated output bytes,
+        info f64[8]); then bam_file_rewrite_windows() yields the windows and bam_file_discard_tails_loads() the loads' refIDs.
+        fai: the index's lines as (name bytes, length, offset, line_bases, line_width)."""
+        fai = list(fai)
+        names = (C.c_char_p * max(len(fai), 1))(*[bytes(e[0]) for e in fai])
+        refs = np.ascontiguousarray(np.array([[e[2], e[1], e[3], e[4]] for e in fai], dtype=np.uint64).reshape(-1, 4))      # sk_genome_ref: file_offset, length, line_bases, line_width
+        outs = [C.c_int64(0) for _ in range(5)]
+        raw_bytes, handled = C.c_uint64(0), C.c_int32(0)
+        info = (C.c_double * 8)()
+        self._check(self._lib.sk_bam_file_discard_tails(self._h, os.fsencode(path), os.fsencode(fasta_path), names, refs.ctypes.data if len(fai) else None, len(fai),
+                                                        tail_length, min_mismatches, co_line, len(co_line), level, window_bytes, *[C.byref(v) for v in outs],
+                                                        C.byref(raw_bytes), C.byref(handled), info), "sk_bam_file_discard_tails")
+        return (bool(handled.value), *(int(v.value) for v in outs), int(raw_bytes.value), [float(x) for x in info])
+
+    def bam_file_discard_tails_loads(self, first: int, n: int):
+        """sk_bam_file_discard_tails_loads: the refIDs of chromosome loads first .. first + n - 1, in file order."""
+        tids = np.zeros(max(n, 0), dtype=np.int32)
+        self._check(self._lib.sk_bam_file_discard_tails_loads(self._h, first, n, tids.ctypes.data if n > 0 else None), "sk_bam_file_discard_tails_loads")
+        return [int(t) for t in tids]
 
     def bam_file_coverage(self, path: str, mode: int = 0, targets=()):
         """sk_bam_file_coverage: (handled, hist u64[COVERAGE_BINS], target positions, positions deeper than the last bin, counted records,

@@ -314,10 +314,10 @@ void finish_at_exit(BamOut *out)
 	host::at_exit_flush(finish_bam_out);
 }
 
-void HostBamRewrite::start()
+void HostBamRewrite::start(const uint8_t *more, size_t n_more)
 {
 	finish_at_exit(&out);
-	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw);
+	const std::vector<uint8_t> hdr = bamfmt::rewrite_header(bam.header_raw, more, n_more);
 	out.put(hdr.data(), hdr.size());
 	out.flush();
 }

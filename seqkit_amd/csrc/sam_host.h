@@ -182,11 +182,12 @@ struct HostBamRewrite {
 	std::unique_ptr<BamStream> own;
 	BamStream &bam;
 	BamOut out;
-	HostBamRewrite(const std::string &path, int level) : own(new BamStream(path, true)), bam(*own), out(level) { start(); }
-	HostBamRewrite(BamStream &reader, int level) : bam(reader), out(level) { start(); }
+	HostBamRewrite(const std::string &path, int level) : own(new BamStream(path, true)), bam(*own), out(level) { start(nullptr, 0); }
+	// more: whole header lines behind the text (sam discard tail artifacts: its @CO line)
+	HostBamRewrite(BamStream &reader, int level, const uint8_t *more = nullptr, size_t n_more = 0) : bam(reader), out(level) { start(more, n_more); }
 	void close();
 private:
-	void start();
+	void start(const uint8_t *more, size_t n_more);
 };
 
 // A record with a new name into rec: the block_size and core as read, the name and its NUL, the `n_tail` bytes kept of what followed the
@@ -208,4 +209,5 @@ int subsample_cmd(int argc, char **argv);
 int recalculate_tlen_cmd(int argc, char **argv);
 int merge_cmd(int argc, char **argv);
 int concatenate_cmd(int argc, char **argv);
+int discard_tail_artifacts_cmd(int argc, char **argv);
 int coverage_histogram_cmd(int argc, char **argv);

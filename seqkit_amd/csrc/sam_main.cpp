@@ -18,10 +18,12 @@
 //   sam recalculate tlen [--uncompressed] [--max-len=N] <bam_file>              sam_bamout.cpp    src/sam_recalculate_tlen.rs
 //   sam merge [--suffix] [--uncompressed] <bam_files>...                        sam_bamout.cpp    src/sam_merge.rs
 //   sam concatenate [--uncompressed] <bam_files>...                             sam_bamout.cpp    src/sam_concatenate.rs
+//   sam discard tail artifacts [--tail-length=N] [--threshold=F] [--mismatches=N] [--debug] <ref_genome.fa> <bam_file> | --test
+//                                                                               sam_tails.cpp     src/sam_discard_tail_artifacts.rs
 //   sam coverage histogram [--region=REGION] [--regions=BED] <bam_file>         sam_coverage.cpp  src/sam_coverage_histogram.rs
 //
-// (`sam concatenate` is a source file of the reference that its src/sam_main.rs does not declare, as `sam recalculate tlen` is: the
-// top-level usage below stays the reference's, which lists neither.)
+// (`sam concatenate` and `sam discard tail artifacts` are source files of the reference that its src/sam_main.rs does not declare, as
+// `sam recalculate tlen` is: the top-level usage below stays the reference's, which lists none of them.)
 //
 // The reference reads BAM through rust-htslib; this host reads and writes the container itself (sam_bamio.cpp, declared with everything
 // else the files share in sam_host.h).  Every command offers a regular file to the device whole first and keeps a record-by-record
@@ -66,6 +68,7 @@ int main(int argc, char **argv)
 	else if (argc >= 3 && is(1, "recalculate") && is(2, "tlen")) rc = recalculate_tlen_cmd(argc, argv);
 	else if (argc >= 2 && is(1, "merge")) rc = merge_cmd(argc, argv);
 	else if (argc >= 2 && is(1, "concatenate")) rc = concatenate_cmd(argc, argv);
+	else if (argc >= 4 && is(1, "discard") && is(2, "tail") && is(3, "artifacts")) rc = discard_tail_artifacts_cmd(argc, argv);
 	else if (argc >= 3 && is(1, "coverage") && is(2, "histogram")) rc = coverage_histogram_cmd(argc, argv);
 	else fprintf(stderr, "%s\n", USAGE_TOP);
 	host::out().flush();

@@ -199,6 +199,10 @@ struct RewriteState : WindowedState {
 	uint64_t disc_gen = 0, n_disc = 0;
 	const uint64_t *disc = nullptr;
 	uint8_t *d_names = nullptr;
+	// sk_bam_file_discard_tails_loads: the refIDs of the chromosome loads after the first, in file order (device, the kept head of ctx
+	// slot kKeepPassWork), of the file call loads_gen (0: none)
+	uint64_t loads_gen = 0, n_loads = 0;
+	const int32_t *loads = nullptr;
 	~RewriteState() { for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
 };
 

@@ -1,5 +1,7 @@
 // sk_bamfile_out.cpp — the BAM-writing file calls (include/seqkit_hip.h: sk_bam_file_rewrite, _minimize, _markdup, _subsample, _recalc_tlen,
-// _merge, _concatenate and sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
+// _merge, _concatenate, _discard_tails and sk_bam_file_rewrite_next) behind the front half of sk_bamfile.cpp: one spine (rw_open, the call's own passes, rw_begin, rw_issue).
+#include <fcntl.h>
+
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -91,9 +93,10 @@ static int rw_open(sk_ctx *c, Cleanup &cl, const Front &fr, int blk_cols, RwOpen
 // What they share once the stream and output offsets (s.krec, s.kout) of the N records that go out are there — every record of the file,
 // or for sk_bam_file_subsample the kept ones —: the window plan, the window area, and the header's members on their way.  `write`:
 // what writes a window; `total`: the records' output bytes; `ends`: SK_CONCAT_HEADER | SK_CONCAT_EOF, both for every call but
-// sk_bam_file_concatenate.
+// sk_bam_file_concatenate; `more`: whole lines behind the header's text (sk_bam_file_discard_tails: its @CO line).
 static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, const WindowWriter &write, int level, uint64_t window_bytes, uint64_t N,
-                    uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8], int ends = SK_CONCAT_HEADER | SK_CONCAT_EOF)
+                    uint64_t total, int64_t *n_records, uint64_t *raw_bytes, int *handled, double info[8], int ends = SK_CONCAT_HEADER | SK_CONCAT_EOF,
+                    const std::vector<uint8_t> *more = nullptr)
 {
 	RewriteState &s = *o.s;
 	int krc = SK_OK;
@@ -103,7 +106,7 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, co
 	if (int r = plan_windows(c, cl, window_bytes, s.kout, nullptr, N, total, 0, s, s.wo, nullptr, mx, &room)) return r;
 	if (!room) BF_LEAVE(21);
 	s.header.clear();
-	if (ends & SK_CONCAT_HEADER) s.header = bamfmt::rewrite_header(fr.header);
+	if (ends & SK_CONCAT_HEADER) s.header = bamfmt::rewrite_header(fr.header, more ? more->data() : nullptr, more ? more->size() : 0);
 	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
 	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
 	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
@@ -659,6 +662,194 @@ extern "C" int sk_bam_file_concatenate(sk_ctx *c, const char *path, uint32_t num
 	}
 	const WindowWriter write = [number, sl](const sk::WriteWindow &w, int n_cu, hipStream_t s) { return sk::launch_bam_concat_write(w, number, sl, n_cu, s); };
 	return rw_begin(c, cl, fr, o, write, level, window_bytes, N, total, n_records, raw_bytes, handled, info, flags);
+}
+
+// ---- sam discard tail artifacts (include/seqkit_hip.h: sk_bam_file_discard_tails, _loads; the windows come from sk_bam_file_rewrite_next) ---
+// The front half, then sk_bamconcat.hip's sizing pass without a suffix for every record's stream offset, the passes of sk_bamtails.hip
+// and sk_bamsubsample.hip's scans and compaction, which leave the WRITTEN records' stream and output offsets where sk_bam_file_rewrite
+// leaves every record's.  The genome: the .fai's entries are matched to the header's reference names here, a first pass marks the
+// refIDs that mapped records name, and only those chromosomes' spans of the FASTA file are read — 64-bit offsets, newlines and all,
+// through two page-locked buffers — into one device buffer that is freed when this call returns: the keep pass is the only reader.
+// The working memory (the compressed file's device buffer, idle by then, or where that is too small ctx slot kKeepPassWork): 32 B per
+// record, the refID tables and the scratch of the scans and the selection.  What sk_bam_file_discard_tails_loads reads is kept in ctx
+// slot kKeepPassWork: 4 B per record, of which the loads take the head.  Declined files: the list in include/seqkit_hip.h.
+namespace {
+struct FdGuard { int fd = -1; ~FdGuard() { if (fd >= 0) close(fd); } };
+}
+
+extern "C" int sk_bam_file_discard_tails(sk_ctx *c, const char *path, const char *fasta_path, const char *const *names, const sk_genome_ref *refs, int32_t n_refs,
+                                         uint32_t tail_length, uint32_t min_mismatches, const uint8_t *co_line, uint32_t co_bytes, int level, uint64_t window_bytes,
+                                         int64_t *n_records, int64_t *n_total, int64_t *n_failed, int64_t *n_passed, int64_t *n_loads, uint64_t *raw_bytes,
+                                         int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_discard_tails", handled, info, cl, fr, [&] {
+		    for (int64_t *p : {n_records, n_total, n_failed, n_passed, n_loads}) if (p) *p = 0;
+		    if (raw_bytes) *raw_bytes = 0;
+		    if (!fasta_path) return sk::ctx_fail(c, SK_ERR_INVALID, "fasta_path is NULL");
+		    if (n_refs < 0 || (n_refs > 0 && (!names || !refs))) return sk::ctx_fail(c, SK_ERR_INVALID, "n_refs = %d", (int)n_refs);
+		    for (int32_t i = 0; i < n_refs; i++)
+			    if (!names[i] || refs[i].line_bases < 1 || refs[i].line_width < refs[i].line_bases) return sk::ctx_fail(c, SK_ERR_INVALID, "refs[%d]", (int)i);
+		    if (tail_length == 0) return sk::ctx_fail(c, SK_ERR_INVALID, "tail_length = 0");
+		    if (co_bytes && !co_line) return sk::ctx_fail(c, SK_ERR_INVALID, "co_line is NULL");
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	const uint64_t N = fr.n_records;
+	if (N >= ((uint64_t)1 << 31)) BF_LEAVE(21);                          // (the reference's counters are i32)
+	// ---- the header's references against the .fai's entries (of two lines with one name the later counts), spans inside the file
+	const std::vector<std::string> bam_names = fr.refs.names(fr.header.data());
+	const int32_t n_bam = (int32_t)std::min<size_t>(bam_names.size(), 0x7fffffff);
+	auto declined = [&](uint32_t bits, const char *why) {
+		if (getenv("SK_BAMFILE_TRACE")) fprintf(stderr, "%s: declined (bits 0x%x): %s\n", fr.who, bits, why);
+	};
+	if (n_bam == 0) { declined(4, "the header lists no reference"); BF_LEAVE(30 + 4); }
+	FdGuard fa;
+	fa.fd = open(fasta_path, O_RDONLY);
+	uint64_t fa_size = 0;
+	if (fa.fd >= 0) {
+		const off_t e = lseek(fa.fd, 0, SEEK_END);
+		if (e > 0) fa_size = (uint64_t)e;
+	}
+	std::vector<sk::TailRef> tab((size_t)n_bam, sk::TailRef{0, 0, 0, 0});
+	std::vector<uint64_t> file_off((size_t)n_bam, 0), span((size_t)n_bam, 0);
+	for (int32_t t = 0; t < n_bam; t++) {
+		for (int32_t i = n_refs - 1; i >= 0; i--) {
+			if (bam_names[(size_t)t] != names[i]) continue;
+			const sk_genome_ref &g = refs[i];
+			if (g.length > ((uint64_t)1 << 40) || g.line_width > ((uint64_t)1 << 40)) break;      // (no chromosome is that long: the span's arithmetic stays in 64 bits)
+			const uint64_t sp = g.length ? (g.length - 1) / g.line_bases * g.line_width + (g.length - 1) % g.line_bases + 1 : 0;
+			if (g.file_offset > fa_size || sp > fa_size - g.file_offset) break;                   // (a span that ends beyond the file: the caller's reader decides)
+			tab[(size_t)t] = sk::TailRef{0, g.length, g.line_bases, g.line_width};
+			file_off[(size_t)t] = g.file_offset; span[(size_t)t] = sp;
+			break;
+		}
+	}
+	if (tab[0].line_bases == 0) { declined(4, "reference 0 has no chromosome in the FASTA index"); BF_LEAVE(30 + 4); }
+	RwOpen o;
+	if (int r = rw_open(c, cl, fr, 6, o, info)) return r;
+	if (!o.s) return SK_OK;
+	hipStream_t st = sk::ctx_stream(c);
+	const int n_cu = sk::ctx_n_cu(c);
+	uint64_t *d_counts = o.d_blk;                                       // (no per-block column, six words: total, failed, passed, written, written bytes; the loads)
+	uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+	const std::vector<uint8_t> more(co_line, co_line + co_bytes);
+	int32_t *loads = nullptr;
+	if (N) {
+		size_t tb = 0, tb2 = 0;
+		BF_HIP(sk::bam_sub_scans(nullptr, &tb, nullptr, nullptr, nullptr, N, st));
+		BF_HIP(sk::bam_tail_loads(nullptr, &tb2, nullptr, nullptr, nullptr, nullptr, N, st));
+		tb = std::max(tb, tb2);
+		uint64_t *krec = nullptr, *off = nullptr;
+		uint32_t *len = nullptr, *pos = nullptr, *used = nullptr;
+		int32_t *tidc = nullptr, *last = nullptr;
+		sk::TailRef *d_tab = nullptr;
+		void *temp = nullptr;
+		passmem::Layout L;
+		L.add(krec, N * 8); L.add(off, N * 8 + 8); L.add(len, N * 4); L.add(pos, N * 4); L.add(tidc, N * 4); L.add(last, N * 4);
+		L.add(used, (uint64_t)n_bam * 4); L.add(d_tab, (uint64_t)n_bam * sizeof(sk::TailRef)); L.add(temp, tb);
+		const passmem::Placement pl = passmem::place(N * 4 + 8, L.total(), fr.fsize + 64, getenv("SK_TAILS_OWN_MEMORY") != nullptr);   // (the knob: for tests of the other placement)
+		uint8_t *own = nullptr;
+		if (!pass_memory(c, pl, own)) BF_LEAVE(21);
+		pl.trace(fr.who, "", "the compressed file's buffer");
+		L.carve(pl.scratch_at(own, fr.d_comp));
+		loads = (int32_t *)own;
+		// ---- every record's stream offset (its length goes where the scan will write): the passes below read valid records only
+		BF_HIP(sk::launch_bam_concat_size(fr.d_out, fr.d_bend, fr.d_entry, fr.nb, o.d_rb, 0u, krec, off, o.d_decline, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (8 an invalid record)
+		// ---- the genome: the chromosomes that mapped records name
+		std::vector<uint32_t> h_used((size_t)n_bam, 0);
+		BF_HIP(sk::launch_bam_tail_used(fr.d_out, krec, N, n_bam, used, n_cu, st));
+		BF_HIP(hipMemcpyAsync(h_used.data(), used, (size_t)n_bam * 4, hipMemcpyDeviceToHost, st));
+		BF_HIP(hipStreamSynchronize(st));
+		uint64_t g_bytes = 0;
+		for (int32_t t = 0; t < n_bam; t++) {
+			if (!h_used[(size_t)t] || tab[(size_t)t].line_bases == 0) { tab[(size_t)t].line_bases = 0; continue; }   // (not read: no record may reach it)
+			tab[(size_t)t].base = g_bytes;
+			g_bytes += (span[(size_t)t] + 255) & ~(uint64_t)255;
+		}
+		const double t_genome = now_ms();
+		uint8_t *d_genome = nullptr;
+		if (hipMalloc((void **)&d_genome, (size_t)g_bytes + 256) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+		cl.dev.push_back(d_genome);
+		if (g_bytes) {
+			const size_t kStage = (size_t)32 << 20;
+			uint8_t *stage[2] = {nullptr, nullptr};
+			hipEvent_t sev[2] = {nullptr, nullptr};
+			for (int b = 0; b < 2; b++) {
+				if (hipHostMalloc((void **)&stage[b], kStage, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+				cl.pinned.push_back(stage[b]);
+				if (hipEventCreateWithFlags(&sev[b], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); BF_LEAVE(21); }
+				cl.events.push_back(sev[b]);
+			}
+			int b = 0;
+			bool busy[2] = {false, false};
+			for (int32_t t = 0; t < n_bam; t++) {
+				if (tab[(size_t)t].line_bases == 0) continue;
+				for (uint64_t done = 0; done < span[(size_t)t];) {
+					const size_t step = (size_t)std::min<uint64_t>(span[(size_t)t] - done, kStage);
+					if (busy[b]) BF_HIP(hipEventSynchronize(sev[b]));
+					for (size_t got = 0; got < step;) {
+						const ssize_t r = pread(fa.fd, stage[b] + got, step - got, (off_t)(file_off[(size_t)t] + done + got));
+						if (r <= 0) BF_LEAVE(21);                                // (the file changed under the call)
+						got += (size_t)r;
+					}
+					BF_HIP(hipMemcpyAsync(d_genome + tab[(size_t)t].base + done, stage[b], step, hipMemcpyHostToDevice, st));
+					BF_HIP(hipEventRecord(sev[b], st));
+					busy[b] = true;
+					b ^= 1;
+					done += step;
+				}
+			}
+		}
+		BF_HIP(hipMemcpyAsync(d_tab, tab.data(), (size_t)n_bam * sizeof(sk::TailRef), hipMemcpyHostToDevice, st));
+		if (getenv("SK_BAMFILE_TRACE")) {
+			BF_HIP(hipStreamSynchronize(st));
+			fprintf(stderr, "%s: genome: %llu bytes read and copied in %.1f ms\n", fr.who, (unsigned long long)g_bytes, now_ms() - t_genome);
+		}
+		// ---- the decisions: the file is served or left here
+		BF_HIP(sk::launch_bam_tail_keep(fr.d_out, krec, N, d_genome, d_tab, n_bam, tail_length, min_mismatches, len, tidc, d_counts, o.d_decline, n_cu, st));
+		BF_HIP(hipMemcpyAsync(counts, d_counts, 40, hipMemcpyDeviceToHost, st));
+		BF_LEAVE_DECLINED(o.d_decline, 0);                              // (1 an operation outside M I D = X, 2 an index out of range, 4 a refID without a chromosome, 16 beyond i32)
+		// ---- the chromosome loads, the written records' stream and output offsets
+		BF_HIP(sk::bam_tail_loads(temp, &tb, tidc, last, loads, d_counts + 5, N, st));
+		BF_HIP(hipMemcpyAsync(counts + 5, d_counts + 5, 8, hipMemcpyDeviceToHost, st));
+		BF_HIP(sk::bam_sub_scans(temp, &tb, len, pos, off, N, st));
+		BF_HIP(sk::launch_bam_sub_compact(krec, len, pos, off, N, o.s->krec, o.s->kout, st));
+		BF_HIP(hipStreamSynchronize(st));
+	}
+	const int rc = rw_begin(c, cl, fr, o, sk::launch_bam_copy_write, level, window_bytes, counts[3], counts[4], n_records, raw_bytes, handled, info,
+	                        SK_CONCAT_HEADER | SK_CONCAT_EOF, &more);
+	if (rc == SK_OK && *handled) {
+		RewriteState &s = *o.s;
+		s.loads_gen = s.gen; s.n_loads = counts[5]; s.loads = loads;
+		if (n_total) *n_total = (int64_t)counts[0];
+		if (n_failed) *n_failed = (int64_t)counts[1];
+		if (n_passed) *n_passed = (int64_t)counts[2];
+		if (n_loads) *n_loads = (int64_t)counts[5];
+	}
+	return rc;
+}
+
+extern "C" int sk_bam_file_discard_tails_loads(sk_ctx *c, int64_t first, int64_t n, int32_t *tids)
+{
+	if (!c) return SK_ERR_INVALID;
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	if (!R || !R->rw.current(R->gen) || R->rw.loads_gen != R->gen)
+		return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_discard_tails_loads: no sk_bam_file_discard_tails to ask");
+	const RewriteState &s = R->rw;
+	if (first < 0 || n < 0 || (uint64_t)first > s.n_loads || (uint64_t)n > s.n_loads - (uint64_t)first)
+		return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_discard_tails_loads: loads %lld .. +%lld of %llu", (long long)first, (long long)n, (unsigned long long)s.n_loads);
+	if (n == 0) return SK_OK;
+	if (!tids) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_discard_tails_loads: tids is NULL");
+	if (int r = sk::ctx_bind(c)) return r;
+	hipStream_t st = sk::ctx_stream(c);
+	BF_HIP(hipMemcpyAsync(tids, s.loads + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+	BF_HIP(hipStreamSynchronize(st));
+	return SK_OK;
 }
 
 extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)

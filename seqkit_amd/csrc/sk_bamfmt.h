@@ -46,19 +46,20 @@ inline void bgzf_trailer(uint8_t *t, uint32_t crc, uint32_t isize)
 
 // Header::from_template + Writer (htslib sam_hdr_write): the text up to its first NUL, trailing '\n's stripped and one appended when
 // anything is left; the reference list as read (htslib would rebuild it from the @SQ lines: DESIGN.md §10).  h: "BAM\1" .. the end of
-// the reference list, as its reader checked it.
-inline std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h)
+// the reference list, as its reader checked it.  more: whole lines behind the text (Header::push_comment, `sam discard tail artifacts`).
+inline std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &h, const uint8_t *more = nullptr, size_t n_more = 0)
 {
 	const uint32_t l_text = le32(h.data() + 4);
 	const uint8_t *text = h.data() + 8;
 	size_t n = 0;
 	while (n < l_text && text[n] != 0) n++;
 	while (n > 0 && text[n - 1] == '\n') n--;
-	const uint32_t l_new = n ? (uint32_t)n + 1 : 0;
+	const uint32_t l_new = (n ? (uint32_t)n + 1 : 0) + (uint32_t)n_more;
 	std::vector<uint8_t> o(h.begin(), h.begin() + 4);
 	for (int k = 0; k < 4; k++) o.push_back((uint8_t)(l_new >> (8 * k)));
 	o.insert(o.end(), text, text + n);
 	if (n) o.push_back('\n');
+	if (n_more) o.insert(o.end(), more, more + n_more);
 	o.insert(o.end(), h.begin() + 8 + (ptrdiff_t)l_text, h.end());
 	return o;
 }

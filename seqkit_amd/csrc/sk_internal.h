@@ -335,6 +335,22 @@ hipError_t launch_bam_merge_write(const WriteWindow &w, const uint8_t *kin, int 
 hipError_t launch_bam_concat_size(const uint8_t *stream, const uint64_t *bend, const uint64_t *entry, int64_t nb, const uint64_t *rb, uint32_t suffix_len,
                                   uint64_t *krec, uint64_t *kout, uint32_t *decline, hipStream_t st);
 hipError_t launch_bam_concat_write(const WriteWindow &w, uint32_t number, uint32_t suffix_len, int n_cu, hipStream_t st);
+// ---- sam discard tail artifacts: the record passes of sk_bam_file_discard_tails (sk_bamtails.hip) ----
+// A BAM refID's chromosome on the device: where its span of the FASTA file begins in the genome buffer, its bases, and the .fai's line
+// shape; line_bases == 0: the refID has none (no line of that name, or a span that ends beyond the file).
+struct TailRef { uint64_t base, length, line_bases, line_width; };
+constexpr int32_t kTailUnmapped = INT32_MIN;     // tidc of an unmapped record (as a refID it is outside every header, and declined)
+// used: used[t] = 1 for the refIDs 0 .. n_refs - 1 that mapped records name (krec: the records' stream offsets).  keep: len[k] = record
+// k's bytes where it is written, else 0; tidc[k] = its refID or kTailUnmapped; counts[0 .. 4] += the records, the failed, the passed
+// and the written ones, the written bytes; decline bits 1 (an operation outside M I D = X on a mapped record), 2 (an examined base
+// outside the read or the chromosome), 4 (a mapped record's refID without a chromosome), 16 (a value outside the i32 range).  loads
+// (temp == nullptr: only *temp_bytes; last: n entries of scratch): the refIDs of the chromosome loads after the first, in file order,
+// and *n_loads (device) their number.
+hipError_t launch_bam_tail_used(const uint8_t *stream, const uint64_t *krec, uint64_t n, int32_t n_refs, uint32_t *used, int n_cu, hipStream_t st);
+hipError_t launch_bam_tail_keep(const uint8_t *stream, const uint64_t *krec, uint64_t n, const uint8_t *genome, const TailRef *refs, int32_t n_refs,
+                                uint32_t tail_length, uint32_t min_mismatches, uint32_t *len, int32_t *tidc, uint64_t *counts, uint32_t *decline, int n_cu,
+                                hipStream_t st);
+hipError_t bam_tail_loads(void *temp, size_t *temp_bytes, const int32_t *tidc, int32_t *last, int32_t *loads, uint64_t *n_loads, uint64_t n, hipStream_t st);
 // ---- sam to: the mate pairing of sk_bam_file_pairs and its windows' text (sk_bampair.hip) ----
 // Over the K kept records of launch_bam_reads_index (file order; kind 0 unpaired, 1 first, 2 last mate).  A record's fate: where its text
 // goes; aux: for a record of a pair the kept index of the record that COMPLETED the pair, for a leftover its order record.  Its class: what

@@ -19,6 +19,18 @@ statistics --on-target` rows, see below] [--on-target-files=DIR: only write that
 run of the command] [--recalc-tlen: only the `sam recalculate tlen` rows, see below] [--use-file=PATH: with --recalc-tlen, the file
 --markdup-file wrote to PATH instead of a new one; it is left there] [--concatenate: only the `sam concatenate` rows, see below]
 [--concatenate-files=DIR: only write those rows' two files to DIR (a.bam, b.bam), for a profiler run of the command]
+[--tails: only the `sam discard tail artifacts` rows, see below] [--tails-files=DIR: only write that row's file and the smaller genome
+to DIR (in.bam, genome.fa, genome.fa.fai), for a profiler run of the command]
+
+--tails: the subsample file with bases that match a generated genome: one chromosome per reference, every reference the same 50 400
+bases that the reads lie on and then filler up to the genome's size; five reads in eight are 150M, one has an insertion and one a
+deletion behind base 70, one has four mismatches in its left tail and fails at the defaults.  Two genomes, about 0.4 GB and about 3 GB
+of FASTA in lines of 60 bases, so that the cost per GB of bringing the genome in separates from the cost per record.  Rows, all to
+/dev/null: `sam subsample --seed=1 <file> 1.0` on the device path (--yardstick-sam: another build's, the parent commit's) — it writes
+every record through the same windows —, `sam discard tail artifacts` on the device path with either genome and, twice, through the host
+reader with the smaller one.  The ratios to the yardstick are printed run for run next to the spread (max - min) of the yardstick's
+repeats, and the library's own line on the genome (bytes, milliseconds).  With --check the device path and the host reader also write a
+file each, and the inflated outputs and stderr (the seconds masked) are compared.
 
 --concatenate: the mark duplicates file cut in two: the first half of its repeats and the second, each position-sorted, under one
 header.  Rows, all to /dev/null: `sam merge --suffix a b` on the device path (--yardstick-sam: another build's, the parent commit's) —
@@ -113,6 +125,8 @@ on_target_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith
 recalc_tlen = "--recalc-tlen" in sys.argv
 concatenate = "--concatenate" in sys.argv
 concatenate_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--concatenate-files=")), None)
+tails_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--tails-files=")), None)
+tails = "--tails" in sys.argv or tails_files is not None
 use_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--use-file=")), None)
 merge_files = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--merge-files=")), None)
 markdup_file = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--markdup-file=")), None)
@@ -137,6 +151,7 @@ unit = bytearray()
 starts, ends = [], []
 dup_mode = markdup or markdup_file is not None or recalc_tlen or concatenate or concatenate_files is not None
 tl_prev, umi_prev = 0, b""
+chrom = rng.integers(0, 4, size=PAIRS + 400).astype(np.uint8) if tails else None          # --tails: the bases the reads lie on (0 .. 3 = A C G T)
 for i in range(PAIRS):
     tl = int(rng.lognormal(np.log(170), 0.35))
     pos, aux = i, b""
@@ -149,11 +164,24 @@ for i in range(PAIRS):
     for mate in (0, 1):
         name = b"read%d\0" % i
         nib = codes[rng.integers(0, 4, size=150)]
+        cigar = struct.pack("<I", 150 << 4)
+        if tails:
+            kind = i % 8
+            if kind == 5:                                                       # 70M 2I 78M
+                nib = codes[np.concatenate([chrom[pos:pos + 70], rng.integers(0, 4, size=2).astype(np.uint8), chrom[pos + 70:pos + 148]])]
+                cigar = struct.pack("<III", 70 << 4, (2 << 4) | 1, 78 << 4)
+            elif kind == 6:                                                     # 70M 3D 80M
+                nib = codes[np.concatenate([chrom[pos:pos + 70], chrom[pos + 73:pos + 153]])]
+                cigar = struct.pack("<III", 70 << 4, (3 << 4) | 2, 80 << 4)
+            else:
+                nib = codes[chrom[pos:pos + 150]]
+                if kind == 7:                                                   # four mismatches in the left tail
+                    nib[2:18:4] = codes[(chrom[pos + 2:pos + 18:4] + 1) & 3]
         packed = ((nib[0::2] << 4) | nib[1::2]).astype(np.uint8).tobytes()
         q = rng.integers(2, 41, size=150, dtype=np.uint8).tobytes()
         flag = 1 | 2 | (64 | 32 if mate == 0 else 128 | 16)
-        body = struct.pack("<iiBBHHHiiii", 0, pos, len(name), 60 if i % 7 else 10, 4680, 1, flag, 150, 0, pos + (tl if mate == 0 else -tl),
-                           tl if mate == 0 else -tl) + name + struct.pack("<I", 150 << 4) + packed + q + aux
+        body = struct.pack("<iiBBHHHiiii", 0, pos, len(name), 60 if i % 7 else 10, 4680, len(cigar) // 4, flag, 150, 0, pos + (tl if mate == 0 else -tl),
+                           tl if mate == 0 else -tl) + name + cigar + packed + q + aux
         starts.append(len(unit))
         unit += struct.pack("<i", len(body)) + body
         ends.append(len(unit))
@@ -452,6 +480,83 @@ def recalc_tlen_rows():
     os.rmdir(d)
 
 
+def write_genome(path, total_bytes):
+    """one chromosome per reference of the count file, every one the reads' bases and filler, in lines of 60 bases; path.fai beside it"""
+    per = max(len(chrom) + 60, total_bytes // reps // 61 * 60) // 60 * 60
+    grng = np.random.default_rng(11)
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[np.concatenate([chrom, grng.integers(0, 4, size=per - len(chrom)).astype(np.uint8)])]
+    body = np.concatenate([bases.reshape(-1, 60), np.full((per // 60, 1), 10, dtype=np.uint8)], axis=1).tobytes()
+    at, fai = 0, []
+    with open(path, "wb") as f:
+        for r in range(reps):
+            head = b">chr%d\n" % (r + 1)
+            f.write(head)
+            f.write(body)
+            fai.append(b"chr%d\t%d\t%d\t60\t61\n" % (r + 1, per, at + len(head)))
+            at += len(head) + len(body)
+    with open(path + ".fai", "wb") as f:
+        f.write(b"".join(fai))
+    return at
+
+
+def mask_seconds(err):
+    return b"".join(b"Processing took N seconds.\n" if ln.startswith(b"Processing took ") else ln for ln in err.splitlines(True)
+                    if not ln.startswith(b"sk_bam") and not ln.startswith(b"sam discard tail artifacts: "))
+
+
+def tails_rows():
+    t0 = time.perf_counter()
+    write_count_file(bam)
+    genomes = []
+    for label, size in (("0.4 GB", 400_000_000), ("3 GB  ", 3_000_000_000)):
+        g = os.path.join(d, "genome%d.fa" % len(genomes))
+        genomes.append((label, g, write_genome(g, size)))
+    print(f"tails file: {n} BAM records on {reps} references, sorted, paired, {os.path.getsize(bam) / 1e6:.0f} MB; genomes of "
+          + " and ".join(f"{b / 1e6:.0f} MB" for _, _, b in genomes) + f" of FASTA, written in {time.perf_counter() - t0:.1f} s; {runs} runs per device row, "
+          "alternating, 2 through the host reader", flush=True)
+    yard_sam = yardstick_sam or SAM
+    yard = "sam subsample 1.0              device" + (" (yardstick build)" if yardstick_sam else "")
+    cmds = [(yard, [yard_sam, "subsample", "--seed=1", bam, "1.0"], None)]
+    for label, g, _ in genomes:
+        cmds.append((f"sam discard tail artifacts {label} device", [SAM, "discard", "tail", "artifacts", g, bam], None))
+    cmds.append((f"sam discard tail artifacts {genomes[0][0]} host  ", [SAM, "discard", "tail", "artifacts", genomes[0][1], bam], {"SEQKIT_HOST_INFLATE": "1"}))
+    rows = {}
+    for k in range(runs):
+        for label, cmd, env in cmds:
+            if env and k >= 2:
+                continue
+            dt, cpu, rc, _, err = timed(cmd, dict(env or {}, SK_BAMFILE_TRACE="1"), sink=os.devnull)
+            lines = err.decode(errors="replace").split("\n")
+            served = [ln for ln in lines if ln.startswith("sam ")]
+            assert rc == 0 and served and ("host reader" if env else "device path") in served[0], (label, rc, err[-400:])
+            rows.setdefault(label, []).append((dt, cpu, [ln for ln in lines if "genome:" in ln or "[FAILED]" in ln]))
+    for label, r in rows.items():
+        w, c = [x[0] for x in r], [x[1] for x in r]
+        print(f"{label} > /dev/null: " + ", ".join(f"{dt:.2f} s / {cpu:.1f} CPU-s" for dt, cpu, _ in r)
+              + f"  (wall {min(w):.2f}-{max(w):.2f} s, CPU {min(c):.1f}-{max(c):.1f} s)", flush=True)
+        for ln in r[-1][2]:
+            print("  " + ln, flush=True)
+    ys = [x[0] for x in rows[yard]]
+    for label, _, _ in genomes:
+        ts = [x[0] for x in rows[f"sam discard tail artifacts {label} device"]]
+        print(f"discard tail artifacts ({label.strip()}) / subsample 1.0, device wall, run for run: " + " ".join(f"{a / b:.2f}x" for a, b in zip(ts, ys))
+              + f"; medians {float(np.median(ts)) / float(np.median(ys)):.2f}x; median difference {float(np.median(ts)) - float(np.median(ys)):+.2f} s against the "
+              f"yardstick's max - min {max(ys) - min(ys):.2f} s = {(max(ys) - min(ys)) / float(np.median(ys)):.2f} of its median", flush=True)
+    if markdup_check:
+        got = []
+        for env in (None, {"SEQKIT_HOST_INFLATE": "1"}):
+            dt, cpu, rc, _, err = timed([SAM, "discard", "tail", "artifacts", genomes[0][1], bam], env, sink=out)
+            got.append((rc, inflated_digest(out), mask_seconds(err)))
+        assert got[0] == got[1], got
+        print(f"sam discard tail artifacts > file: inflated outputs and stderr (the seconds masked) identical on both paths ({got[0][1]})", flush=True)
+        os.remove(out)
+    for _, g, _ in genomes:
+        os.remove(g)
+        os.remove(g + ".fai")
+    os.remove(bam)
+    os.rmdir(d)
+
+
 def write_half_files(dirname):
     """the mark duplicates file cut in two: the first half of its repeats in a.bam, the second in b.bam; the paths"""
     halves = [os.path.join(dirname, "a.bam"), os.path.join(dirname, "b.bam")]
@@ -737,6 +842,15 @@ if markdup:
     sys.exit(0)
 if recalc_tlen:
     recalc_tlen_rows()
+    sys.exit(0)
+if tails_files is not None:
+    write_count_file(os.path.join(tails_files, "in.bam"))
+    write_genome(os.path.join(tails_files, "genome.fa"), 400_000_000)
+    print(f"wrote {tails_files}/in.bam ({n} records), genome.fa and genome.fa.fai", flush=True)
+    os.rmdir(d)
+    sys.exit(0)
+if tails:
+    tails_rows()
     sys.exit(0)
 if concatenate_files is not None:
     write_half_files(concatenate_files)

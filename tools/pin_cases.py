@@ -332,5 +332,84 @@ def concatenate_cases():
 
 
 concatenate_cases()
+
+
+# sam discard tail artifacts.  src/sam_discard_tail_artifacts.rs and src/genome_reader.rs are source files that the reference's
+# src/sam_main.rs does not declare: these cases need a host with Rust, on which the reference was built from a copy with `mod
+# sam_discard_tail_artifacts; mod genome_reader;`, a dispatch arm for "discard tail artifacts", `use crate::genome_reader::RefGenomeReader`
+# at :11 and the crates bio and ansi_term (--ref-sam names that binary); any other reference binary answers with its top-level usage, and
+# the cases are not run.  They hold it to tests/bam_discard_tails_model.py: the served records over the parameter grid, every stop
+# (status, and for an ERROR: the message; a panic's text is not compared), the header's @CO line, the argument errors, --test's 30
+# lines, and the readings of DESIGN.md §10 (the .fai arithmetic on the three line shapes, an index that does not parse, a base index
+# at l_seq, ansi_term's bytes).  After a stop the reference may lose its last block: only a prefix is asked for there.
+def discard_tails_cases():
+    global failures
+    from pathlib import Path
+
+    from tests import bam_discard_tails_model as tm
+    words = ["discard", "tail", "artifacts"]
+
+    def differs(what, detail=""):
+        global failures
+        failures += 1
+        print(f"DIFFERENT: sam discard tail artifacts: {what} {detail}")
+
+    def ref(argv, d, stdin=None):
+        r = subprocess.run([args.ref_sam] + words + argv, cwd=d, input=stdin, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        try:
+            out = b"".join(x for x, _ in tm.members(r.stdout)) if r.stdout else b""
+        except Exception:
+            out = None                                                  # (a stream the reference left unfinished)
+        return r.returncode % 256, out, tm.mask_seconds(r.stderr)
+    d = tempfile.mkdtemp(prefix="sk_pin_tails_")
+    try:
+        fasta, genome = tm.write_genome(Path(d))
+        genome.path = "genome.fa"
+        code, out, err = ref([], d)
+        if b"sam discard tail artifacts" not in err:
+            print("sam discard tail artifacts: this reference binary does not declare the command (src/sam_main.rs), cases not run")
+            return
+        if (code, err) != (255, tm.INVALID):
+            differs("usage", f"rc={code} stderr={err[-300:]!r}")
+        raw = tm.write(os.path.join(d, "in.bam"), list(tm.served_records()), text=tm.TEXT, refs=tm.REFS)
+        for T in (1, 20, 33, 64, 300):
+            for opt in ("--threshold=0", "--threshold=0.15", "--threshold=1", "--mismatches=3"):
+                key, val = opt.split("=")
+                exp = tm.model(raw, genome, T, float(val)) if key == "--threshold" else tm.model(raw, genome, T, 0.15, mismatches=int(val))
+                code, out, err = ref(["--tail-length=%d" % T, opt, "genome.fa", "in.bam"], d)
+                if (out, err, code) != exp[:3]:
+                    differs("served records", f"T={T} {opt}: rc={code} stderr={err[-300:]!r}")
+        for label, (before, stop, status, line) in sorted(tm.stop_cases().items()):
+            sraw = tm.write(os.path.join(d, "stop.bam"), before + [stop] + before, text=tm.TEXT, refs=tm.REFS)
+            exp = tm.model(sraw, genome)
+            code, out, err = ref(["genome.fa", "stop.bam"], d)
+            if code != status or (status == 255 and err != exp[1]) or (out is not None and not exp[0].startswith(out)):
+                differs("stop: " + label, f"rc={code} stderr={err[-300:]!r}")
+        odd = tm.record(b"odd", 0, 100, [(0, 7)], [1] * 7, 0)            # T = 8 over 7M of an odd l_seq: no base index reaches l_seq
+        oraw = tm.write(os.path.join(d, "odd.bam"), [odd, tm.record(b"pad", 0, 100, [(0, 8)], [1] * 7, 0)], text=tm.TEXT, refs=tm.REFS)
+        code, out, err = ref(["--tail-length=8", "genome.fa", "odd.bam"], d)
+        if code != tm.model(oraw, genome, 8)[2]:
+            print("known difference: a base index equal to an odd l_seq reads the pad nibble in the reference (DESIGN.md §10)")
+        for argv, message in ((["--tail-length=x"], tm.TAIL_LENGTH_ERROR), (["--tail-length=0"], tm.TAIL_LENGTH_ERROR), (["--threshold=abc"], tm.THRESHOLD_PARSE_ERROR),
+                              (["--mismatches=x"], tm.MISMATCHES_ERROR), (["--threshold=1.01"], tm.THRESHOLD_RANGE_ERROR)):
+            code, out, err = ref(argv + ["genome.fa", "in.bam"], d)
+            if (code, err) != (255, message):
+                differs("argument error", f"{argv}: rc={code} stderr={err[-300:]!r}")
+        with open(os.path.join(d, "bad.fa"), "wb") as f:
+            f.write(tm.genome_files()[0])
+        with open(os.path.join(d, "bad.fa.fai"), "wb") as f:
+            f.write(b"chrA\t5000\t22\t60\n")
+        code, out, err = ref(["bad.fa", "in.bam"], d)
+        if (code, err[-len(tm.open_error("bad.fa")):]) != (255, tm.open_error("bad.fa")):
+            differs("an index that does not parse", f"rc={code} stderr={err[-300:]!r}")
+        r = subprocess.run([args.ref_sam] + words + ["--test"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        lines = r.stderr.split(b"\n")
+        if r.returncode != 0 or len(lines) != 32 or not all(ln.startswith(b"[\x1b[32mPASS\x1b[0m] ") for ln in lines[:30]):
+            differs("--test", f"rc={r.returncode} stderr={r.stderr[-300:]!r}")
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+discard_tails_cases()
 print(f"{failures} differences")
 sys.exit(1 if failures else 0)
