@@ -445,6 +445,31 @@ int sk_bam_file_pairs(sk_ctx *ctx, const char *path, int format /* 0 raw, 1 fast
                       uint64_t window_bytes /* 0 = default */, uint64_t counts[8], int *handled, double info[8]);
 int sk_bam_file_pairs_next(sk_ctx *ctx, sk_bam_pairs_window *w);
 
+/* ---- `sam to` into three .gz files: the paired texts deflated and framed on the device ------------------------------------------
+ * sk_bam_file_pairs_gz: exactly sk_bam_file_pairs with interleaved = 0 — the same records kept, the same three streams in the same
+ * order, the same counts[8], the same *handled = 0 cases and info[5] codes (-94 under SK_PAIR_KEY_BITS among them), all taken before
+ * any window exists — but a window leaves as complete BGZF members, compressed where its text lies, as sk_bam_file_rewrite's do.  One
+ * more *handled = 0 case: the window area (a window's text, 31 B, and with level 1 a deflate slot and its tokens, per block; two packed
+ * buffers on the device and two page-locked ones) cannot be had (info[5] = -21).  level as for sk_bam_file_rewrite: 0 stores every
+ * member, 1 deflates on the device and stores a member that does not shrink.  A bad format or level: SK_ERR_INVALID.  There is no
+ * interleaved form.
+ * sk_bam_file_pairs_gz_next: the next window; w->n == 0 at the end.  A window is a rank range of one stream, stream 1's windows first,
+ * then stream 2's, then the single stream's; window_bytes (0: 64 MiB) bounds its text (a single record may go beyond it).  The text is
+ * cut into blocks of at most SK_DEFLATE_MAX_IN bytes wherever the byte count falls: a record may span members.  The windows of one
+ * stream, concatenated, inflate to exactly the bytes sk_bam_file_pairs hands out for that stream.  A stream without records has no
+ * window, and no window carries the BGZF EOF block: closing a file is the caller's job.  The HOST bytes (the ctx's, page-locked) hold
+ * until the next call on the ctx; the device works on the following window meanwhile.  Calling it after another sk_bam_file_* call, or
+ * without sk_bam_file_pairs_gz: SK_ERR_INVALID; so is sk_bam_file_pairs_next after sk_bam_file_pairs_gz.                          */
+typedef struct sk_bam_pairs_gz_window {
+	int32_t stream;            /* 0 first mates, 1 last mates, 2 the single stream */
+	int64_t first, n;          /* the stream's records first .. first + n - 1; n == 0: the end */
+	const uint8_t *bgzf;       /* HOST, page-locked: complete BGZF members back to back */
+	uint64_t bytes, raw_bytes; /* compressed bytes; the text bytes they inflate to */
+} sk_bam_pairs_gz_window;
+int sk_bam_file_pairs_gz(sk_ctx *ctx, const char *path, int format, uint8_t min_baseq, int level /* 0 stored, 1 deflate */,
+                         uint64_t window_bytes, uint64_t counts[8], int *handled, double info[8]);
+int sk_bam_file_pairs_gz_next(sk_ctx *ctx, sk_bam_pairs_gz_window *w);
+
 /* ---- BAM out for `sam trim qnames`, `sam tags from qname`, `sam qname from tags` (src/sam_trim_qnames.rs:20-30,
  * src/sam_tags_from_qname.rs:33-52, src/sam_qname_from_tags.rs:32-41) ------------------------------------------------------
  * sk_bam_file_rewrite: what sk_bam_file_reduce does up to and including the verified walk (same files, knobs SK_BAMFILE_*, *handled = 0

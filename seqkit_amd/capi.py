@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "sk_counts_reset", "sk_counts_get", "sk_counts_device_ptr",
     "sk_comm_ready", "sk_comm_get_unique_id", "sk_comm_init_rank", "sk_comm_destroy", "sk_counts_allreduce", "sk_allreduce_u64_dev", "sk_bam_flag_tlen", "sk_bam_flag_tlen_dev",
     "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bgzf_inflate_dev", "sk_bam_walk_dev", "sk_bam_walk_reduce_dev", "sk_bam_file_reduce",
-    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_concatenate", "sk_bam_file_discard_tails", "sk_bam_file_discard_tails_loads", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
+    "sk_bam_file_columns", "sk_bam_file_reads", "sk_bam_file_reads_next", "sk_bam_file_pairs", "sk_bam_file_pairs_next", "sk_bam_file_pairs_gz", "sk_bam_file_pairs_gz_next", "sk_bam_file_rewrite", "sk_bam_file_rewrite_next", "sk_bam_file_minimize", "sk_bam_file_markdup", "sk_subsample_keep", "sk_bam_file_subsample", "sk_bam_file_recalc_tlen", "sk_bam_file_recalc_tlen_discarded", "sk_bam_file_merge", "sk_bam_file_concatenate", "sk_bam_file_discard_tails", "sk_bam_file_discard_tails_loads", "sk_bam_file_coverage", "sk_bam_fragments", "sk_bam_fragments_dev", "sk_bam_fragments_bed_dev", "sk_bam_sequence", "sk_bam_sequence_dev",
     "sk_count_set_regions", "sk_count_add", "sk_count_add_dev", "sk_count_get", "sk_count_order_check_dev", "sk_gc_set_genome", "sk_gc_count",
     "sk_on_target_set_regions", "sk_on_target_add", "sk_on_target_add_dev", "sk_on_target_get",
     "sk_census_reset", "sk_census_add", "sk_census_add_dev", "sk_census_stats", "sk_census_count_hist", "sk_census_entries",
@@ -78,6 +78,10 @@ class _ReadsWindow(C.Structure):
 
 class _PairsWindow(C.Structure):
     _fields_ = [("stream", C.c_int32), ("first", C.c_int64), ("n", C.c_int64), ("text", C.c_void_p), ("bytes", C.c_uint64)]
+
+
+class _PairsGzWindow(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("first", C.c_int64), ("n", C.c_int64), ("bgzf", C.c_void_p), ("bytes", C.c_uint64), ("raw_bytes", C.c_uint64)]
 
 
 PAIR_BLOCK = 256                     # kPairBlock (sk_internal.h): the workgroup of sk_bam_file_pairs' pairing kernels
@@ -268,6 +272,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "sk_bam_file_reads_next": (i32, [vp, C.POINTER(_ReadsWindow)]),
         "sk_bam_file_pairs": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
         "sk_bam_file_pairs_next": (i32, [vp, C.POINTER(_PairsWindow)]),
+        "sk_bam_file_pairs_gz": (i32, [vp, C.c_char_p, i32, C.c_uint8, i32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "sk_bam_file_pairs_gz_next": (i32, [vp, C.POINTER(_PairsGzWindow)]),
         "sk_bam_fragments_bed_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(i64)]),
         "sk_count_order_check_dev": (i32, [vp, vp, vp, vp, vp, i64, C.c_uint8, i32, C.POINTER(i64), C.POINTER(i32)]),
         "sk_bam_fragments": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]),
@@ -506,6 +512,24 @@ class Context:
             if w.n == 0:
                 return
             yield {"stream": int(w.stream), "first": int(w.first), "n": int(w.n), "text": C.string_at(w.text, int(w.bytes)) if w.bytes else b""}
+
+    def bam_file_pairs_gz(self, path: str, fmt: str = "fastq", min_baseq: int = 10, level: int = 1, window_bytes: int = 0):
+        """sk_bam_file_pairs_gz: (handled, counts as bam_file_pairs, info f64[8]); then bam_file_pairs_gz_windows() yields the windows."""
+        counts, handled = (C.c_uint64 * 8)(), C.c_int32(0)
+        info = (C.c_double * 8)()
+        f = READS_FORMAT[fmt] if isinstance(fmt, str) else int(fmt)
+        self._check(self._lib.sk_bam_file_pairs_gz(self._h, os.fsencode(path), f, min_baseq, level, window_bytes, counts, C.byref(handled), info),
+                    "sk_bam_file_pairs_gz")
+        return bool(handled.value), [int(x) for x in counts], [float(x) for x in info]
+
+    def bam_file_pairs_gz_windows(self):
+        """sk_bam_file_pairs_gz_next until the end: one dict per window (stream, first, n, bgzf: a bytes copy of its members, raw_bytes)."""
+        while True:
+            w = _PairsGzWindow()
+            self._check(self._lib.sk_bam_file_pairs_gz_next(self._h, C.byref(w)), "sk_bam_file_pairs_gz_next")
+            if w.n == 0:
+                return
+            yield {"stream": int(w.stream), "first": int(w.first), "n": int(w.n), "bgzf": C.string_at(w.bgzf, int(w.bytes)), "raw_bytes": int(w.raw_bytes)}
 
     def _bam_out_call(self, name: str, path: str, args, with_duplicates: bool = False):
         """One of the calls that set rewrite windows up (sk_bam_file_rewrite, _minimize, _markdup, _subsample): its own arguments, which end with

@@ -1176,6 +1176,22 @@ void GzWriter::write(std::string &&s)
 	if (impl_->bytes >= kGzBlock) impl_->submit();
 }
 
+// Members that are finished already (the device deflated and framed them: sk_bam_file_pairs_gz_next) go to the file as they are.  What
+// was written before goes to the pool first and is waited for, so the file keeps the order of the calls; the caller's bytes are written
+// from where they lie, on this thread (they hold only until its next call on the ctx: handing them to the pool would cost a copy).
+void GzWriter::write_members(const uint8_t *p, size_t n)
+{
+	if (!impl_ || impl_->fd < 0) return;
+	if (impl_->bytes > 0) impl_->submit();
+	std::unique_lock<std::mutex> lk(impl_->m);
+	impl_->cv.wait(lk, [this] { return impl_->next_write == impl_->next_submit; });
+	for (size_t off = 0; off < n;) {
+		const ssize_t w = ::write(impl_->fd, p + off, n - off);
+		if (w <= 0) break;                                     // (write errors are ignored, as in completed())
+		off += (size_t)w;
+	}
+}
+
 // what is buffered goes to the pool now; nothing is waited for (a command that closes many files hands in all their tails first: closing
 // them one after the other made every tail a launch of its own on the device path — 96 files, 7 ms each)
 void GzWriter::flush_tail()

@@ -88,6 +88,7 @@ public:
 	void write(const char *p, size_t n);
 	void write(const std::string &s) { write(s.data(), s.size()); }
 	void write(std::string &&s);                         // takes the string over: the copy into the member happens on a pool thread
+	void write_members(const uint8_t *p, size_t n);      // finished gzip members: written as they are, behind everything submitted before
 	void flush_tail();                                   // hand what is buffered to the pool, wait for nothing
 	void close();                                        // flush, wait for this file's blocks, close the descriptor
 	struct Impl;

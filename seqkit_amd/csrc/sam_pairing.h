@@ -26,6 +26,18 @@ inline void write_pair_windows(Next next, Write write)
 	}
 }
 
+// the same loop over the windows of sk_bam_file_pairs_gz, whose bytes are finished BGZF members: `write(stream, p, n)` takes them as they are
+template <class Next, class Write>
+inline void write_member_windows(Next next, Write write)
+{
+	sk_bam_pairs_gz_window w;
+	for (;;) {
+		next(&w);
+		if (w.n == 0) break;
+		write((int)w.stream, w.bgzf, (size_t)w.bytes);
+	}
+}
+
 // The reference's HashMap<Box<str>, Box<str>> (:97-98) over the device path's records, its leftovers listed in insertion order: a flat open-addressing table keyed by the device's 64-bit qname key (names compared
 // byte for byte on a key match), the pending names and texts in an arena that is compacted when most of it is dead.  Same semantics:
 // a second insert under a name replaces the text and keeps its order; after a removal a new insert takes a new order number.

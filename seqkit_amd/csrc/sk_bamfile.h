@@ -1,6 +1,6 @@
 // sk_bamfile.h — what the units of the BAM file calls (include/seqkit_hip.h: sk_bam_file_*) share.  sk_bamfile.cpp holds the front half
 // (read, ship, inflate, verify, walk: bam_file_front) and the helpers declared here, with the two calls that keep no state (reduce,
-// columns); sk_bamfile_reads.cpp the reads call and its windows; sk_bamfile_out.cpp the BAM-writing calls and theirs;
+// columns); sk_bamfile_reads.cpp the reads and pairs calls and their windows; sk_bamfile_out.cpp the BAM-writing calls and theirs;
 // sk_bamfile_coverage.cpp the coverage call.  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,6 +142,24 @@ struct WindowedState {
 	}
 };
 
+// The window area of a call whose windows leave as BGZF members (the BAM-writing calls; sk_bam_file_pairs_gz): one device area for the
+// window's raw bytes, the block table, the deflate's results, CRCs, member sizes, slots and tokens, and two packed-member buffers on
+// each side (ctx slots kKeepFileWin / kKeepFilePin).  pack_area sizes and takes it for windows of at most max_raw bytes (false: it cannot
+// be had); pack_issue is what follows once a window's raw_len bytes lie in d_raw: cut, deflate or crc, pack into packed buffer b, the packed
+// size back, and `done` recorded; pack_fetch copies buffer b's `bytes` to its page-locked twin on the second stream and waits for them.
+struct PackArea {
+	int level = 1;
+	uint8_t *d_raw = nullptr, *d_slots = nullptr, *d_pack[2] = {nullptr, nullptr}, *h_pin[2] = {nullptr, nullptr};
+	uint32_t *d_tokens = nullptr, *d_result = nullptr, *d_crc = nullptr;
+	uint64_t *d_msz = nullptr, *h_size = nullptr;   // h_size[b]: window b's packed bytes (page-locked)
+	void *d_blocks = nullptr;
+	hipEvent_t ev_copy[2] = {nullptr, nullptr};     // the copy of packed buffer b on the second stream
+	~PackArea() { for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
+};
+bool pack_area(sk_ctx *c, PackArea &a, uint64_t max_raw, int level);
+hipError_t pack_issue(sk_ctx *c, PackArea &a, uint64_t raw_len, int b, hipEvent_t done);
+hipError_t pack_fetch(sk_ctx *c, PackArea &a, int b, uint64_t bytes);
+
 // sk_bam_file_reads / sk_bam_file_reads_next (`sam to`): the kept records' columns (device, ctx slot kKeepFileCols), the window plan (text and name
 // bytes of window w from wt[w] / wn[w] on), and two window buffers on each side (ctx slots kKeepFileWin / kKeepFilePin)
 struct ReadsState : WindowedState {
@@ -157,7 +175,8 @@ struct ReadsState : WindowedState {
 // sk_bam_file_pairs / sk_bam_file_pairs_next (`sam to`, the texts in output order): the kept records' stream offsets (device, ctx slot
 // kKeepFileCols), every stream's permutation rank -> record and stream offsets (device, the kept head of ctx slot kKeepPassWork; stream s
 // from entry base[s] + s on), the windows of all streams in the order they are returned — stream 1's, stream 2's, the single stream's —
-// and two text buffers on each side (ctx slots kKeepFileWin / kKeepFilePin).  (ws / next_window of the base are not used: a window here
+// and two text buffers on each side (ctx slots kKeepFileWin / kKeepFilePin) or, for sk_bam_file_pairs_gz / sk_bam_file_pairs_gz_next, the
+// window area of the BAM-writing calls in the same slots.  (ws / next_window of the base are not used: a window here
 // is a rank range of ONE stream.)
 struct PairsState : WindowedState {
 	int fmt = 0;
@@ -169,6 +188,8 @@ struct PairsState : WindowedState {
 	std::vector<Window> plan;
 	uint8_t *d_win[2] = {nullptr, nullptr}, *h_win[2] = {nullptr, nullptr};
 	Window in[2] = {};                           // the window in buffer b
+	bool members = false;                        // sk_bam_file_pairs_gz: a window's text goes to pk.d_raw and leaves as members (d_win / h_win idle)
+	PackArea pk;
 };
 
 // What writes a window's records for the rewrite-window call that is running: that call's launcher (sk_internal.h: launch_bam_*_write)
@@ -179,19 +200,13 @@ typedef std::function<hipError_t(const sk::WriteWindow &w, int n_cu, hipStream_t
 // (device, ctx slot kKeepFileCols), the window plan (output bytes of window w from wo[w] on), the write kernel of the call that runs,
 // one device area for the window being rewritten and compressed (raw bytes, deflate scratch, blocks) and two packed-member buffers on
 // each side (ctx slots kKeepFileWin / kKeepFilePin)
-struct RewriteState : WindowedState {
+struct RewriteState : WindowedState, PackArea {
 	WindowWriter write;
-	int level = 1;
 	uint64_t *krec = nullptr, *kout = nullptr;
 	std::vector<uint64_t> wo;
 	std::vector<uint8_t> header;                 // the output header (the first window); empty: the call writes none (sk_bam_file_concatenate)
 	bool header_done = false;
 	bool eof_due = true;                         // the 28-byte EOF block is still to come (false from the start: the call writes none)
-	uint8_t *d_raw = nullptr, *d_slots = nullptr, *d_pack[2] = {nullptr, nullptr}, *h_pin[2] = {nullptr, nullptr};
-	uint32_t *d_tokens = nullptr, *d_result = nullptr, *d_crc = nullptr;
-	uint64_t *d_msz = nullptr, *h_size = nullptr;   // h_size[b]: window b's packed bytes (page-locked)
-	void *d_blocks = nullptr;
-	hipEvent_t ev_copy[2] = {nullptr, nullptr};     // the copy of packed buffer b on the second stream
 	uint64_t raw[2] = {0, 0};
 	// sk_bam_file_recalc_tlen_discarded: the discarded records' stream offsets in file order and a staging area of kTlenNameSlots name
 	// slots (device, the kept head of ctx slot kKeepPassWork), of the file call disc_gen (0: none)
@@ -203,7 +218,6 @@ struct RewriteState : WindowedState {
 	// slot kKeepPassWork), of the file call loads_gen (0: none)
 	uint64_t loads_gen = 0, n_loads = 0;
 	const int32_t *loads = nullptr;
-	~RewriteState() { for (hipEvent_t e : ev_copy) if (e) (void)hipEventDestroy(e); }
 };
 
 // what stays with the ctx: the range of the compressed file and the range of the inflated stream

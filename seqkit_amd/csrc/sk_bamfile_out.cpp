@@ -21,8 +21,63 @@ using namespace bamfile;
 // complete members; only the members' bytes are copied back.  Every allocation that fails leaves the file to the caller's reader
 // (info[5] = -21).
 
-// the header (first) or window w of the plan (the next non-empty one) into packed buffer b: rewrite, cut, deflate, pack, and the packed
-// size back; false: nothing left
+// ---- the window area and what runs in it (sk_bamfile.h: PackArea), for the calls here and for sk_bam_file_pairs_gz -------------------
+// the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
+bool bamfile::pack_area(sk_ctx *c, PackArea &a, uint64_t max_raw, int level)
+{
+	int krc = SK_OK;
+	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	const uint64_t pack = max_raw + nblk * 31 + 64;
+	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
+	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
+	if (!dw) return false;
+	const size_t p_pack = up(pack + 28);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * p_pack + 64, true, &krc);
+	if (!hw) return false;
+	a.d_raw = dw; a.d_blocks = dw + a_raw; a.d_result = (uint32_t *)(dw + a_raw + a_blk); a.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
+	a.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
+	uint8_t *dp = dw + a_raw + a_blk + a_res + a_crc + a_msz;
+	a.d_pack[0] = dp; a.d_pack[1] = dp + a_pack;
+	a.d_slots = level ? dp + 2 * a_pack : nullptr;
+	a.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
+	a.h_pin[0] = hw; a.h_pin[1] = hw + p_pack; a.h_size = (uint64_t *)(hw + 2 * p_pack);
+	a.level = level;
+	for (int b = 0; b < 2; b++) {
+		if (!blocking_event(a.ev_copy[b])) return false;
+		if (hipEventRecord(a.ev_copy[b], sk::ctx_stream2(c)) != hipSuccess) { (void)hipGetLastError(); return false; }   // (nothing to wait for before the first copy)
+	}
+	return true;
+}
+
+// a window's raw_len bytes lie in d_raw: cut, deflate or crc, pack into packed buffer b, and the packed size back; then `done`
+hipError_t bamfile::pack_issue(sk_ctx *c, PackArea &a, uint64_t raw_len, int b, hipEvent_t done)
+{
+	hipStream_t st = sk::ctx_stream(c);
+	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
+	hipError_t e = hipMemsetAsync(a.d_raw + raw_len, 0, 8, st);                          // (the deflate reads whole dwords)
+	if (e == hipSuccess) e = hipStreamWaitEvent(st, a.ev_copy[b], 0);                   // (the copy out of this packed buffer)
+	if (e == hipSuccess) e = sk::launch_bgzf_cut(raw_len, a.d_blocks, nblk, st);
+	if (e == hipSuccess) e = a.level ? sk::launch_bgzf_deflate(a.d_raw, a.d_blocks, nblk, a.d_slots, SK_DEFLATE_SLOT, a.d_tokens, a.d_result, a.d_crc, sk::ctx_n_cu(c), st)
+	                                 : sk::launch_bgzf_crc(a.d_raw, a.d_blocks, nblk, a.d_crc, sk::ctx_n_cu(c), st);
+	if (e == hipSuccess) e = sk::launch_bgzf_pack(a.d_raw, a.d_blocks, nblk, a.d_slots, SK_DEFLATE_SLOT, a.d_result, a.d_crc, a.level ? 0 : 1, a.d_msz,
+	                                              a.d_pack[b], sk::ctx_n_cu(c), st);
+	if (e == hipSuccess) e = hipMemcpyAsync(a.h_size + b, a.d_msz + nblk, 8, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipEventRecord(done, st);
+	return e;
+}
+
+// packed buffer b's bytes into its page-locked twin, on the second stream (the first one runs the next window meanwhile), and waited for
+hipError_t bamfile::pack_fetch(sk_ctx *c, PackArea &a, int b, uint64_t bytes)
+{
+	hipStream_t st2 = sk::ctx_stream2(c);
+	hipError_t e = bytes ? hipMemcpyAsync(a.h_pin[b], a.d_pack[b], (size_t)bytes, hipMemcpyDeviceToHost, st2) : hipSuccess;
+	if (e == hipSuccess) e = hipEventRecord(a.ev_copy[b], st2);
+	if (e == hipSuccess) e = hipEventSynchronize(a.ev_copy[b]);
+	return e;
+}
+
+// the header (first) or window w of the plan (the next non-empty one) into packed buffer b: rewrite, then pack_issue; false: nothing left
 static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 {
 	*rc = SK_OK;
@@ -41,16 +96,7 @@ static bool rw_issue(sk_ctx *c, RewriteState &s, int b, int *rc)
 		raw_len = s.wo[w + 1] - s.wo[w];
 		e = s.write(sk::WriteWindow{s.d_out, s.krec, s.kout, first, n, s.wo[w], s.d_raw}, sk::ctx_n_cu(c), st);
 	}
-	const int64_t nblk = (int64_t)((raw_len + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
-	if (e == hipSuccess) e = hipMemsetAsync(s.d_raw + raw_len, 0, 8, st);              // (the deflate reads whole dwords)
-	if (e == hipSuccess) e = hipStreamWaitEvent(st, s.ev_copy[b], 0);                   // (the copy out of this packed buffer)
-	if (e == hipSuccess) e = sk::launch_bgzf_cut(raw_len, s.d_blocks, nblk, st);
-	if (e == hipSuccess) e = s.level ? sk::launch_bgzf_deflate(s.d_raw, s.d_blocks, nblk, s.d_slots, SK_DEFLATE_SLOT, s.d_tokens, s.d_result, s.d_crc, sk::ctx_n_cu(c), st)
-	                                 : sk::launch_bgzf_crc(s.d_raw, s.d_blocks, nblk, s.d_crc, sk::ctx_n_cu(c), st);
-	if (e == hipSuccess) e = sk::launch_bgzf_pack(s.d_raw, s.d_blocks, nblk, s.d_slots, SK_DEFLATE_SLOT, s.d_result, s.d_crc, s.level ? 0 : 1, s.d_msz,
-	                                              s.d_pack[b], sk::ctx_n_cu(c), st);
-	if (e == hipSuccess) e = hipMemcpyAsync(s.h_size + b, s.d_msz + nblk, 8, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipEventRecord(s.ev[b], st);
+	if (e == hipSuccess) e = pack_issue(c, s, raw_len, b, s.ev[b]);
 	if (e != hipSuccess) { *rc = sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_rewrite: window at record %lld: %s", (long long)first, hipGetErrorString(e)); return false; }
 	s.first[b] = first; s.n[b] = n; s.raw[b] = raw_len;
 	return true;
@@ -99,7 +145,6 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, co
                     const std::vector<uint8_t> *more = nullptr)
 {
 	RewriteState &s = *o.s;
-	int krc = SK_OK;
 	// ---- the windows: at most W rewritten bytes each
 	uint64_t mx[3];                                                     // records, rewritten bytes
 	bool room = true;
@@ -108,27 +153,10 @@ static int rw_begin(sk_ctx *c, Cleanup &cl, const Front &fr, const RwOpen &o, co
 	s.header.clear();
 	if (ends & SK_CONCAT_HEADER) s.header = bamfmt::rewrite_header(fr.header, more ? more->data() : nullptr, more ? more->size() : 0);
 	const uint64_t max_raw = std::max<uint64_t>(s.header.size(), mx[1]);
-	// ---- the window area: raw bytes, blocks, deflate scratch and slots, member sizes, two packed buffers (device); two page-locked ones
-	const uint64_t nblk = std::max<uint64_t>(1, (max_raw + SK_DEFLATE_MAX_IN - 1) / SK_DEFLATE_MAX_IN);
-	const uint64_t pack = max_raw + nblk * 31 + 64;
-	const size_t a_raw = up(max_raw + 64), a_blk = up(nblk * 16), a_res = up(nblk * 8), a_crc = up(nblk * 4), a_msz = up((nblk + 1) * 8), a_pack = up(pack);
-	const size_t a_slots = level ? up(nblk * (uint64_t)SK_DEFLATE_SLOT) : 0, a_tok = level ? up(nblk * sk::deflate_tokens_per_block() * 4) : 0;
-	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, a_raw + a_blk + a_res + a_crc + a_msz + 2 * a_pack + a_slots + a_tok, false, &krc);
-	if (!dw) BF_LEAVE(21);
-	const size_t p_pack = up(pack + 28);
-	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * p_pack + 64, true, &krc);
-	if (!hw) BF_LEAVE(21);
-	s.d_raw = dw; s.d_blocks = dw + a_raw; s.d_result = (uint32_t *)(dw + a_raw + a_blk); s.d_crc = (uint32_t *)(dw + a_raw + a_blk + a_res);
-	s.d_msz = (uint64_t *)(dw + a_raw + a_blk + a_res + a_crc);
-	uint8_t *dp = dw + a_raw + a_blk + a_res + a_crc + a_msz;
-	s.d_pack[0] = dp; s.d_pack[1] = dp + a_pack;
-	s.d_slots = level ? dp + 2 * a_pack : nullptr;
-	s.d_tokens = level ? (uint32_t *)(dp + 2 * a_pack + a_slots) : nullptr;
-	s.h_pin[0] = hw; s.h_pin[1] = hw + p_pack; s.h_size = (uint64_t *)(hw + 2 * p_pack);
+	if (!pack_area(c, s, max_raw, level)) BF_LEAVE(21);
 	for (int b = 0; b < 2; b++)
-		if (!blocking_event(s.ev[b]) || !blocking_event(s.ev_copy[b])) BF_LEAVE(21);
-	for (int b = 0; b < 2; b++) BF_HIP(hipEventRecord(s.ev_copy[b], sk::ctx_stream2(c)));   // (nothing to wait for before the first copy)
-	s.write = write; s.level = level;
+		if (!blocking_event(s.ev[b])) BF_LEAVE(21);
+	s.write = write;
 	s.header_done = !(ends & SK_CONCAT_HEADER); s.eof_due = (ends & SK_CONCAT_EOF) != 0;
 	s.begin(fr.d_out, ((Ranges *)sk::ctx_ext(c))->gen);
 	int rc = SK_OK;
@@ -874,10 +902,7 @@ extern "C" int sk_bam_file_rewrite_next(sk_ctx *c, sk_bam_out_window *w)
 	int rc = SK_OK;
 	s.cur = rw_issue(c, s, b ^ 1, &rc) ? (b ^ 1) : -1;                    // (the buffer of the window returned last time: the caller is done with it)
 	if (rc) { s.live = false; return rc; }
-	hipStream_t st2 = sk::ctx_stream2(c);
-	if (bytes) BF_HIP(hipMemcpyAsync(s.h_pin[b], s.d_pack[b], (size_t)bytes, hipMemcpyDeviceToHost, st2));
-	BF_HIP(hipEventRecord(s.ev_copy[b], st2));
-	BF_HIP(hipEventSynchronize(s.ev_copy[b]));
+	BF_HIP(pack_fetch(c, s, b, bytes));
 	if (s.cur < 0 && s.eof_due) { s.eof_due = false; memcpy(s.h_pin[b] + bytes, bamfmt::kBgzfEof, 28); bytes += 28; }   // the last window ends with the EOF block
 	w->first = s.first[b]; w->n = s.n[b];
 	w->bgzf = s.h_pin[b]; w->bytes = bytes; w->raw_bytes = s.raw[b];

@@ -1,5 +1,5 @@
-// sk_bamfile_reads.cpp — sk_bam_file_reads / sk_bam_file_reads_next and sk_bam_file_pairs / sk_bam_file_pairs_next (include/seqkit_hip.h)
-// behind the front half of sk_bamfile.cpp.
+// sk_bamfile_reads.cpp — sk_bam_file_reads / sk_bam_file_reads_next, sk_bam_file_pairs / sk_bam_file_pairs_next and sk_bam_file_pairs_gz /
+// sk_bam_file_pairs_gz_next (include/seqkit_hip.h) behind the front half of sk_bamfile.cpp.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -169,7 +169,14 @@ extern "C" int sk_bam_file_reads_next(sk_ctx *c, sk_bam_reads_window *w)
 // fate, class and partner — and the scratch of the sort and the scans; the scratch lies in the device buffer of the COMPRESSED file, idle
 // once the stream is verified, where it fits there, else behind the kept head.
 
-// plan window w into buffer b: the text kernel, then the copy back; false: no window left
+//
+// sk_bam_file_pairs_gz / sk_bam_file_pairs_gz_next: the same front (pairs_plan), then the window area of the BAM-writing calls
+// (sk_bamfile.h: PackArea) in place of the text buffers.  A window's text is written into its raw area, cut into blocks of at most
+// SK_DEFLATE_MAX_IN bytes wherever the count falls, deflated where it lies and packed into complete members; only those are copied back,
+// on the second stream, while the first runs the following window.  Per window: the text, 31 B and a deflate slot and its tokens per
+// block, and twice the packed bytes on each side.
+
+// plan window w into buffer b: the text kernel, then the copy back or, for members, cut, deflate and pack; false: no window left
 static bool pairs_issue(sk_ctx *c, PairsState &s, int b, int *rc)
 {
 	*rc = SK_OK;
@@ -177,29 +184,35 @@ static bool pairs_issue(sk_ctx *c, PairsState &s, int b, int *rc)
 	const PairsState::Window &w = s.plan[s.next_w++];
 	hipStream_t st = sk::ctx_stream(c);
 	const uint64_t at = s.base[w.stream] + (uint64_t)w.stream;
-	hipError_t e = sk::launch_bam_pair_text(s.d_out, s.krec, s.perm + at, s.soff + at, (int64_t)w.first, (int64_t)w.n, s.fmt, s.min_baseq, s.d_win[b],
+	uint8_t *text = s.members ? s.pk.d_raw : s.d_win[b];
+	hipError_t e = sk::launch_bam_pair_text(s.d_out, s.krec, s.perm + at, s.soff + at, (int64_t)w.first, (int64_t)w.n, s.fmt, s.min_baseq, text,
 	                                        sk::ctx_n_cu(c), st);
-	if (e == hipSuccess && w.bytes) e = hipMemcpyAsync(s.h_win[b], s.d_win[b], (size_t)w.bytes, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipEventRecord(s.ev[b], st);
+	if (s.members) {
+		if (e == hipSuccess) e = pack_issue(c, s.pk, w.bytes, b, s.ev[b]);
+	} else {
+		if (e == hipSuccess && w.bytes) e = hipMemcpyAsync(s.h_win[b], s.d_win[b], (size_t)w.bytes, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipEventRecord(s.ev[b], st);
+	}
 	if (e != hipSuccess) { *rc = sk::ctx_fail(c, SK_ERR_HIP, "sk_bam_file_pairs: window %zu: %s", s.next_w - 1, hipGetErrorString(e)); return false; }
 	s.in[b] = w;
 	return true;
 }
 
-extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_t min_baseq, int interleaved, uint64_t window_bytes, uint64_t counts[8],
-                                 int *handled, double info[8])
+// What sk_bam_file_pairs and sk_bam_file_pairs_gz do behind the front half, up to the per-stream window plan: it leaves the kept records'
+// stream offsets, perm, soff, base[] and plan in the ctx's PairsState and the counts here.  ready = false: the file is left to the caller's
+// reader (info[5] says why).
+struct PairsPlan {
+	bool ready = false;
+	uint64_t K = 0, max_t = 0;                   // kept records; the largest window's text
+	uint32_t P = 0;                              // paired records among them
+	sk::PairRanks tot{0, 0, 0, 0};
+	uint64_t bytes[3] = {0, 0, 0};               // the streams' text
+	double t_size = 0;
+};
+static int pairs_plan(sk_ctx *c, Cleanup &cl, const Front &fr, int format, int interleaved, uint64_t window_bytes, double info[8], PairsPlan &pp)
 {
-	Cleanup cl;
-	Front fr;
-	if (int r = file_call_open(c, path, "sk_bam_file_pairs", handled, info, cl, fr, [&] {
-		    if (counts) for (int i = 0; i < 8; i++) counts[i] = 0;
-		    if (format < 0 || format > 2) return sk::ctx_fail(c, SK_ERR_INVALID, "format = %d", format);
-		    return (int)SK_OK;
-	    }))
-		return r;
-	if (!fr.ready) return SK_OK;
 	hipStream_t st = sk::ctx_stream(c);
-	const double t_size = now_ms();
+	pp.t_size = now_ms();
 	KeptCols kc;
 	if (int r = kept_columns(c, cl, fr, format, interleaved ? 0 : 1, info, kc)) return r;
 	if (!kc.ready) return SK_OK;
@@ -229,7 +242,7 @@ extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_
 	static_assert(sizeof(sk::PairRanks) == 16, "the ranks lie in the two key buffers");
 	// ---- the paired records, sorted by key; fates; ranks
 	BF_HIP(hipMemsetAsync(d_decline, 0, 4, st));
-	uint32_t P = 0;
+	uint32_t &P = pp.P;
 	if (K) {
 		BF_HIP(sk::bam_pair_scan_paired(sb.temp, sb.temp_bytes, kc.kkind, ipos, K, st));
 		BF_HIP(hipMemcpyAsync(&P, ipos + (K - 1), 4, hipMemcpyDeviceToHost, st));
@@ -251,7 +264,7 @@ extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_
 	BF_HIP(sk::launch_bam_pair_holds(skey, lz, P, hs, st));
 	BF_HIP(sk::bam_pair_scan_max(sb.temp, sb.temp_bytes, hs, P, st));
 	BF_HIP(sk::launch_bam_pair_fates(skey, sidx, kc.kkind, lz, hs, P, fate, aux, cls, st));
-	sk::PairRanks tot{0, 0, 0, 0};
+	sk::PairRanks &tot = pp.tot;
 	if (K) {
 		BF_HIP(sk::bam_pair_scan_ranks(sb.temp, sb.temp_bytes, cls, ranks, K, st));
 		BF_HIP(hipMemcpyAsync(&tot, ranks + (K - 1), sizeof tot, hipMemcpyDeviceToHost, st));
@@ -267,7 +280,7 @@ extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_
 	n[2] = interleaved ? 0 : (uint64_t)tot.single + tot.order1 + tot.order2;
 	s.base[0] = 0; s.base[1] = n[0]; s.base[2] = n[0] + n[1];
 	BF_HIP(sk::launch_bam_pair_place(fate, aux, ranks, kc.ktoff, K, kc.T, n, s.base, tot.single, tot.order1, interleaved ? 1 : 0, perm, soff, st));
-	uint64_t bytes[3] = {0, 0, 0};
+	uint64_t (&bytes)[3] = pp.bytes;
 	for (int q = 0; q < 3; q++) {
 		uint64_t *so = soff + s.base[q] + q;
 		BF_HIP(sk::bam_pair_scan_offsets(sb.temp, sb.temp_bytes, so, n[q], st));
@@ -276,7 +289,7 @@ extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_
 	BF_HIP(hipStreamSynchronize(st));
 	// ---- the windows: at most W text bytes each, stream by stream
 	s.plan.clear();
-	uint64_t max_t = 0;
+	uint64_t &max_t = pp.max_t;
 	for (int q = 0; q < 3; q++) {
 		WindowedState ws;
 		std::vector<uint64_t> w0;
@@ -288,35 +301,63 @@ extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_
 			if (ws.ws[w + 1] > ws.ws[w]) s.plan.push_back(PairsState::Window{q, ws.ws[w], ws.ws[w + 1] - ws.ws[w], w0[w + 1] - w0[w]});
 		max_t = std::max(max_t, mx[1]);
 	}
-	// ---- two text buffers, on the device and page-locked
-	int krc = SK_OK;
-	const size_t wbytes = up(max_t + 16);
-	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, 2 * wbytes, false, &krc);
-	if (!dw) BF_LEAVE(21);
-	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * wbytes, true, &krc);
-	if (!hw) BF_LEAVE(21);
-	for (int b = 0; b < 2; b++) {
-		s.d_win[b] = dw + (size_t)b * wbytes; s.h_win[b] = hw + (size_t)b * wbytes;
-		if (!blocking_event(s.ev[b])) BF_LEAVE(21);
-	}
-	s.fmt = format; s.min_baseq = min_baseq;
+	s.fmt = format;
 	s.krec = kc.krec; s.perm = perm; s.soff = soff;
-	s.begin(fr.d_out, R->gen);
+	pp.K = K;
+	pp.ready = true;
+	return SK_OK;
+}
+
+// What both calls end with once their window buffers are there: the first window on its way, the counts, the trace line.
+static int pairs_start(sk_ctx *c, const Front &fr, PairsState &s, const PairsPlan &pp, uint8_t min_baseq, bool members, uint64_t counts[8], int *handled,
+                       double info[8])
+{
+	for (int b = 0; b < 2; b++)
+		if (!blocking_event(s.ev[b])) BF_LEAVE(21);
+	s.min_baseq = min_baseq; s.members = members;
+	s.begin(fr.d_out, ((Ranges *)sk::ctx_ext(c))->gen);
 	int rc = SK_OK;
 	if (pairs_issue(c, s, 0, &rc)) s.cur = 0;
 	if (rc) return rc;
 	s.live = true;
 	if (counts) {
-		counts[0] = tot.pair; counts[1] = tot.single; counts[2] = tot.order1; counts[3] = tot.order2;
-		counts[4] = (uint64_t)P - 2ull * tot.pair - tot.order1 - tot.order2;
-		for (int q = 0; q < 3; q++) counts[5 + q] = bytes[q];
+		counts[0] = pp.tot.pair; counts[1] = pp.tot.single; counts[2] = pp.tot.order1; counts[3] = pp.tot.order2;
+		counts[4] = (uint64_t)pp.P - 2ull * pp.tot.pair - pp.tot.order1 - pp.tot.order2;
+		for (int q = 0; q < 3; q++) counts[5 + q] = pp.bytes[q];
 	}
 	*handled = 1;
 	char tail[160];
-	snprintf(tail, sizeof tail, "; %llu kept, %u pairs, %llu text bytes, %zu windows", (unsigned long long)K, tot.pair,
-	         (unsigned long long)(bytes[0] + bytes[1] + bytes[2]), s.plan.size());
-	file_call_close(fr, "size + index + pair + plan", t_size, tail, info);
+	snprintf(tail, sizeof tail, "; %llu kept, %u pairs, %llu text bytes, %zu windows", (unsigned long long)pp.K, pp.tot.pair,
+	         (unsigned long long)(pp.bytes[0] + pp.bytes[1] + pp.bytes[2]), s.plan.size());
+	file_call_close(fr, "size + index + pair + plan", pp.t_size, tail, info);
 	return SK_OK;
+}
+
+extern "C" int sk_bam_file_pairs(sk_ctx *c, const char *path, int format, uint8_t min_baseq, int interleaved, uint64_t window_bytes, uint64_t counts[8],
+                                 int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_pairs", handled, info, cl, fr, [&] {
+		    if (counts) for (int i = 0; i < 8; i++) counts[i] = 0;
+		    if (format < 0 || format > 2) return sk::ctx_fail(c, SK_ERR_INVALID, "format = %d", format);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	PairsPlan pp;
+	if (int r = pairs_plan(c, cl, fr, format, interleaved, window_bytes, info, pp)) return r;
+	if (!pp.ready) return SK_OK;
+	PairsState &s = ((Ranges *)sk::ctx_ext(c))->pairs;
+	// ---- two text buffers, on the device and page-locked
+	int krc = SK_OK;
+	const size_t wbytes = up(pp.max_t + 16);
+	uint8_t *dw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFileWin, 2 * wbytes, false, &krc);
+	if (!dw) BF_LEAVE(21);
+	uint8_t *hw = (uint8_t *)sk::ctx_keep(c, sk::kKeepFilePin, 2 * wbytes, true, &krc);
+	if (!hw) BF_LEAVE(21);
+	for (int b = 0; b < 2; b++) { s.d_win[b] = dw + (size_t)b * wbytes; s.h_win[b] = hw + (size_t)b * wbytes; }
+	return pairs_start(c, fr, s, pp, min_baseq, false, counts, handled, info);
 }
 
 extern "C" int sk_bam_file_pairs_next(sk_ctx *c, sk_bam_pairs_window *w)
@@ -324,7 +365,7 @@ extern "C" int sk_bam_file_pairs_next(sk_ctx *c, sk_bam_pairs_window *w)
 	if (!c || !w) return SK_ERR_INVALID;
 	memset(w, 0, sizeof *w);
 	Ranges *R = (Ranges *)sk::ctx_ext(c);
-	if (!R || !R->pairs.current(R->gen)) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_pairs_next: no sk_bam_file_pairs in progress");
+	if (!R || !R->pairs.current(R->gen) || R->pairs.members) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_pairs_next: no sk_bam_file_pairs in progress");
 	if (int r = sk::ctx_bind(c)) return r;
 	PairsState &s = R->pairs;
 	const int b = s.cur;
@@ -335,5 +376,48 @@ extern "C" int sk_bam_file_pairs_next(sk_ctx *c, sk_bam_pairs_window *w)
 	BF_HIP(hipEventSynchronize(s.ev[b]));
 	w->stream = s.in[b].stream; w->first = (int64_t)s.in[b].first; w->n = (int64_t)s.in[b].n;
 	w->text = s.h_win[b]; w->bytes = s.in[b].bytes;
+	return SK_OK;
+}
+
+extern "C" int sk_bam_file_pairs_gz(sk_ctx *c, const char *path, int format, uint8_t min_baseq, int level, uint64_t window_bytes, uint64_t counts[8],
+                                    int *handled, double info[8])
+{
+	Cleanup cl;
+	Front fr;
+	if (int r = file_call_open(c, path, "sk_bam_file_pairs_gz", handled, info, cl, fr, [&] {
+		    if (counts) for (int i = 0; i < 8; i++) counts[i] = 0;
+		    if (format < 0 || format > 2) return sk::ctx_fail(c, SK_ERR_INVALID, "format = %d", format);
+		    if (level < 0 || level > 1) return sk::ctx_fail(c, SK_ERR_INVALID, "level = %d", level);
+		    return (int)SK_OK;
+	    }))
+		return r;
+	if (!fr.ready) return SK_OK;
+	PairsPlan pp;
+	if (int r = pairs_plan(c, cl, fr, format, 0, window_bytes, info, pp)) return r;
+	if (!pp.ready) return SK_OK;
+	PairsState &s = ((Ranges *)sk::ctx_ext(c))->pairs;
+	if (!pack_area(c, s.pk, pp.max_t, level)) BF_LEAVE(21);
+	return pairs_start(c, fr, s, pp, min_baseq, true, counts, handled, info);
+}
+
+extern "C" int sk_bam_file_pairs_gz_next(sk_ctx *c, sk_bam_pairs_gz_window *w)
+{
+	if (!c || !w) return SK_ERR_INVALID;
+	memset(w, 0, sizeof *w);
+	Ranges *R = (Ranges *)sk::ctx_ext(c);
+	if (!R || !R->pairs.current(R->gen) || !R->pairs.members) return sk::ctx_fail(c, SK_ERR_INVALID, "sk_bam_file_pairs_gz_next: no sk_bam_file_pairs_gz in progress");
+	if (int r = sk::ctx_bind(c)) return r;
+	PairsState &s = R->pairs;
+	const int b = s.cur;
+	if (b < 0) return SK_OK;                                            // the end
+	BF_HIP(hipEventSynchronize(s.ev[b]));
+	const uint64_t bytes = s.pk.h_size[b];
+	const PairsState::Window in = s.in[b];
+	int rc = SK_OK;
+	s.cur = pairs_issue(c, s, b ^ 1, &rc) ? (b ^ 1) : -1;                 // (the buffer of the window returned last time: the caller is done with it)
+	if (rc) { s.live = false; return rc; }
+	BF_HIP(pack_fetch(c, s.pk, b, bytes));
+	w->stream = in.stream; w->first = (int64_t)in.first; w->n = (int64_t)in.n;
+	w->bgzf = s.pk.h_pin[b]; w->bytes = bytes; w->raw_bytes = in.bytes;
 	return SK_OK;
 }

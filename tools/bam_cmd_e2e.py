@@ -56,7 +56,9 @@ The stdout and stderr of both paths are compared on every run.
 --no-gz, `sam to fastq <prefix>` to files, each with the mates paired on the device (SEQKIT_DEVICE_PAIRING=1), paired on the host over the device's
 texts (SEQKIT_HOST_PAIRING=1) and, with --yardstick-sam, by another build's `sam` (the parent commit's), alternating.  Wall and CPU-seconds
 of every run, each row's spread (max - min), and default / yardstick run for run.  The .gz files of the first run of every row are
-compared decompressed.  Then sk_bam_file_pairs' library-call time and its windows drained, next to sk_bam_file_reads'.
+compared decompressed.  To files the device pairing also deflates and frames the outputs there (sk_bam_file_pairs_gz); one more row, device
+pairing with SEQKIT_GPU_DEFLATE=0, separates the pairing from the deflate.  Then sk_bam_file_pairs' and sk_bam_file_pairs_gz's library-call
+times and their windows drained, next to sk_bam_file_reads'.
 
 --merge: the subsample file, and its records dealt alternately (record j of a repeat to part j mod P) into P = 2 and P = 8 position-
 sorted parts.  Mates share a position, so every key occurs in two parts: with ties by input the merge writes the undealt file's records
@@ -318,15 +320,19 @@ def pairing_rows():
         modes.append(("sam to fastq <prefix>", ["to", "fastq", bam, os.path.join(d, "o")], os.path.join(d, "o")))
     for label, args, prefix in modes:
         rows, seen = {}, set()
+        # to files, the device pairing deflates there too (sk_bam_file_pairs_gz): one more row separates the pairing from the deflate
+        more = [("device pairing, SEQKIT_GPU_DEFLATE=0", SAM, {"SEQKIT_DEVICE_PAIRING": "1", "SEQKIT_GPU_DEFLATE": "0"})] if prefix else []
         for k in range(runs):
-            for name, binary, env in variants:
+            for name, binary, env in variants + more:
                 dt, cpu, rc, _, err = timed([binary] + args, env, sink=os.devnull)
                 assert rc == 0, (label, name, rc, err[-400:])
                 rows.setdefault(name, []).append((dt, cpu))
-                if prefix:
-                    h = gz_digest(prefix)
-                    if k == 0:
-                        seen.add(h)
+                if prefix and k == 0:
+                    seen.add(gz_digest(prefix))
+                elif prefix:                                                # (the later runs' files are only removed)
+                    for f in os.listdir(d):
+                        if f.startswith(os.path.basename(prefix)) and f.endswith(".gz"):
+                            os.remove(os.path.join(d, f))
         assert len(seen) <= 1, f"{label}: outputs differ: {seen}"
         for name, r in rows.items():
             w = [x[0] for x in r]
@@ -337,6 +343,7 @@ def pairing_rows():
             print(f"{label:36s} device pairing / yardstick, run for run: " + " ".join(f"{x / y:.2f}x" for x, y in zip(a, b))
                   + f"; medians {float(np.median(a)) / float(np.median(b)):.2f}x; median difference {float(np.median(b)) - float(np.median(a)):+.2f} s "
                   f"against the yardstick's max - min {max(b) - min(b):.2f} s" + ("; decompressed outputs identical" if prefix else ""), flush=True)
+            print(f"{label:36s} yardstick - device pairing, run for run: " + " ".join(f"{y - x:+.2f}" for x, y in zip(a, b)) + " s", flush=True)
     tr = subprocess.run([SAM, "to", "interleaved", "fastq", bam], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, env=dict(os.environ, SK_BAMFILE_TRACE="1")).stderr
     print("trace of the default: " + str([ln for ln in tr.decode(errors="replace").split("\n") if ln.startswith("sam ")]), flush=True)
 
@@ -934,6 +941,22 @@ with seqkit_amd.Context(0) as ctx:
         assert h
         print(f"library call, {n} records: sk_bam_file_pairs (fastq{', interleaved' if inter else ''}) {1e3 * (t1 - t0):.0f} ms, {counts[0]} pairs, "
               f"{sum(counts[5:]) / 1e9:.2f} GB of text; {nw} windows drained in {1e3 * (t2 - t1):.0f} ms", flush=True)
+    # sk_bam_file_pairs_gz (fastq, level 1) and its windows: the three streams deflated and framed on the device, the members copied back
+    t0 = time.perf_counter()
+    h, counts, _ = ctx.bam_file_pairs_gz(bam, "fastq", 10, 1)
+    t1 = time.perf_counter()
+    gw = capi._PairsGzWindow()
+    nw = packed = 0
+    while True:
+        ctx._check(ctx._lib.sk_bam_file_pairs_gz_next(ctx._h, capi.C.byref(gw)), "sk_bam_file_pairs_gz_next")
+        if gw.n == 0:
+            break
+        nw += 1
+        packed += gw.bytes
+    t2 = time.perf_counter()
+    assert h
+    print(f"library call, {n} records: sk_bam_file_pairs_gz (fastq, level 1) {1e3 * (t1 - t0):.0f} ms, {counts[0]} pairs, "
+          f"{sum(counts[5:]) / 1e9:.2f} GB of text in {packed / 1e9:.2f} GB of members; {nw} windows drained in {1e3 * (t2 - t1):.0f} ms", flush=True)
 os.remove(bam)
 if lib_only or pairing:
     os.rmdir(d)
